@@ -1,6 +1,18 @@
 """bench.py -- aligned 512x512 faces/sec of the MI355X-native CodeFormer path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N=1: plain python; N>1: launched by torchrun, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                                                           (N=1: plain python; N>1: launched by torchrun, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given, and prints the line
+with the headline (`value`, `ms_per_step`, `dtype`, `config`, `whole_path`).  Everything else described below (the golden-face
+gates, `roofline`, the f16x2 / config-3 legs, `cpu_baseline`, --details) runs only with --full; the --no-* options select among it.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed back as float32 .npy files (< 64 MB in all):
+  faces.npy         the restored faces (on rank 0, every rank's; more than 16: a fixed seeded sample of 16 faces, in order)
+  logits.npy        rank 0's code logits, a fixed seeded sample of 1024 (face, token) rows
+  lq_feat.npy       rank 0's encoder features (more than 16 faces: a fixed seeded sample of 16)
+  code_indices.npy  rank 0's code indices (net.last_indices), every face
+Inputs and weights are seeded, so two builds run with the same arguments can be compared file for file.
 
 A "step" is one CodeFormer.forward(x, w=0.5, adain=True) over one batch of 16 synthetic faces per GPU (config 2 of
 BASELINE.json: seeded rand(16,3,512,512)*2-1, seed-0 random-init weights unless weights/CodeFormer/codeformer.pth exists)
@@ -8,10 +20,10 @@ followed, for N>1, by the single gather of the restored faces to rank 0 (left in
 gathers are joined inside the timed region).  Inputs are resident in HBM before the timed region; host PNG decode/encode is
 outside the path and outside the timed region.  Weak scaling: 16 faces per GPU.
 
-The headline (`value`, `ms_per_step`, `dtype`, `roofline`) is the IEEE-fp32 evaluation -- BASELINE config 2 to the letter
+The headline (`value`, `ms_per_step`, `dtype`) is the IEEE-fp32 evaluation -- BASELINE config 2 to the letter
 (--precision fp32, the default since round 6): every product of every convolution / Linear / attention on fp32 MFMA operands, fp32
 tensors, fp32 accumulation (Winograd F(2x2,3x3) / F(4x4,3x3) where eligible: the same function in another summation order than
-ATen's).  At N=1 the default run also gates and times two secondary legs and reports them as SCALARS (top level and, mirrored,
+ATen's).  At N=1 a --full run also gates and times two secondary legs and reports them as SCALARS (top level and, mirrored,
 inside `config`, so that no consumer has to dig through nested objects):
   f16x2_*         the same step with precision='f16x2' (the module's product default): fp32 tensors / accumulation, the 3x3 / image-sized
                   1x1 / LayerNorm-bounded Linear products on split operands (fp32 = hi + lo IEEE halves, three f16 MFMAs per product:
@@ -22,7 +34,7 @@ inside `config`, so that no consumer has to dig through nested objects):
 The whole JSON line stays under 2 KB; the long-form records (every kernel class of every leg, gate derivations, sample descriptions)
 go to stderr with --details.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line with the contract fields plus, with --full,
   roofline:     the kernel class with the largest summed duration of a step, timed live per launch with events on the launch stream:
                 `achieved` / `frac` against the dense peak of the MFMA type it issues (fp32: 157.3 TFLOP/s, f16: 2500; MI355X_MICROARCH.md).
                 For a Winograd kernel on un-split operands (fewer multiplies than the direct form) achieved = EXECUTED MFMA FLOPs /
@@ -307,6 +319,25 @@ def compact_roofline(r):
     return out
 
 
+def sample_rows(t, n, seed):
+    """t when it has at most n rows (dim 0), else n of its rows chosen with a fixed seed, kept in order."""
+    if t.shape[0] <= n:
+        return t
+    keep = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    return t[keep.to(t.device)]
+
+
+def dump_outputs(d, faces, local, indices):
+    """--dump-outputs: the last timed step's outputs as float32 DIR/<name>.npy (see the module docstring)."""
+    import numpy as np
+    _, logits, lq_feat = local
+    arrays = {'faces': sample_rows(faces, 16, 0), 'logits': sample_rows(logits.reshape(-1, logits.shape[-1]), 1024, 1),
+              'lq_feat': sample_rows(lq_feat, 16, 2), 'code_indices': indices}
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, f'{name}.npy'), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -318,6 +349,9 @@ def main():
                     help="arithmetic of the headline: fp32 (default) = IEEE-fp32 MFMA operands everywhere, BASELINE config 2 to the letter; "
                          "f16x2 = fp32 operands split into hi+lo IEEE halves (22-bit operands, the module's product default); bf16 / fp16 = 16-bit "
                          "operands (bf16: also 16-bit storage) in generator + CFT (BASELINE configs 3/5), encoder on split halves")
+    ap.add_argument('--dump-outputs', metavar='DIR', help="after the timed steps, write the last step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument('--full', action='store_true', help='also run the gates, the roofline, the f16x2 / config-3 legs and the CPU baseline '
+                                                        '(selected by the --no-* options below)')
     ap.add_argument('--no-parity-gate', action='store_true', help='skip the golden-face check that precedes the timed region')
     ap.add_argument('--no-f16x2-leg', '--no-exact-leg', dest='no_f16x2_leg', action='store_true', help="skip the secondary precision='f16x2' timing of the default run")
     ap.add_argument('--no-config3-leg', action='store_true', help='skip the bf16 / w=0.7 timing (one rank of BASELINE config 3) of the default run')
@@ -325,6 +359,8 @@ def main():
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--details', action='store_true', help='print the long-form record (every kernel class of every leg, gates, samples) to stderr')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     import torch.distributed as dist
     from codeformer_amd import lib, parallel
@@ -345,12 +381,13 @@ def main():
     # One gather is kept in flight: step i's restored faces travel to rank 0 (RCCL, its own stream) while step i+1 computes.
     # Every gather of the timed steps is joined before the closing synchronize, so the K steps are complete inside the bracket.
     parity = None
-    if rank == 0 and not args.no_parity_gate and args.precision in ('fp32', 'f16x2'):
+    if args.full and rank == 0 and not args.no_parity_gate and args.precision in ('fp32', 'f16x2'):
         parity = parity_gate(net, sd_cpu, weights, args.w)     # raises before anything is timed if the path does not match the reference
     pending = [None]
+    local = [None]      # the last step's (faces, logits, lq_feat) on this rank
 
     def step():
-        handle, _ = parallel.restore_sharded_async(net, x, total, w=args.w, adain=True, dst=0)
+        handle, local[0] = parallel.restore_sharded_async(net, x, total, w=args.w, adain=True, dst=0)
         prev, pending[0] = pending[0], handle
         return prev.wait() if prev is not None else None
 
@@ -368,7 +405,7 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
-    drain()
+    faces = drain()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -378,6 +415,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, faces, local[0], net.last_indices)
 
     if rank == 0:
         faces_per_s = args.steps * total / dt
@@ -400,7 +439,7 @@ def main():
             line['parity'] = {k: parity[k] for k in ('max_abs_pixel_diff', 'max_abs_logit_diff', 'code_indices_equal')}
             line['parity']['against'] = 'reference golden' if 'golden' in parity['against'] else 'CPU oracle'
             details['parity'] = parity
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             roof, table = roofline_leg(net, x, args.w)
             ex = roof.pop('executed_gflop_per_face_whole_path')      # products really evaluated (folded upsample taps, Winograd 4/9 / 1/4)
             details['roofline'] = roof
@@ -433,7 +472,7 @@ def main():
             if key.endswith(('_faces_per_s', '_ms_per_step')):
                 line['config'][key] = val
 
-        secondary = world == 1 and args.precision == 'fp32' and config2
+        secondary = args.full and world == 1 and args.precision == 'fp32' and config2
         if secondary and not args.no_f16x2_leg:
             y_exact = net(x, w=args.w, adain=True)
             net.precision = 'f16x2'
@@ -468,7 +507,7 @@ def main():
             if args.details and not args.no_roofline:
                 details['config3_rank']['roofline'] = leg_roofline(0.7)
             net.precision = args.precision
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline_leg(sd_cpu, args.w)
             details['cpu_baseline'] = dict(cb)
             cb['sample'] = cb['sample_short']
@@ -485,7 +524,7 @@ def main():
             for k in [k for k in line['config'] if k.startswith(('f16x2_', 'config3_'))]:
                 del line['config'][k]
             out = json.dumps(line)
-        if args.details:
+        if args.full and args.details:
             print(json.dumps(details, indent=1), file=sys.stderr)
         print(out, flush=True)
     if world > 1:

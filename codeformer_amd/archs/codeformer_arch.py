@@ -12,6 +12,7 @@ codeformer_amd/csrc with channels-last activations:
   -> logits GEMM -> wavefront-shuffle argmax (== softmax+topk(1), lowest index on ties) -> codebook gather (+AdaIN)
   -> generator with the controllable feature transform fused into conv gathers / epilogues.
 """
+import gc
 import os
 import threading
 
@@ -455,8 +456,16 @@ class CodeFormer(VQAutoEncoder):
                     ops._act_cells(x.device, 4 * max(int(x.shape[0]), 1))
                     ops._counters(x.device, 4096)
                 cap.synchronize()
-                with torch.cuda.graph(graph, stream=cap):
-                    outs = self._forward_hip(static_x, w, code_only, adain)
+                # No garbage collection while capturing: a dead network (each one holds itself in _sig_modules, so it waits for the
+                # cyclic collector) takes its captured graphs with it, and tearing a graph down during a capture aborts the process.
+                gc_on = gc.isenabled()
+                gc.disable()
+                try:
+                    with torch.cuda.graph(graph, stream=cap):
+                        outs = self._forward_hip(static_x, w, code_only, adain)
+                finally:
+                    if gc_on:
+                        gc.enable()
                 ent = {'graph': graph, 'x': static_x, 'outs': outs, 'epoch': PACK_EPOCH[0], 'sig': sig, 'idx': getattr(self, 'last_indices', None)}
                 self._graphs.pop(key, None)
                 while len(self._graphs) >= 4:           # oldest first: a graph pins the activations of its shape

@@ -2,7 +2,7 @@
 # One-face call, graph replay: kernel timeline (rocprofv3 --kernel-trace) of N replays -> busy time, gaps and per-class sums per forward.
 # usage (GPU box, repo root): bash tools/b1_timeline.sh [batch] [tag]
 b=${1:-1}; tag=${2:-b$b}
-mkdir -p gpurun_out; export TMPDIR=/tmp
+mkdir -p run_out; export TMPDIR=/tmp
 cat > /tmp/b1_run.py <<PY
 import sys, torch
 sys.path.insert(0, '.')
@@ -24,7 +24,7 @@ print('ms per call', (time.perf_counter() - t) / 20 * 1e3)
 PY
 rm -rf /tmp/b1prof && timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/b1prof -o t -- python /tmp/b1_run.py 2>&1 | grep "ms per call"
 f=$(find /tmp/b1prof -name '*kernel_trace.csv' | head -1)
-python - "$f" <<'PY' | tee gpurun_out/b1_timeline_$tag.txt
+python - "$f" <<'PY' | tee run_out/b1_timeline_$tag.txt
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
