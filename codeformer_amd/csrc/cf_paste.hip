@@ -10,6 +10,9 @@
 //   inv_soft_mask*pasted + (1-inv_soft_mask)*img, parse-mask fusion   -> blend_kernel (samples the restored face itself)
 //   cv2.resize(INTER_LINEAR) of the background, final astype(uint8)   -> resize_u8_kernel, trunc_u8_kernel
 //   cv2.resize(INTER_AREA) of the frame for the detector (:208-215)    -> resize_area_u8_kernel
+//   cv2.resize(float32, INTER_LINEAR) of the parse masks (:482)        -> resize_f32_kernel
+//   draw_box blend (:439-445, :502-509) + astype(uint8) + imwrite      -> box_overlay_kernel
+//   RealESRGANer pre_process / tile crop / post_process of the faces   -> esr_gather_kernel, esr_scatter_kernel (face upsampler, :389)
 //
 // The arithmetic follows OpenCV's fixed-point definitions (restated with citations in oracle/paste_oracle.py): source coordinates
 // in 10-bit fixed point from per-axis rounded terms, +1/64 px, truncated to 1/32 px; uint8 taps weighted with the 15-bit table and
@@ -69,6 +72,17 @@ __global__ __launch_bounds__(256) void warp_u8_kernel(const uint8_t* __restrict_
   }
 }
 
+// float taps of a warpAffine sample: float weights from the 1/32-pixel fractions, accumulated in the order 00, 01, 10, 11
+__device__ __forceinline__ float taps_f32(float p00, float p01, float p10, float p11, int a, int b) {
+  const float fa = (float)a / 32.0f, fb = (float)b / 32.0f;
+  float acc = 0.f;
+  acc = add_rn(acc, mul_rn(p00, mul_rn(1.f - fa, 1.f - fb)));
+  acc = add_rn(acc, mul_rn(p01, mul_rn(fa, 1.f - fb)));
+  acc = add_rn(acc, mul_rn(p10, mul_rn(1.f - fa, fb)));
+  acc = add_rn(acc, mul_rn(p11, mul_rn(fa, fb)));
+  return acc;
+}
+
 // float32 single-channel source [sh][sw] -> compact region buffer [rh][rw] (border 0)
 __global__ __launch_bounds__(256) void warp_f32_kernel(const float* __restrict__ src, int sh, int sw, Inv6 v, float* __restrict__ dst,
                                                        int rx, int ry, int rw, int rh) {
@@ -77,14 +91,127 @@ __global__ __launch_bounds__(256) void warp_f32_kernel(const float* __restrict__
   const int x = rx + (int)(i % rw), y = ry + (int)(i / rw);
   int ix, iy, a, b;
   warp_coord(v, x, y, ix, iy, a, b);
-  const float fa = (float)a / 32.0f, fb = (float)b / 32.0f;
   const bool x0 = ix >= 0 && ix < sw, x1 = ix + 1 >= 0 && ix + 1 < sw, y0 = iy >= 0 && iy < sh, y1 = iy + 1 >= 0 && iy + 1 < sh;
-  float acc = 0.f;
-  acc = add_rn(acc, mul_rn((x0 && y0) ? src[(long)iy * sw + ix] : 0.f, mul_rn(1.f - fa, 1.f - fb)));
-  acc = add_rn(acc, mul_rn((x1 && y0) ? src[(long)iy * sw + ix + 1] : 0.f, mul_rn(fa, 1.f - fb)));
-  acc = add_rn(acc, mul_rn((x0 && y1) ? src[(long)(iy + 1) * sw + ix] : 0.f, mul_rn(1.f - fa, fb)));
-  acc = add_rn(acc, mul_rn((x1 && y1) ? src[(long)(iy + 1) * sw + ix + 1] : 0.f, mul_rn(fa, fb)));
-  dst[i] = acc;
+  dst[i] = taps_f32((x0 && y0) ? src[(long)iy * sw + ix] : 0.f, (x1 && y0) ? src[(long)iy * sw + ix + 1] : 0.f,
+                    (x0 && y1) ? src[(long)(iy + 1) * sw + ix] : 0.f, (x1 && y1) ? src[(long)(iy + 1) * sw + ix + 1] : 0.f, a, b);
+}
+
+// draw_box (face_restoration_helper.py:439-445, :499-509) fused with the final astype(uint8): every pixel truncates the canvas, then each
+// face whose box bounding box (x0, y0, x1, y1) holds it, in face order, blends green with m = warp of its border-band mask (1 on the outer
+// `border` pixels of the fh x fw face, 0 inside and outside the face: mask[border:h-border, border:w-border] = 0), sampled like
+// warp_f32_kernel; v = m * colour + (1 - m) * v in separately rounded float32; cv2.imwrite's conversion (rint, saturate) at the end.
+// faces: per face 11 doubles = dst->src matrix (6), border, x0, y0, x1, y1.
+__device__ __forceinline__ float band_px(int ix, int iy, int fw, int fh, int border) {
+  if (ix < 0 || ix >= fw || iy < 0 || iy >= fh) return 0.f;
+  return (ix >= border && ix < fw - border && iy >= border && iy < fh - border) ? 0.f : 1.f;
+}
+__global__ __launch_bounds__(256) void box_overlay_kernel(const float* __restrict__ canvas, int ch, int cw, const double* __restrict__ faces,
+                                                          int nf, int fh, int fw, uint8_t* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)cw * ch) return;
+  const int x = (int)(i % cw), y = (int)(i / cw);
+  const float colour[3] = {0.f, 255.f, 0.f};  // BGR
+  float v[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = (float)(int)canvas[i * 3 + c];
+  for (int k = 0; k < nf; ++k) {
+    const double* f = faces + (long)k * 11;
+    if (x < (int)f[7] || y < (int)f[8] || x >= (int)f[9] || y >= (int)f[10]) continue;
+    Inv6 m6;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) m6.m[j] = f[j];
+    const int border = (int)f[6];
+    int ix, iy, a, b;
+    warp_coord(m6, x, y, ix, iy, a, b);
+    const float m = taps_f32(band_px(ix, iy, fw, fh, border), band_px(ix + 1, iy, fw, fh, border), band_px(ix, iy + 1, fw, fh, border),
+                             band_px(ix + 1, iy + 1, fw, fh, border), a, b);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = add_rn(mul_rn(m, colour[c]), mul_rn(sub_rn(1.0f, m), v[c]));
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float r = rintf(v[c]);
+    out[i * 3 + c] = (uint8_t)(r < 0.f ? 0 : (r > 255.f ? 255 : (int)r));
+  }
+}
+
+// cv2.resize(float32, INTER_LINEAR) of single-channel planes [batch][sh][sw] -> [batch][dh][dw] (OpenCV's generic float path): per axis
+// f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s, clamped to (0, 0) / (n - 1, 0) at the edges; rows are filtered
+// horizontally first (src[s] * (1 - fx) + src[s + 1] * fx, a plain copy of src[s] where s + 1 is past the edge), then vertically
+// (r0 * (1 - fy) + r1 * fy), every multiply and add separately rounded
+__device__ __forceinline__ void linear_axis_f32(int d, int nsrc, double scale, int& s, float& f) {
+  f = (float)(((double)d + 0.5) * scale - 0.5);
+  s = (int)floorf(f);
+  f = sub_rn(f, (float)s);
+  if (s < 0) {
+    s = 0;
+    f = 0.f;
+  }
+  if (s >= nsrc - 1) {
+    s = nsrc - 1;
+    f = 0.f;
+  }
+}
+__global__ __launch_bounds__(256) void resize_f32_kernel(const float* __restrict__ src, int sh, int sw, float* __restrict__ dst, int dh,
+                                                         int dw, double scale_x, double scale_y) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)dw * dh) return;
+  const int x = (int)(i % dw), y = (int)(i / dw);
+  const float* s = src + (long)blockIdx.y * sh * sw;
+  int sx, sy;
+  float fx, fy;
+  linear_axis_f32(x, sw, scale_x, sx, fx);
+  linear_axis_f32(y, sh, scale_y, sy, fy);
+  const int sy1 = min(sy + 1, sh - 1);
+  const float* r0 = s + (long)sy * sw;
+  const float* r1 = s + (long)sy1 * sw;
+  float h0 = r0[sx], h1 = r1[sx];
+  if (sx + 1 < sw) {
+    h0 = add_rn(mul_rn(r0[sx], sub_rn(1.f, fx)), mul_rn(r0[sx + 1], fx));
+    h1 = add_rn(mul_rn(r1[sx], sub_rn(1.f, fx)), mul_rn(r1[sx + 1], fx));
+  }
+  dst[(long)blockIdx.y * dh * dw + i] = add_rn(mul_rn(h0, sub_rn(1.f, fy)), mul_rn(h1, fy));
+}
+
+// Face upsampler tile I/O (RealESRGANer, codeformer_amd/utils/realesrgan_utils.py).  Gather: uint8 BGR faces [n][h][w][3] -> the model's
+// fp32 NCHW RGB input [n][3][th][tw] = window (py0, px0) of the padded view pre_process builds (reflect pre-pad of `pre_pad` on the
+// right / bottom, then reflect pad up to a multiple of `mod`), / 255 through a 256-entry table of correctly rounded quotients.
+__device__ __forceinline__ int esr_source(int i, int n, int n1) {  // padded index -> source index (n1 = n + pre_pad)
+  if (i >= n1) i = 2 * (n1 - 1) - i;                                // F.pad(reflect) of the pre-padded image
+  if (i >= n) i = 2 * (n - 1) - i;                                  // F.pad(reflect) of the face
+  return i;
+}
+__global__ __launch_bounds__(256) void esr_gather_kernel(const uint8_t* __restrict__ faces, int h, int w, int h1, int w1, int py0, int px0,
+                                                         int th, int tw, float* __restrict__ out) {
+  __shared__ float lut[256];
+  lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0);
+  __syncthreads();
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long plane = (long)th * tw;
+  if (i >= plane) return;
+  const int x = (int)(i % tw), y = (int)(i / tw);
+  const int sy = esr_source(py0 + y, h, h1), sx = esr_source(px0 + x, w, w1);
+  const uint8_t* p = faces + (((long)blockIdx.y * h + sy) * w + sx) * 3;
+  float* o = out + (long)blockIdx.y * 3 * plane + i;
+  o[0] = lut[p[2]];
+  o[plane] = lut[p[1]];
+  o[2 * plane] = lut[p[0]];
+}
+// Scatter: rows oy.. / columns ox.. (ch x cw) of the model's NCHW RGB output [n][3][uh][uw] -> (dy, dx) of the uint8 BGR faces
+// [n][oh][ow][3]: clamp(0, 1), * 255.0f, rint (enhance: clamp_, np.round(out * 255.0), astype(uint8))
+__global__ __launch_bounds__(256) void esr_scatter_kernel(const float* __restrict__ up, int uh, int uw, int oy, int ox, int ch, int cw,
+                                                          uint8_t* __restrict__ out, int oh, int ow, int dy, int dx) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)ch * cw) return;
+  const int c = (int)(i % cw), r = (int)(i / cw);
+  const long plane = (long)uh * uw;
+  const float* s = up + (long)blockIdx.y * 3 * plane + (long)(oy + r) * uw + ox + c;
+  uint8_t* o = out + (((long)blockIdx.y * oh + dy + r) * ow + dx + c) * 3;
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    const float v = fminf(fmaxf(s[(2 - b) * plane], 0.f), 1.f);
+    o[b] = (uint8_t)(int)rintf(mul_rn(v, 255.0f));
+  }
 }
 
 // 1-D minimum over [-lo, +hi] along x (axis 0) or y (axis 1); samples outside the region do not take part (+inf)
@@ -433,5 +560,52 @@ extern "C" int cf_scale_clear_border_f32(float* x, int batch, int h, int w, int 
   const long n = (long)batch * h * w;
   hipLaunchKernelGGL(scale_clear_border_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)stream, x, h, w, n, border, scale);
   CF_CHECK_LAUNCH("cf_scale_clear_border_f32");
+  return CF_OK;
+}
+
+extern "C" int cf_box_overlay_u8(const float* canvas, int ch, int cw, const double* faces_dev, int nfaces, int fh, int fw, uint8_t* out,
+                                 cf_stream_t stream) {
+  CF_REQUIRE(canvas && out && ch > 0 && cw > 0 && nfaces >= 0 && (faces_dev || nfaces == 0) && fh > 0 && fw > 0,
+             "cf_box_overlay_u8: bad args");
+  hipLaunchKernelGGL(box_overlay_kernel, dim3(nblk((long)ch * cw)), dim3(256), 0, (hipStream_t)stream, canvas, ch, cw, faces_dev, nfaces, fh,
+                     fw, out);
+  CF_CHECK_LAUNCH("cf_box_overlay_u8");
+  return CF_OK;
+}
+
+extern "C" int cf_resize_linear_f32(const float* src, int batch, int sh, int sw, float* dst, int dh, int dw, cf_stream_t stream) {
+  CF_REQUIRE(src && dst && batch > 0 && batch <= 65535 && sh > 0 && sw > 0 && dh > 0 && dw > 0, "cf_resize_linear_f32: bad args");
+  hipLaunchKernelGGL(resize_f32_kernel, dim3(nblk((long)dh * dw), batch), dim3(256), 0, (hipStream_t)stream, src, sh, sw, dst, dh, dw,
+                     (double)sw / dw, (double)sh / dh);
+  CF_CHECK_LAUNCH("cf_resize_linear_f32");
+  return CF_OK;
+}
+
+extern "C" int cf_esrgan_tile_gather_u8(const uint8_t* faces, int n, int h, int w, int pre_pad, int mod, int py0, int px0, int th, int tw,
+                                        float* out, cf_stream_t stream) {
+  CF_REQUIRE(faces && out && n > 0 && n <= 65535 && h > 0 && w > 0 && mod > 0 && th > 0 && tw > 0, "cf_esrgan_tile_gather_u8: bad args");
+  CF_REQUIRE(pre_pad >= 0 && pre_pad < h && pre_pad < w, "cf_esrgan_tile_gather_u8: reflect pre-pad %d needs faces larger than it (%dx%d)",
+             pre_pad, w, h);
+  const int h1 = h + pre_pad, w1 = w + pre_pad;
+  const int h2 = h1 + (mod - h1 % mod) % mod, w2 = w1 + (mod - w1 % mod) % mod;
+  CF_REQUIRE(h2 - h1 < h1 && w2 - w1 < w1, "cf_esrgan_tile_gather_u8: reflect pad to a multiple of %d exceeds %dx%d", mod, w1, h1);
+  CF_REQUIRE(py0 >= 0 && px0 >= 0 && py0 + th <= h2 && px0 + tw <= w2, "cf_esrgan_tile_gather_u8: window %d,%d %dx%d outside %dx%d", px0, py0,
+             tw, th, w2, h2);
+  hipLaunchKernelGGL(esr_gather_kernel, dim3(nblk((long)th * tw), n), dim3(256), 0, (hipStream_t)stream, faces, h, w, h1, w1, py0, px0, th,
+                     tw, out);
+  CF_CHECK_LAUNCH("cf_esrgan_tile_gather_u8");
+  return CF_OK;
+}
+
+extern "C" int cf_esrgan_tile_scatter_u8(const float* up, int n, int uh, int uw, int oy, int ox, int ch, int cw, uint8_t* out, int oh, int ow,
+                                         int dy, int dx, cf_stream_t stream) {
+  CF_REQUIRE(up && out && n > 0 && n <= 65535 && ch > 0 && cw > 0, "cf_esrgan_tile_scatter_u8: bad args");
+  CF_REQUIRE(oy >= 0 && ox >= 0 && oy + ch <= uh && ox + cw <= uw, "cf_esrgan_tile_scatter_u8: core %d,%d %dx%d outside the %dx%d tile", ox, oy,
+             cw, ch, uw, uh);
+  CF_REQUIRE(dy >= 0 && dx >= 0 && dy + ch <= oh && dx + cw <= ow, "cf_esrgan_tile_scatter_u8: destination %d,%d %dx%d outside %dx%d", dx, dy,
+             cw, ch, ow, oh);
+  hipLaunchKernelGGL(esr_scatter_kernel, dim3(nblk((long)ch * cw), n), dim3(256), 0, (hipStream_t)stream, up, uh, uw, oy, ox, ch, cw, out, oh,
+                     ow, dy, dx);
+  CF_CHECK_LAUNCH("cf_esrgan_tile_scatter_u8");
   return CF_OK;
 }

@@ -6,10 +6,17 @@ frame, the crops, the masks and the upsampled canvas living in HBM and every Ope
 face's bounding box (the reference filters the whole upsampled frame once per face).  Face DETECTION (RetinaFace, landmarks,
 `cv2.estimateAffinePartial2D`) stays on the host as the north star says: the 2x3 alignment matrices are this class's input.
 
+With a face upsampler (:388-392) every restored face is upsampled first -- all faces of the frame in ONE batched
+`RealESRGANer.enhance_faces` call, or handed over already upsampled (`add_restored_faces(faces, upsampled=True)`) -- and pasted at
+face_size * upscale with the rescaled inverse affine; with `draw_box` (:439-445, :502-509) the green border bands are blended in the
+launch that also casts the frame to uint8 (cf_box_overlay_u8).
+
 Differences from the reference, all stated in DESIGN.md: one device->host read-back per FRAME (the face areas that size the
-feathering kernel, :433-441) instead of arrays crossing PCIe at every step; the parse-mask branch blends in float32 where numpy
-promotes to float64 (the final image is truncated to uint8, so at most rare 1-LSB differences); `draw_box` and the alpha channel of
-RGBA backgrounds are not built.
+feathering kernel, :433-441, and the box borders) instead of arrays crossing PCIe at every step; the parse-mask branch blends in
+float32 where numpy promotes to float64 (the final image is truncated to uint8, so at most rare 1-LSB differences);
+`inverse_affine_matrices` are not rescaled in place by a face-upsampled paste (the reference's are, which only shows when it pastes
+twice); a face entirely outside the frame draws no box (the reference divides by its zero area).  The alpha channel of RGBA
+backgrounds is not built.
 """
 import math
 
@@ -54,7 +61,7 @@ class DeviceFaceHelper:
         self.device = torch.device(device)
         self.use_parse = bool(use_parse)
         self.face_parse = face_parse              # a codeformer_amd.facelib.parsing ParseNet on `device` (needed when use_parse)
-        self._ones = torch.ones(self.face_size[1], self.face_size[0], dtype=torch.float32, device=self.device)
+        self._ones = {}                           # face size -> ones((fh, fw)) (the square mask, :425)
         self._taps = {}
         self._partials = None
         self.clean_all()
@@ -65,6 +72,7 @@ class DeviceFaceHelper:
         self.inverse_affine_matrices = []
         self.cropped_faces = None
         self.restored_faces = None
+        self.faces_upsampled = False
 
     def read_image(self, img):
         """img: uint8 (H,W,3) BGR numpy array or CUDA tensor (the decoded frame)."""
@@ -93,9 +101,24 @@ class DeviceFaceHelper:
         self.inverse_affine_matrices = [invert_affine(a) * self.upscale_factor for a in self.affine_matrices]   # :354-356
         return self.inverse_affine_matrices
 
-    def add_restored_faces(self, restored):
-        """restored: uint8 (n,512,512,3) BGR CUDA tensor (cf_tensor_to_img_u8 output)."""
+    def add_restored_faces(self, restored, upsampled=False):
+        """restored: uint8 (n,512,512,3) BGR CUDA tensor (cf_tensor_to_img_u8 output); upsampled=True: the faces already went through
+        the face upsampler (uint8 (n,512*upscale,512*upscale,3)) and are pasted as the reference's face_upsampler branch does."""
         self.restored_faces = restored
+        self.faces_upsampled = bool(upsampled)
+
+    def upsample_faces(self, faces, face_upsampler):
+        """face_upsampler.enhance(face, outscale=upscale)[0] for every face (:389): one batched call on the device when the upsampler
+        has `enhance_faces` (RealESRGANer), else per face on the host with the reference's semantics."""
+        u = self.upscale_factor
+        if hasattr(face_upsampler, 'enhance_faces'):
+            return face_upsampler.enhance_faces(faces, outscale=u)
+        up = [np.ascontiguousarray(face_upsampler.enhance(f, outscale=u)[0]) for f in faces.cpu().numpy()]
+        fw, fh = self.face_size
+        if any(f.dtype != np.uint8 or f.shape != (fh * u, fw * u, 3) for f in up):
+            raise ValueError(f'face_upsampler must return uint8 {(fh * u, fw * u, 3)} faces')
+        return torch.from_numpy(np.stack(up)).to(self.device) if up else \
+            torch.empty(0, fh * u, fw * u, 3, dtype=torch.uint8, device=self.device)
 
     # ---- parse mask (:455-481) -------------------------------------------------------------------------------------------------------
     def parse_soft_masks(self, restored):
@@ -118,10 +141,16 @@ class DeviceFaceHelper:
         return self._taps[key]
 
     # ---- paste_faces_to_input_image (:372-499) -----------------------------------------------------------------------------------------
-    def _region(self, inv_up, h_up, w_up):
+    def _ones_dev(self, fw, fh):
+        if (fw, fh) not in self._ones:
+            self._ones[(fw, fh)] = torch.ones(fh, fw, dtype=torch.float32, device=self.device)
+        return self._ones[(fw, fh)]
+
+    @staticmethod
+    def _region(inv_up, h_up, w_up, face_size):
         """Bounding box of the warped face square, grown by everything the masks can spread (erosions only shrink; the Gaussian
         spreads by its radius) and clipped to the canvas: outside it the soft mask is exactly 0."""
-        fw, fh = self.face_size
+        fw, fh = face_size
         corners = np.array([[0, 0, 1], [fw, 0, 1], [0, fh, 1], [fw, fh, 1]], dtype=np.float64).T
         q = inv_up @ corners
         area = abs(inv_up[0, 0] * inv_up[1, 1] - inv_up[0, 1] * inv_up[1, 0]) * fw * fh
@@ -132,9 +161,11 @@ class DeviceFaceHelper:
         return (x0, y0, x1 - x0, y1 - y0) if (x1 > x0 and y1 > y0) else None
 
     @torch.no_grad()
-    def paste_faces_to_input_image(self, upsample_img=None, return_tensor=False):
+    def paste_faces_to_input_image(self, upsample_img=None, return_tensor=False, face_upsampler=None, draw_box=False):
         """Returns the pasted uint8 (h_up, w_up, 3) BGR frame (numpy, or the CUDA tensor with return_tensor=True).
-        upsample_img: optional uint8 background already at (h_up, w_up) (e.g. the Real-ESRGAN output)."""
+        upsample_img: optional uint8 background already at (h_up, w_up) (e.g. the Real-ESRGAN output).
+        face_upsampler: upsample the restored faces first (:388-392; not needed when they were added with upsampled=True).
+        draw_box: green border band around every face (:439-445, :502-509)."""
         h, w, _ = self.input_img.shape
         u = self.upscale_factor
         h_up, w_up = int(h * u), int(w * u)
@@ -150,26 +181,50 @@ class DeviceFaceHelper:
         if not self.inverse_affine_matrices:
             self.get_inverse_affine()
         assert n == len(self.inverse_affine_matrices), 'length of restored_faces and affine_matrices are different.'
-        parse = self.parse_soft_masks(faces) if (self.use_parse and n) else None
+        upsampled = self.faces_upsampled or face_upsampler is not None
+        fw, fh = self.face_size
+        if upsampled:
+            fw, fh = fw * u, fh * u                                                    # :392
+            if n and not self.faces_upsampled:
+                faces = self.upsample_faces(faces, face_upsampler)                     # :389, all faces of the frame in one call
+            if n and tuple(faces.shape[1:]) != (fh, fw, 3):
+                raise ValueError(f'upsampled faces must be {(fh, fw, 3)}, got {tuple(faces.shape[1:])}')
+        parse = None
+        if self.use_parse and n:
+            # ParseNet sees the face at 512^2 (:459, cv2.resize INTER_LINEAR; at 2:1 that is (a+b+c+d+2)>>2).  The faces are stacked
+            # as one tall image: at an integer ratio no output row reads a neighbouring face with a non-zero weight.
+            small = faces
+            if upsampled and u != 1:
+                sw_, sh_ = self.face_size
+                small = ops.f32_to_u8_trunc(ops.resize_linear_u8(faces.reshape(n * fh, fw, 3), n * sh_, sw_)).reshape(n, sh_, sw_, 3)
+            parse = self.parse_soft_masks(small)
+            if parse.shape[1:] != (fh, fw):
+                parse = ops.resize_linear_f32(parse, fh, fw)                          # :482
         # phase 1 (all faces): warped square mask, first erosion, area partials -> ONE read-back per frame
         if self._partials is None or self._partials.shape[0] < max(n, 1):
             self._partials = torch.empty(max(n, 1), 64, dtype=torch.float64, device=self.device)
+        ones = self._ones_dev(fw, fh)
         work = []
         for k in range(n):
-            inv = self.inverse_affine_matrices[k].copy()
-            inv[:, 2] += 0.5 * u if u > 1 else 0                                       # :393-398
-            region = self._region(inv, h_up, w_up)
+            inv = self.inverse_affine_matrices[k].copy()                               # (the reference rescales its list in place)
+            if upsampled:
+                inv /= u                                                               # :390-391
+                inv[:, 2] *= u
+            else:
+                inv[:, 2] += 0.5 * u if u > 1 else 0                                   # :393-398
+            region = self._region(inv, h_up, w_up, (fw, fh))
             if region is None:
                 work.append(None)
                 self._partials[k].zero_()
                 continue
             dst2src = invert_affine(inv)                                               # what cv2.warpAffine derives from its M
-            inv_mask = ops.warp_affine_f32(self._ones, dst2src, region)                # :428
+            inv_mask = ops.warp_affine_f32(ones, dst2src, region)                      # :428
             ero = ops.erode(inv_mask, int(2 * u))                                      # :430-431
             ops.sum_partials(ero, self._partials[k])                                   # :433
             work.append((region, dst2src, ero))
         areas = self._partials[:n].sum(dim=1).cpu().numpy() if n else []
         # phase 2: feathered mask + blend, face by face (the order matters where faces overlap)
+        boxes = []
         for k in range(n):
             if work[k] is None:
                 continue
@@ -179,5 +234,19 @@ class DeviceFaceHelper:
             soft = ops.gaussian_blur(center, self._taps_dev(w_edge * 2 + 1), (region[0], region[1]), (h_up, w_up))   # :445
             pm = ops.warp_affine_f32(parse[k], dst2src, region) if parse is not None else None   # :478-479
             ops.paste_blend(canvas, faces[k], dst2src, ero, soft, region, parse=pm)    # :400, :432, :481-492
-        out = ops.f32_to_u8_trunc(canvas)                                              # :497
+            if draw_box:
+                border = box_border(areas[k])                                          # :440
+                if border > 0:                                                         # border 0: the band is empty
+                    x0, y0, rw, rh = region
+                    boxes.append(list(dst2src.reshape(-1)) + [border, x0, y0, x0 + rw, y0 + rh])
+        if draw_box:                                                                   # :497 + :502-509 in one launch
+            recs = torch.tensor(boxes, dtype=torch.float64).to(self.device) if boxes else None
+            out = ops.box_overlay_u8(canvas, recs, (fh, fw))
+        else:
+            out = ops.f32_to_u8_trunc(canvas)                                          # :497
         return out if return_tensor else out.cpu().numpy()
+
+
+def box_border(total_face_area):
+    """Width of the drawn box band, int(1400 / np.sqrt(total_face_area)) in float32 as numpy evaluates it (:440)."""
+    return int(np.float32(1400) / np.sqrt(np.float32(total_face_area)))

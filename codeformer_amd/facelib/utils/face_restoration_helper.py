@@ -9,8 +9,11 @@ Method names, arguments and the lists a caller reads (`all_landmarks_5`, `det_fa
 `cropped_faces`, `restored_faces`) follow the reference; `cropped_faces` / `restored_faces` hold uint8 HWC BGR arrays on the host
 when asked for (`cropped_faces` property) and stay device tensors otherwise.
 
-Not built (raise NotImplementedError): `det_model='dlib'`, `pad_blur=True` (cv2.boxFilter padding of blurry inputs), `draw_box`,
-`face_upsampler` inside the paste, 16-bit / RGBA inputs.
+`paste_faces_to_input_image(draw_box=..., face_upsampler=...)` runs on the device as well: a RealESRGANer upsamples all faces of the
+frame in one batched call, any other object with `.enhance` is called per face on the host.
+
+Not built (raise NotImplementedError): `det_model='dlib'`, `pad_blur=True` (cv2.boxFilter padding of blurry inputs), 16-bit / RGBA
+inputs.
 """
 import os
 
@@ -220,8 +223,6 @@ class FaceRestoreHelper(object):
 
     # ---- paste-back (:372-499) ------------------------------------------------------------------------------------------------------
     def paste_faces_to_input_image(self, save_path=None, upsample_img=None, draw_box=False, face_upsampler=None):
-        if draw_box or face_upsampler is not None:
-            raise NotImplementedError('draw_box / face_upsampler inside the paste-back are not built')
         dev = self._device_helper()
         faces = self.restored_faces
         if not torch.is_tensor(faces):
@@ -235,7 +236,7 @@ class FaceRestoreHelper(object):
         if upsample_img is not None:
             h, w = self.input_img.shape[:2]
             upsample_img = resize_bilinear(np.ascontiguousarray(upsample_img), (w * self.upscale_factor, h * self.upscale_factor))
-        out = dev.paste_faces_to_input_image(upsample_img=upsample_img)
+        out = dev.paste_faces_to_input_image(upsample_img=upsample_img, face_upsampler=face_upsampler, draw_box=draw_box)
         if save_path is not None:
             imwrite(out, f'{os.path.splitext(save_path)[0]}.{self.save_ext}')
         return out

@@ -106,6 +106,10 @@ SIGNATURES = {
     'cf_f32_to_u8_trunc': (_I, [_P, _L, _P, _P]),
     'cf_label_lut_f32': (_I, [_P, _L, ctypes.POINTER(ctypes.c_float), _I, _P, _P]),
     'cf_scale_clear_border_f32': (_I, [_P, _I, _I, _I, _I, _F, _P]),
+    'cf_box_overlay_u8': (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P]),
+    'cf_resize_linear_f32': (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
+    'cf_esrgan_tile_gather_u8': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    'cf_esrgan_tile_scatter_u8': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -1033,6 +1033,53 @@ def f32_to_u8_trunc(x):
     return out
 
 
+def box_overlay_u8(canvas, faces_dev, face_hw):
+    """The final uint8 frame of a draw_box paste: truncation of `canvas` (float32 (H,W,3)) and, face by face, the green blend through the
+    warped border band.  faces_dev: float64 CUDA (n, 11) = dst->src matrix, border, x0, y0, x1, y1 (None / n == 0: truncation only)."""
+    lib = L.load()
+    out = torch.empty(canvas.shape, dtype=torch.uint8, device=canvas.device)
+    n = 0 if faces_dev is None else faces_dev.shape[0]
+    if n and tuple(faces_dev.shape) != (n, 11):
+        raise ValueError('box_overlay_u8: faces_dev must be (n, 11)')
+    L.check(lib.cf_box_overlay_u8(L.ptr(canvas), canvas.shape[0], canvas.shape[1], L.ptr(faces_dev, dtype=torch.float64) if n else None, n,
+                                  int(face_hw[0]), int(face_hw[1]), L.ptr(out, dtype=torch.uint8), L.stream_ptr()), 'cf_box_overlay_u8')
+    return out
+
+
+def resize_linear_f32(x, dh, dw):
+    """cv2.resize(float32 plane, (dw, dh), INTER_LINEAR) of every plane of x (n, sh, sw) -> (n, dh, dw)."""
+    lib = L.load()
+    if x.dim() != 3:
+        raise ValueError('resize_linear_f32 expects (n, H, W) planes')
+    out = torch.empty(x.shape[0], dh, dw, dtype=torch.float32, device=x.device)
+    if x.shape[0]:
+        L.check(lib.cf_resize_linear_f32(L.ptr(x), x.shape[0], x.shape[1], x.shape[2], L.ptr(out), dh, dw, L.stream_ptr()),
+                'cf_resize_linear_f32')
+    return out
+
+
+def esrgan_tile_gather(faces, pre_pad, mod, window):
+    """uint8 BGR faces (n, h, w, 3) -> float32 RGB NCHW (n, 3, th, tw) in [0, 1]: window (py0, px0, th, tw) of the reflect-padded view."""
+    lib = L.load()
+    n, h, w, _ = faces.shape
+    py0, px0, th, tw = window
+    out = torch.empty(n, 3, th, tw, dtype=torch.float32, device=faces.device)
+    L.check(lib.cf_esrgan_tile_gather_u8(L.ptr(faces, dtype=torch.uint8), n, h, w, int(pre_pad), int(mod), py0, px0, th, tw, L.ptr(out),
+                                         L.stream_ptr()), 'cf_esrgan_tile_gather_u8')
+    return out
+
+
+def esrgan_tile_scatter(up, core, out, dst_yx):
+    """The core (oy, ox, ch, cw) of the model output up (n, 3, uh, uw) into the uint8 BGR faces out (n, oh, ow, 3) at dst_yx (dy, dx)."""
+    lib = L.load()
+    n, _, uh, uw = up.shape
+    oy, ox, ch, cw = core
+    if out.shape[0] != n:
+        raise ValueError('esrgan_tile_scatter: batch mismatch')
+    L.check(lib.cf_esrgan_tile_scatter_u8(L.ptr(up), n, uh, uw, oy, ox, ch, cw, L.ptr(out, dtype=torch.uint8), out.shape[1], out.shape[2],
+                                          int(dst_yx[0]), int(dst_yx[1]), L.stream_ptr()), 'cf_esrgan_tile_scatter_u8')
+
+
 def label_lut(labels, lut):
     lib = L.load()
     out = torch.empty(labels.shape, dtype=torch.float32, device=labels.device)

@@ -27,6 +27,8 @@ def _spans(length, tile, pad):
 
 
 class RealESRGANer:
+    FACE_CHUNK = 16   # faces per model call in enhance_faces
+
 
     def __init__(self, scale, model_path, model=None, tile=0, tile_pad=10, pre_pad=10, half=False, device=None, gpu_id=None):
         self.scale, self.tile_size, self.tile_pad, self.pre_pad = scale, tile, tile_pad, pre_pad
@@ -108,3 +110,43 @@ class RealESRGANer:
         if outscale is not None and float(outscale) != float(self.scale):
             raise NotImplementedError('outscale != network scale needs a LANCZOS4 resize (cv2); resize on the caller side')
         return out, img_mode
+
+    # -- batched faces on the device (the paste-back's face upsampler) ---------------------------------------------------
+    @torch.no_grad()
+    def enhance_faces(self, faces, outscale=None):
+        """uint8 (n,H,W,3) BGR faces on the device -> uint8 (n,H*scale,W*scale,3) BGR on the device, bit for bit
+        `np.stack([enhance(f)[0] for f in faces])`: the same padded view, the same tile grid (`_spans`), one model call per
+        tile position for up to FACE_CHUNK faces (RRDBNet is batch-invariant), and enhance's clamp / * 255 / round.  The
+        uint8 <-> tile conversions are the cf_esrgan_tile_gather_u8 / _scatter_u8 kernels; nothing leaves HBM."""
+        from .. import ops
+        if outscale is not None and float(outscale) != float(self.scale):
+            raise NotImplementedError('outscale != network scale needs a LANCZOS4 resize (cv2); resize on the caller side')
+        if faces.dtype != torch.uint8 or faces.dim() != 4 or faces.shape[3] != 3 or not faces.is_cuda:
+            raise ValueError('enhance_faces expects uint8 (n, H, W, 3) BGR faces on the device')
+        faces = faces.contiguous()
+        n, h, w, _ = faces.shape
+        s, mod = self.scale, self.mod_scale or 1
+        out = torch.empty(n, h * s, w * s, 3, dtype=torch.uint8, device=faces.device)
+        if n == 0:
+            return out
+        hp, wp = h + self.pre_pad, w + self.pre_pad
+        hp, wp = hp + (-hp) % mod, wp + (-wp) % mod
+        if self.tile_size > 0:
+            rows, cols = list(_spans(hp, self.tile_size, self.tile_pad)), list(_spans(wp, self.tile_size, self.tile_pad))
+        else:
+            rows, cols = [(0, hp, 0, hp)], [(0, wp, 0, wp)]
+        for b in range(0, n, self.FACE_CHUNK):
+            chunk = faces[b:b + self.FACE_CHUNK]
+            dst = out[b:b + self.FACE_CHUNK]
+            for y0, y1, py0, py1 in rows:
+                ch = min(y1, h) * s - y0 * s             # post_process crops the pads away: cores past the face are not kept
+                if ch <= 0:
+                    continue
+                for x0, x1, px0, px1 in cols:
+                    cw = min(x1, w) * s - x0 * s
+                    if cw <= 0:
+                        continue
+                    tile = ops.esrgan_tile_gather(chunk, self.pre_pad, mod, (py0, px0, py1 - py0, px1 - px0))
+                    up = self.model(tile).float().contiguous()
+                    ops.esrgan_tile_scatter(up, ((y0 - py0) * s, (x0 - px0) * s, ch, cw), dst, (y0 * s, x0 * s))
+        return out

@@ -417,6 +417,24 @@ int cf_f32_to_u8_trunc(const float* src, int64_t n, uint8_t* dst, cf_stream_t st
 int cf_label_lut_f32(const int64_t* labels, int64_t n, const float* lut_host, int nlut, float* out, cf_stream_t stream);
 /* in place: x * scale inside the frame of `border` pixels, 0 on it (face_restoration_helper.py:476-481), x: [batch][h][w] */
 int cf_scale_clear_border_f32(float* x, int batch, int h, int w, int border, float scale, cf_stream_t stream);
+/* draw_box fused with the final astype(uint8) (face_restoration_helper.py:439-445, :497-509): out (u8 [ch][cw][3]) = imwrite's rint /
+ * saturate of the truncated canvas (f32 [ch][cw][3]) blended, face by face in order, with green through the warp of each face's border
+ * band (ones on the outer `border` pixels of the fh x fw face, zeros inside).  faces_dev: DEVICE array of nfaces x 11 doubles = the
+ * dst->src matrix (6), border, and the band's bounding box x0, y0, x1, y1 in canvas pixels (outside it the warped band is 0).
+ * nfaces == 0 is a plain truncation. */
+int cf_box_overlay_u8(const float* canvas, int ch, int cw, const double* faces_dev, int nfaces, int fh, int fw, uint8_t* out,
+                      cf_stream_t stream);
+/* cv2.resize(float32 plane, (dw, dh), INTER_LINEAR) of `batch` planes [batch][sh][sw] -> [batch][dh][dw] (face_restoration_helper.py:482:
+ * the 512^2 soft parse masks brought to the upsampled face size) */
+int cf_resize_linear_f32(const float* src, int batch, int sh, int sw, float* dst, int dh, int dw, cf_stream_t stream);
+/* Face upsampler tile I/O (RealESRGANer.enhance_faces).  Gather: u8 BGR faces [n][h][w][3] -> f32 RGB NCHW [n][3][th][tw] = window
+ * (py0, px0) of the padded view pre_process builds (reflect pre-pad on the right / bottom, reflect pad to a multiple of mod), / 255 */
+int cf_esrgan_tile_gather_u8(const uint8_t* faces, int n, int h, int w, int pre_pad, int mod, int py0, int px0, int th, int tw, float* out,
+                             cf_stream_t stream);
+/* Scatter: the ch x cw core at (oy, ox) of the model's f32 RGB NCHW output [n][3][uh][uw] -> (dy, dx) of u8 BGR faces [n][oh][ow][3],
+ * rint(clamp(v, 0, 1) * 255.0f) */
+int cf_esrgan_tile_scatter_u8(const float* up, int n, int uh, int uw, int oy, int ox, int ch, int cw, uint8_t* out, int oh, int ow, int dy,
+                              int dx, cf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@ Same flags, same result tree (results/<input>_<w>/restored_faces/<basename>.png)
   * under torchrun the face list is sharded over ranks (one process per GPU) -- each rank writes its own results.
 Whole images (and directories of extracted video frames) take the reference's full flow: RetinaFace detection + alignment fit on the
 host (facelib), crop warp / batched restoration / paste-back on the device; --affine_npz replaces the detector by a file of matrices.
+--face_upsample (faces through Real-ESRGAN x2 in batches before the paste, -s 2) and --draw_box run on the device too.
 Video container files (.mp4 ...) need ffmpeg, which this image lacks: extract the frames to a directory first.
 """
 import argparse
@@ -85,7 +86,7 @@ def set_realesrgan(args, device, random_init_seed=None):
         if random_init_seed is None:
             print(f'NOTE: {e}; the Real-ESRGAN upsampler is not used on the --has_aligned path and is skipped')
             return None
-        print('WARNING: RealESRGAN_x2plus.pth not found -- using random weights for the (unused) upsampler')
+        print('WARNING: RealESRGAN_x2plus.pth not found -- using random weights for the upsampler')
         return RealESRGANer(scale=2, model_path=None, model=model, tile=args.bg_tile, tile_pad=40, pre_pad=0,
                             half=device.type == 'cuda', device=device)
 
@@ -129,8 +130,6 @@ def restore_whole_images(args, input_img_list, result_root, w):
     device = torch.device(args.device) if args.device else get_device()
     if device.type != 'cuda':
         raise NotImplementedError('the whole-image path runs on a ROCm device (alignment warp and paste-back are HIP kernels)')
-    if args.draw_box or args.face_upsample:
-        raise NotImplementedError('--draw_box / --face_upsample inside the paste-back are not built')
     from codeformer_amd.video import VideoRestorer, frame_shard
     from facelib.utils.face_restoration_helper import FaceRestoreHelper
     table = np.load(args.affine_npz) if args.affine_npz else None
@@ -141,20 +140,24 @@ def restore_whole_images(args, input_img_list, result_root, w):
     mine = [input_img_list[i] for i in frame_shard(len(input_img_list), rank, world)]       # frames are the unit of sharding
     net = build_net(device, args)
     parser = build_parser(args, device)
-    bg = None
+    bg = ups = None
     if args.bg_upsampler == 'realesrgan':
         ups = set_realesrgan(args, device, args.random_init_seed)
         if ups is not None:
             def bg(frame):
                 img = ups.enhance(frame, outscale=args.upscale)[0]
                 return resize_bilinear(img, (frame.shape[1] * args.upscale, frame.shape[0] * args.upscale))
+    face_upsampler = None
+    if args.face_upsample:                                       # the background upsampler doubles as the face upsampler (:124-132)
+        face_upsampler = ups if ups is not None else (set_realesrgan(args, device, args.random_init_seed)
+                                                      if args.bg_upsampler != 'realesrgan' else None)
     # (the helper lives on the compute device: a detector placed there reads the uploaded frame through the INTER_AREA / INTER_LINEAR
     # kernels instead of a host-side resize; crops and paste-back are the VideoRestorer's)
     helper = FaceRestoreHelper(args.upscale, face_size=512, crop_ratio=(1, 1), det_model=args.detection_model, save_ext='png',
                                use_parse=False, device=device, face_detector=build_detector(args, device) if table is None else False)
     vr = VideoRestorer(net, device, upscale=args.upscale, batch_size=args.batch_size or 16, bg_upsampler=bg,
-                       use_parse=parser is not None, face_parse=parser)
-    totals = {'frames': 0, 'faces': 0, 'forward_calls': 0}
+                       use_parse=parser is not None, face_parse=parser, face_upsampler=face_upsampler, draw_box=args.draw_box)
+    totals = {'frames': 0, 'faces': 0, 'forward_calls': 0, 'upsampler_calls': 0}
     failed = []
 
     def flush(frames, affs, names, grays):
@@ -208,6 +211,8 @@ def restore_whole_images(args, input_img_list, result_root, w):
     if frames:
         flush(frames, affs, names, grays)
     print(f"{totals['faces']} faces of {totals['frames']} images in {totals['forward_calls']} forward calls")
+    if face_upsampler is not None:
+        print(f"faces upsampled in {totals['upsampler_calls']} batched Real-ESRGAN calls")
     if failed:
         print(f'{len(failed)} image(s) failed: {failed[:8]}{" ..." if len(failed) > 8 else ""}')
     print(f'\nAll results are saved in {result_root}')
@@ -243,8 +248,20 @@ def build_net(device, args):
     return net.to(device).eval()
 
 
+FACE_UPSAMPLER_SCALE = 2   # RealESRGAN_x2plus, the reference's face upsampler (inference_codeformer.py:19-45)
+
+
+def check_args(args):
+    """Argument checks that need no device."""
+    if args.face_upsample and not args.has_aligned and args.upscale != FACE_UPSAMPLER_SCALE:
+        raise NotImplementedError(f'--face_upsample with -s {args.upscale}: the x{FACE_UPSAMPLER_SCALE} face upsampler pastes at -s '
+                                  f'{FACE_UPSAMPLER_SCALE} only; other scales need the LANCZOS4 resize of its output (cv2.INTER_LANCZOS4), '
+                                  'which is not built')
+
+
 def main(argv=None):
     args = parse_args(argv)
+    check_args(args)
     device = torch.device(args.device) if args.device else get_device()
     w = args.fidelity_weight
     input_img_list, result_root = collect_inputs(args)

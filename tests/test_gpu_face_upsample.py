@@ -1,0 +1,414 @@
+"""-m gpu: --face_upsample and --draw_box in the device paste-back (face_restoration_helper.py:372-512 of the reference).
+
+RealESRGANer.enhance_faces (batched, tiled, cf_esrgan_tile_gather_u8 / _scatter_u8) against the per-face `enhance`; the paste-back
+with upsampled faces, the ParseNet branch under upsampling (cf_resize_linear_f32) and the box overlay (cf_box_overlay_u8) against a
+numpy restatement of the reference's lines composed from oracle/paste_oracle.py primitives (below); VideoRestorer, FaceRestoreHelper
+and inference_codeformer.py end to end.  Everything is compared bit for bit.  The face upsampler is the 2-block `x2_small` RRDBNet of
+tests/golden/rrdbnet_digests.json unless a case says otherwise."""
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, 'tests', 'golden')
+pytestmark = pytest.mark.gpu
+
+
+# ---- numpy restatement of the new reference steps (CPU; also exercised by tests/test_face_upsample_host.py) ------------------------
+def reduce_2to1_u8(img):
+    """cv2.resize(uint8 (2h, 2w, 3), (w, h), INTER_LINEAR) at exactly 2:1: (a + b + c + d + 2) >> 2 (:459)."""
+    s = img.astype(np.int64)
+    return ((s[0::2, 0::2] + s[0::2, 1::2] + s[1::2, 0::2] + s[1::2, 1::2] + 2) >> 2).astype(np.uint8)
+
+
+def resize_linear_f32(img, dsize):
+    """cv2.resize(float32 plane, (dw, dh), INTER_LINEAR) (:482): f = float32((d + 0.5) * scale - 0.5), s = floor(f), f -= s, edges
+    clamped to (0, 0) / (n - 1, 0); rows horizontally first (a plain copy where s + 1 is past the edge), then vertically; float32
+    products and sums rounded separately."""
+    h, w = img.shape
+    dw, dh = dsize
+
+    def axis(n_src, n_dst):
+        f = ((np.arange(n_dst, dtype=np.float64) + 0.5) * (n_src / n_dst) - 0.5).astype(np.float32)
+        s = np.floor(f).astype(np.int64)
+        f = f - s.astype(np.float32)
+        lo, hi = s < 0, s >= n_src - 1
+        f[lo | hi] = 0
+        s[lo] = 0
+        s[hi] = n_src - 1
+        return s, f
+
+    sx, fx = axis(w, dw)
+    sy, fy = axis(h, dh)
+    one = np.float32(1)
+    two = sx + 1 < w
+    hr = np.where(two[None, :], img[:, sx] * (one - fx)[None, :] + img[:, np.minimum(sx + 1, w - 1)] * fx[None, :], img[:, sx])
+    return hr[sy] * (one - fy)[:, None] + hr[np.minimum(sy + 1, h - 1)] * fy[:, None]
+
+
+def band_mask(fs, border):
+    """:441-443: ones on the outer `border` band of the fs x fs face, zeros inside (border 0: all zeros)."""
+    m = np.ones((fs, fs), dtype=np.float32)
+    m[border:fs - border, border:fs - border] = 0
+    return m
+
+
+def paste_oracle(frame, faces, affines, upscale, upsampled=False, parse_masks=None, draw_box=False):
+    """paste_faces_to_input_image (:372-512), upsample_img=None.  faces: uint8 512^2 faces, or (upsampled=True) the face upsampler's
+    uint8 (512*upscale)^2 output, pasted with the rescaled inverse affine and no half-pixel offset (:388-392).  parse_masks: per-face
+    float32 512^2 soft masks (:466-477), resized to the face size (:482) and warped (:483).  draw_box: :439-445 and :502-509, with
+    cv2.imwrite's float32 -> uint8 conversion (rint, saturate) at the end."""
+    P = _paste_oracle_module()
+    h, w = frame.shape[:2]
+    h_up, w_up = int(h * upscale), int(w * upscale)
+    img = P.resize_linear_u8(frame, (w_up, h_up)).astype(np.float32) if upscale != 1 else frame.astype(np.float32)
+    borders = []
+    for k, (face, aff) in enumerate(zip(faces, affines)):
+        inv = P.invert_affine(aff) * upscale                                     # get_inverse_affine (:352-356)
+        if upsampled:
+            inv /= upscale                                                       # :390-392
+            inv[:, 2] *= upscale
+            fs = 512 * upscale
+        else:
+            inv[:, 2] += 0.5 * upscale if upscale > 1 else 0                     # :393-398
+            fs = 512
+        inv_restored = P.warp_affine_u8(face, inv, (w_up, h_up))
+        inv_mask = P.warp_affine_f32(np.ones((fs, fs), np.float32), inv, (w_up, h_up))
+        ero = P.erode(inv_mask, int(2 * upscale))
+        pasted = ero[:, :, None] * inv_restored.astype(np.float32)
+        total_face_area = np.sum(ero)
+        if draw_box:
+            border = int(1400 / np.sqrt(total_face_area))
+            borders.append(P.warp_affine_f32(band_mask(fs, border), inv, (w_up, h_up)))
+        w_edge = int(total_face_area ** 0.5) // 20
+        soft = P.gaussian_blur(P.erode(ero, w_edge * 2), w_edge * 2 + 1)
+        if parse_masks is not None:
+            pm = parse_masks[k]
+            if pm.shape != (fs, fs):
+                pm = resize_linear_f32(pm, (fs, fs))
+            pm = P.warp_affine_f32(pm, inv, (w_up, h_up))
+            soft = np.where(pm < soft, pm, soft)
+        m = soft[:, :, None]
+        img = m * pasted + (1 - m) * img
+    out = img.astype(np.uint8)
+    if not draw_box:
+        return out
+    colour = np.zeros(out.shape, dtype=np.float32)
+    colour[:, :, 1] = 255
+    for b in borders:
+        out = b[:, :, None] * colour + (1 - b[:, :, None]) * out
+    return np.clip(np.rint(out), 0, 255).astype(np.uint8)
+
+
+def _paste_oracle_module():
+    from oracle import paste_oracle as P
+    return P
+
+
+# ---- fixtures -----------------------------------------------------------------------------------------------------------------------
+def _img(h, w, seed=0):
+    import scipy.ndimage as ndi
+    rng = np.random.default_rng(seed)
+    base = ndi.gaussian_filter(rng.normal(size=(h, w, 3)), (3, 3, 0)) * 400 + 128
+    return np.clip(base + rng.normal(size=(h, w, 3)) * 8, 0, 255).astype(np.uint8)
+
+
+def _affine(cx, cy, size, angle=0.0):
+    """frame -> 512-face similarity for a face of `size` frame pixels centred at (cx, cy), rotated by `angle`."""
+    P = _paste_oracle_module()
+    c, s = np.cos(angle), np.sin(angle)
+    pts = np.array([[-0.25, -0.1], [0.25, -0.1], [0.0, 0.25]]) * size
+    src = pts @ np.array([[c, -s], [s, c]]).T + [cx, cy]
+    dst = np.array([[-0.25, -0.1], [0.25, -0.1], [0.0, 0.25]]) * 512 + 256
+    return P.similarity_from_points(src, dst)
+
+
+# an overlapping pair and a face cut by the border, as in tests/test_gpu_paste.py
+AFFS = [_affine(150, 120, 130, 0.2), _affine(260, 150, 150, -0.15), _affine(470, 20, 90, 0.0)]
+
+
+def _net(name='x2_small', scale=None):
+    from basicsr.archs.rrdbnet_arch import RRDBNet
+    import torch
+    with open(os.path.join(GOLD, 'rrdbnet_digests.json')) as f:
+        case = json.load(f)[name]
+    torch.manual_seed(case['seed'])
+    return RRDBNet(3, 3, scale=scale or case['scale'], num_feat=64, num_block=case['num_block'], num_grow_ch=32).eval()
+
+
+def _upsampler(tile=400, tile_pad=40, pre_pad=0, half=True, scale=2):
+    from codeformer_amd.utils.realesrgan_utils import RealESRGANer
+    return RealESRGANer(scale=scale, model_path=None, model=_net(scale=scale), tile=tile, tile_pad=tile_pad, pre_pad=pre_pad, half=half,
+                        device='cuda')
+
+
+@pytest.fixture(scope='module')
+def env():
+    import torch
+    assert torch.cuda.is_available(), 'gpu tests need an MI355X'
+    from codeformer_amd import lib, ops
+    lib.load()
+    return torch, ops
+
+
+def _faces(n, seed, size=512):
+    return np.stack([_img(size, size, seed + i) for i in range(n)])
+
+
+# ---- enhance_faces -------------------------------------------------------------------------------------------------------------------
+CONFIGS = [(0, 10, 0), (0, 10, 10)] + [(400, tp, pp) for tp in (10, 40) for pp in (0, 10)]
+
+
+@pytest.mark.parametrize('half', [False, True])
+@pytest.mark.parametrize('tile,tile_pad,pre_pad', CONFIGS)
+def test_enhance_faces_equals_per_face_enhance(env, tile, tile_pad, pre_pad, half):
+    torch, ops = env
+    up = _upsampler(tile, tile_pad, pre_pad, half)
+    faces = _faces(5, 100 + tile + pre_pad)
+    got = up.enhance_faces(torch.from_numpy(faces).cuda())
+    assert got.dtype == torch.uint8 and tuple(got.shape) == (5, 1024, 1024, 3)
+    want = np.stack([up.enhance(f, outscale=2)[0] for f in faces])
+    assert np.array_equal(got.cpu().numpy(), want)
+
+
+@pytest.mark.parametrize('half', [False, True])
+def test_enhance_faces_odd_sizes_and_reflect_pads(env, half):
+    """Small tiles over a face whose pre-padded size is odd: the reflect pre-pad, the reflect pad to even sizes and the crop of both."""
+    torch, ops = env
+    up = _upsampler(tile=40, tile_pad=10, pre_pad=10, half=half)
+    faces = np.stack([_img(101, 75, 300 + i) for i in range(3)])
+    got = up.enhance_faces(torch.from_numpy(faces).cuda()).cpu().numpy()
+    assert got.shape == (3, 202, 150, 3)
+    assert np.array_equal(got, np.stack([up.enhance(f)[0] for f in faces]))
+
+
+def test_enhance_faces_chunks_of_16(env):
+    torch, ops = env
+    up = _upsampler(tile=400, tile_pad=40, pre_pad=0, half=True)
+    sizes = []
+    forward = up.model.forward
+
+    def counting(x):
+        sizes.append(x.shape[0])
+        return forward(x)
+
+    up.model.forward = counting
+    faces = _faces(17, 400)
+    got = up.enhance_faces(torch.from_numpy(faces).cuda()).cpu().numpy()
+    assert sizes == [16] * 4 + [1] * 4                       # 2 x 2 tile positions per chunk
+    del up.model.forward
+    assert np.array_equal(got, np.stack([up.enhance(f)[0] for f in faces]))
+    with pytest.raises(NotImplementedError):
+        up.enhance_faces(torch.from_numpy(faces[:1]).cuda(), outscale=4)
+
+
+# ---- paste-back with face upsampling, parse branch, boxes ---------------------------------------------------------------------------
+def _helper(upscale, **kw):
+    from codeformer_amd.facelib.paste import DeviceFaceHelper
+    return DeviceFaceHelper(upscale_factor=upscale, device='cuda', **kw)
+
+
+def _paste(torch, frame, restored, upscale, **kw):
+    h = _helper(upscale, **{k: kw.pop(k) for k in ('use_parse', 'face_parse') if k in kw})
+    h.read_image(frame)
+    h.align_warp_face(AFFS)
+    h.add_restored_faces(torch.from_numpy(np.stack(restored)).cuda())
+    return h, h.paste_faces_to_input_image(**kw)
+
+
+def test_paste_with_face_upsampler_matches_the_oracle(env):
+    torch, ops = env
+    frame = _img(270, 480, 11)
+    restored = [_img(512, 512, 21 + i) for i in range(3)]
+    up = _upsampler()
+    h, got = _paste(torch, frame, restored, 2, face_upsampler=up)
+    ups = up.enhance_faces(torch.from_numpy(np.stack(restored)).cuda()).cpu().numpy()
+    want = paste_oracle(frame, list(ups), AFFS, 2, upsampled=True)
+    assert got.shape == want.shape == (540, 960, 3)
+    d = np.abs(got.astype(int) - want.astype(int))
+    assert d.max() == 0, (int(d.max()), float((d > 0).mean()))
+    inv_before = [m.copy() for m in h.inverse_affine_matrices]
+    again = h.paste_faces_to_input_image(face_upsampler=up)              # the matrices are not rescaled in place
+    assert np.array_equal(again, got) and all(np.array_equal(a, b) for a, b in zip(inv_before, h.inverse_affine_matrices))
+    _, plain = _paste(torch, frame, restored, 2)
+    assert (plain != got).any()
+    # faces handed over already upsampled take the same branch
+    h2 = _helper(2)
+    h2.read_image(frame)
+    h2.align_warp_face(AFFS)
+    h2.add_restored_faces(torch.from_numpy(ups).cuda(), upsampled=True)
+    assert np.array_equal(h2.paste_faces_to_input_image(), got)
+
+    class HostOnly:                                                        # an upsampler with `.enhance` only: called per face
+        calls = 0
+
+        def enhance(self, img, outscale=None):
+            HostOnly.calls += 1
+            return up.enhance(img, outscale=outscale)
+
+    h3 = _helper(2)
+    h3.read_image(frame)
+    h3.align_warp_face(AFFS)
+    h3.add_restored_faces(torch.from_numpy(np.stack(restored)).cuda())
+    assert np.array_equal(h3.paste_faces_to_input_image(face_upsampler=HostOnly()), got) and HostOnly.calls == 3
+
+
+def test_parse_branch_under_face_upsampling(env):
+    torch, ops = env
+    import torch.nn.functional as F
+    rng = np.random.default_rng(5)
+    labels = rng.integers(0, 19, (3, 512, 512))
+    labels[:, 100:400, 120:390] = 1
+    seen = []
+
+    class RecordingParse:
+        def parse_labels(self, x):
+            seen.append(x.clone())
+            return torch.from_numpy(labels[:x.shape[0]]).cuda()
+
+    frame = _img(270, 480, 31)
+    restored = [_img(512, 512, 41 + i) for i in range(3)]
+    up = _upsampler()
+    h, got = _paste(torch, frame, restored, 2, face_upsampler=up, use_parse=True, face_parse=RecordingParse())
+    ups = up.enhance_faces(torch.from_numpy(np.stack(restored)).cuda()).cpu().numpy()
+    small = np.stack([reduce_2to1_u8(f) for f in ups])
+    P = _paste_oracle_module()
+    assert all(np.array_equal(small[i], P.resize_linear_u8(ups[i], (512, 512))) for i in range(3))
+    assert len(seen) == 1 and torch.equal(seen[0], ops.img_u8_to_tensor(torch.from_numpy(small).cuda()))
+    soft = h.parse_soft_masks(torch.from_numpy(small).cuda())
+    big = ops.resize_linear_f32(soft, 1024, 1024).cpu().numpy()
+    soft = soft.cpu().numpy()
+    for i in range(3):
+        assert np.array_equal(big[i], resize_linear_f32(soft[i], (1024, 1024))), i
+    ref = F.interpolate(torch.from_numpy(soft).double()[:, None], size=(1024, 1024), mode='bilinear', align_corners=False)[:, 0].numpy()
+    assert np.abs(big - ref).max() <= 1e-6
+    odd = np.random.default_rng(6).random((2, 37, 53)).astype(np.float32)        # other ratios, both directions
+    for dh, dw in ((80, 101), (20, 30), (37, 53)):
+        got_o = ops.resize_linear_f32(torch.from_numpy(odd).cuda(), dh, dw).cpu().numpy()
+        assert all(np.array_equal(got_o[i], resize_linear_f32(odd[i], (dw, dh))) for i in range(2)), (dh, dw)
+    want = paste_oracle(frame, list(ups), AFFS, 2, upsampled=True, parse_masks=list(soft))
+    d = np.abs(got.astype(int) - want.astype(int))
+    assert d.max() == 0, (int(d.max()), float((d > 0).mean()))
+
+
+@pytest.mark.parametrize('upscale,upsample,scale', [(1, False, None), (2, False, None), (2, True, 2), (1, True, 1)])
+def test_draw_box_matches_the_oracle(env, upscale, upsample, scale):
+    torch, ops = env
+    frame = _img(270, 480, 50 + upscale)
+    restored = [_img(512, 512, 60 + i) for i in range(3)]
+    up = _upsampler(scale=scale) if upsample else None
+    _, got = _paste(torch, frame, restored, upscale, face_upsampler=up, draw_box=True)
+    _, nobox = _paste(torch, frame, restored, upscale, face_upsampler=up)
+    faces = up.enhance_faces(torch.from_numpy(np.stack(restored)).cuda()).cpu().numpy() if upsample else restored
+    want = paste_oracle(frame, list(faces), AFFS, upscale, upsampled=upsample, draw_box=True)
+    d = np.abs(got.astype(int) - want.astype(int))
+    assert d.max() == 0, (int(d.max()), float((d > 0).mean()))
+    assert np.array_equal(nobox, paste_oracle(frame, list(faces), AFFS, upscale, upsampled=upsample))
+    if not upsample:                                                     # without draw_box: today's paste, bit for bit
+        assert np.array_equal(nobox, _paste_oracle_module().paste_faces(frame, restored, AFFS, upscale=upscale))
+    changed = (got != nobox).any(-1)
+    assert changed.any()
+    g, n = got.astype(int), nobox.astype(int)                           # blending towards (0, 255, 0) only
+    assert (g[..., 1] >= n[..., 1]).all() and (g[..., 0] <= n[..., 0]).all() and (g[..., 2] <= n[..., 2]).all()
+    if not upsample:
+        assert (got == np.array([0, 255, 0], np.uint8)).all(-1).any()   # the band's interior is pure green
+
+
+def test_draw_box_border_zero_draws_nothing(env):
+    """int(1400 / sqrt(area)) == 0 for a face wider than 1400 px: the band mask is all zeros."""
+    torch, ops = env
+    from codeformer_amd.facelib.paste import box_border
+    frame = _img(1600, 1600, 70)
+    h = _helper(1)
+    h.read_image(frame)
+    h.align_warp_face([_affine(800, 800, 1500)])
+    h.add_restored_faces(torch.from_numpy(_faces(1, 71)).cuda())
+    boxed = h.paste_faces_to_input_image(draw_box=True)
+    assert np.array_equal(boxed, h.paste_faces_to_input_image())
+    assert box_border(1490.0 ** 2) == 0 and box_border(1390.0 ** 2) == 1
+
+
+# ---- pipeline, helper, entry point ---------------------------------------------------------------------------------------------------
+def test_video_restorer_with_face_upsampler_and_boxes(env):
+    torch, ops = env
+    from codeformer_amd.utils.face_misc import adain_npy, bgr2gray
+    from codeformer_amd.video import VideoRestorer
+    rng = np.random.default_rng(7)
+    frames = [_img(180, 320, 80 + i) for i in range(9)]
+    affs = []
+    for i in range(9):
+        k = [3, 0, 5, 2, 4, 1, 6, 2, 3][i]
+        affs.append(np.stack([_affine(rng.uniform(60, 260), rng.uniform(50, 130), rng.uniform(50, 110), rng.uniform(-0.3, 0.3))
+                              for _ in range(k)]) if k else np.zeros((0, 2, 3)))
+
+    def net(x, w=0.5, adain=True):
+        return (-x,)
+
+    up = _upsampler()
+    gray = [False] * 9
+    gray[4] = True
+    for flags in (None, gray):
+        vr = VideoRestorer(net, 'cuda', upscale=2, batch_size=16, face_upsampler=up, draw_box=True)
+        out = vr.restore(frames, affs, w=0.5, keep_faces=True, gray=flags)
+        regrays = 0 if flags is None else 1
+        assert vr.stats == {'frames': 9, 'faces': 26, 'forward_calls': 2, 'upsampler_calls': math.ceil(26 / 16) + regrays}
+        for i in range(9):
+            h = _helper(2)
+            h.read_image(frames[i])
+            crops = h.align_warp_face(affs[i])
+            restored = ops.tensor_to_img_u8(-ops.img_u8_to_tensor(crops)) if crops.shape[0] else crops
+            if flags is not None and flags[i]:
+                moved = [adain_npy(bgr2gray(f), c) for f, c in zip(restored.cpu().numpy(), crops.cpu().numpy())]
+                restored = torch.from_numpy(np.clip(np.rint(np.stack(moved)), 0, 255).astype(np.uint8)).cuda()
+            h.add_restored_faces(restored)
+            want = h.paste_faces_to_input_image(face_upsampler=up, draw_box=True)
+            assert out[i].shape == (360, 640, 3) and np.array_equal(out[i], want), i
+            assert vr.faces_out[i][1].shape[1:] == (512, 512, 3)                       # keep_faces: the 512^2 faces
+            assert np.array_equal(vr.faces_out[i][1], restored.cpu().numpy())
+
+
+def test_face_restore_helper_forwards_the_flags(env):
+    torch, ops = env
+    from facelib.utils.face_restoration_helper import FaceRestoreHelper
+    frame = _img(520, 640, 90)
+    affs = [_affine(200, 220, 180, 0.1), _affine(420, 260, 160, -0.2)]
+    restored = torch.from_numpy(_faces(2, 91)).cuda()
+    up = _upsampler()
+    fh = FaceRestoreHelper(2, face_size=512, device='cuda', face_detector=False)
+    fh.read_image(frame)
+    fh._device_helper().align_warp_face(affs)
+    fh.affine_matrices = affs
+    fh.add_restored_faces(restored)
+    got = fh.paste_faces_to_input_image(draw_box=True, face_upsampler=up)
+    h = _helper(2)
+    h.read_image(frame)
+    h.align_warp_face(affs)
+    h.add_restored_faces(restored)
+    assert np.array_equal(got, h.paste_faces_to_input_image(draw_box=True, face_upsampler=up))
+
+
+def test_entrypoint_face_upsample_and_draw_box(env, tmp_path):
+    """The upstream README's whole-image command with --face_upsample --draw_box on a directory of frames."""
+    import subprocess
+    import sys
+    from PIL import Image
+    src = tmp_path / 'whole_imgs'
+    os.makedirs(src)
+    table = {}
+    for i in range(2):
+        Image.fromarray(_img(520, 640, 95 + i)[:, :, ::-1]).save(src / f'im{i}.png')
+        table[f'im{i}'] = np.stack([_affine(220 + 60 * i, 210, 180, 0.1 * i)])
+    np.savez(tmp_path / 'aff.npz', **table)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'inference_codeformer.py'), '-i', str(src), '-o', str(tmp_path / 'o'), '-s', '2',
+                        '--affine_npz', str(tmp_path / 'aff.npz'), '--random_init_seed', '0', '--bg_upsampler', 'realesrgan',
+                        '--face_upsample', '--draw_box', '--device', 'cuda'],
+                       capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert sorted(os.listdir(tmp_path / 'o' / 'final_results')) == ['im0.png', 'im1.png']
+    for i in range(2):
+        assert np.asarray(Image.open(tmp_path / 'o' / 'final_results' / f'im{i}.png')).shape == (1040, 1280, 3)
+        assert np.asarray(Image.open(tmp_path / 'o' / 'restored_faces' / f'im{i}_00.png')).shape == (512, 512, 3)
+    assert 'faces upsampled in 1 batched Real-ESRGAN calls' in r.stdout
