@@ -29,10 +29,6 @@ from .hip_module import PACK_EPOCH, HipModule
 from .vqgan_arch import ResBlock, VQAutoEncoder
 
 
-# The q | k and v projections of a Transformer layer as one split-half token GEMM (round 6; CODEFORMER_HIP_QKV_ONE_LAUNCH=0: two launches, A/B --
-# the same bits either way)
-QKV_ONE_LAUNCH = os.environ.get('CODEFORMER_HIP_QKV_ONE_LAUNCH', '1') != '0'
-
 # Graphed forwards share static input / output buffers per captured shape, so capture and replay are serialised (one lock for the
 # process: module attributes must stay picklable / deep-copyable).  The eager path (more than `graph_max_batch` faces) is re-entrant.
 _GRAPH_LOCK = threading.RLock()
@@ -102,7 +98,7 @@ class TransformerSALayer(HipModule):
             t2, t2p = ops.layernorm(X, self.norm1.weight, self.norm1.bias, self.norm1.eps, pos=pos)
         else:
             t2 = t2p = ops.layernorm(X, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-        if c1 == ops.GSPLIT and QKV_ONE_LAUNCH and (2 * E) % 128 == 0:
+        if c1 == ops.GSPLIT and (2 * E) % 128 == 0:
             # split-half token GEMM: the whole in_proj (3 E rows) in ONE launch -- the q | k columns contract LN(x) + pos, the v columns LN(x)
             # (cf_conv_desc.in0_alt; per output element the arithmetic of the two launches below -- with ONE power-of-two pack scale for the whole
             #  in_proj instead of one per part, so q, k, v agree with the two-launch form to the last bits of the 22-bit operands, not bitwise)
@@ -201,7 +197,7 @@ class Fuse_sft_block(HipModule):
         pws = [self._pw_conv(m, bf16, hw=hw) for m in (self.scale[0], self.scale[2], self.shift[0], self.shift[2])]
         rs = [ops.needs_act_scale(p) for p in pws]
         act_e = ops.act_scale(e) if (rs[0] or rs[2]) else None
-        if rs[1] and rs[3] and ops.ACT_FUSED:
+        if rs[1] and rs[3]:
             # both second convolutions want a table: the two first convolutions write their statistics into one buffer and ONE launch turns
             # them into both tables (bitwise act_scale of each) -- 4 launches fewer per forward
             pair = ops.StatsPair()
@@ -259,14 +255,12 @@ class CodeFormer(VQAutoEncoder):
         # Transformer, argmax, the 16x16 / 32x32 latents (AttnBlocks, AdaIN) stay fp32, so logits and code indices are bitwise those of the
         # default mode.  CODEFORMER_HIP_BF16_STORAGE=0 / False: bf16 OPERANDS on fp32 tensors (rounds 2-5).
         self.bf16_storage = os.environ.get('CODEFORMER_HIP_BF16_STORAGE', '1') != '0'
-        # Exact-fp32 convolutions (precision='fp32', and in every mode the layers the split kernel does not take): evaluate 3x3
-        # stride-1 convolutions with Winograd F(2x2,3x3) -- the same function in fp32 with 2.25x fewer multiplies (cf_winograd.hip).
-        # Set False (or CODEFORMER_HIP_WINOGRAD=0) for the direct evaluation everywhere.
-        self.winograd = os.environ.get('CODEFORMER_HIP_WINOGRAD', '1') != '0'
-        # precision 'f16x2' and 'fp32': generator / CFT layers the F(4x4,3x3) kernel covers (ops.f43_ok; which shapes: CODEFORMER_HIP_F43) run
-        # there (split-half / IEEE-fp32 operands) -- 2.25 instead of 4 transform-domain products per output.  Its error against fp64 is ~5x that of F(2x2,3x3): far inside
-        # the pixel tolerance; the encoder's use of it has its own switch and gate (next attribute).  False / CODEFORMER_HIP_F43=0: F(2x2,3x3) everywhere.
-        self.winograd_f43 = ops.F43_LAYERS != '0'
+        # Exact-fp32 convolutions (precision='fp32', and in every mode the layers the split kernel does not take) evaluate 3x3 stride-1
+        # convolutions with Winograd F(2x2,3x3) where the shape allows -- the same function in fp32 with 2.25x fewer multiplies
+        # (cf_winograd.hip); the encoder too, in every precision mode.  Precision 'f16x2' and 'fp32': generator / CFT layers the F(4x4,3x3)
+        # kernel covers (ops.f43_ok) run there (split-half / IEEE-fp32 operands) -- 2.25 instead of 4 transform-domain products per output.
+        # Its error against fp64 is ~5x that of F(2x2,3x3): far inside the pixel tolerance; the encoder's use of it has its own switch and
+        # gate (next attribute).
         # The same kernel for the ENCODER's covered layers (the 64-channel 512^2, 128-channel 256^2 / 128^2 stages and, for fp32 operands, the
         # 256-channel 64^2 stage): on by default since round 5 (CODEFORMER_HIP_F43_ENCODER=0 / False: F(2x2,3x3) there, the round-2..4 encoder).
         # The encoder decides the code indices and F(4x4,3x3) carries ~5x the per-layer error of F(2x2,3x3), so the switch was admitted on
@@ -277,17 +271,9 @@ class CodeFormer(VQAutoEncoder):
         # the step in the default mode and 9 % in 'fp32'.  Gate: tests/test_gpu_real_images.py::test_encoder_logit_margin (tools/logit_margin.py,
         # profiles/r05_logit_margin.txt).
         self.winograd_f43_encoder = os.environ.get('CODEFORMER_HIP_F43_ENCODER', '1') == '1'
-        # Also evaluate the ENCODER's 3x3 stride-1 convolutions with Winograd, in every precision mode (the encoder is always
-        # fp32, so logits / indices stay bitwise identical across 'fp32' / 'bf16' / 'fp16').  Measured against the reference:
-        # logits 4.3e-6 (direct kernel 5.5e-6), lq_feat 1.0e-5 (1.4e-5), indices exact on every seeded face incl. one whose
-        # top-2 gap is 1.7e-5 -- the Winograd form sums fewer products per output and is, if anything, the more accurate one.
-        # Round 2 added the reference's own crops (three PNGs, one masked face) and an 8-face sweep to the gate: indices equal the
-        # reference's on every token whose reference gap is >= 1e-5 (tests/test_gpu_real_images.py).
-        self.winograd_encoder = os.environ.get('CODEFORMER_HIP_WINOGRAD_ENCODER', '1') != '0'
         # Operand format of the ENCODER's 3x3 stride-1 convolutions: 'fp32' (exact fp32 MFMA, Winograd where eligible), 'f16x2' (split
-        # halves on every layer but the first conv -- the 16x16 latents included, on the four-wave Winograd kernel with split-K; only with
-        # winograd = False do the latents stay on the exact direct kernel) or 'auto' = 'fp32' when
-        # precision is 'fp32', 'f16x2' otherwise (a 16-bit generator does not ask for an exact-fp32 encoder at 0.54 of the fp32 MFMA peak).  The code indices hang on the encoder, so this was measured before it became the
+        # halves on every layer but the first conv -- the 16x16 latents included, on the four-wave Winograd kernel with split-K) or
+        # 'auto' = 'fp32' when precision is 'fp32', 'f16x2' otherwise (a 16-bit generator does not ask for an exact-fp32 encoder at 0.54 of the fp32 MFMA peak).  The code indices hang on the encoder, so this was measured before it became the
         # default (tools/encoder_split_check.py, profiles/r02_encoder_split_check.txt): against the reference's logits on its own
         # crops the split encoder is as close as the exact one (max 6.7e-6 / 5.4e-6 / 5.7e-6 vs 7.6e-6 / 5.5e-6 / 6.0e-6; the
         # reference's own 1-vs-8-thread noise is 2.6e-6), the smallest (reference top-2 gap) / (2 x our logit error) over all tokens
@@ -350,11 +336,9 @@ class CodeFormer(VQAutoEncoder):
                     for f in self.connect_list}
         if self.encoder_precision not in ('auto', 'fp32', 'f16x2'):
             raise ValueError(f"encoder_precision must be 'auto', 'fp32' or 'f16x2', got {self.encoder_precision!r}")
-        enc_code = ops.WINOGRAD if (self.winograd and self.winograd_encoder) else 0
-        if self.encoder_precision == 'f16x2' or (self.encoder_precision == 'auto' and self.precision != 'fp32'):
-            enc_code = ops.SPLIT if enc_code == ops.WINOGRAD else ops.SPLIT_DIRECT
-        if self.winograd_f43_encoder and self.winograd_f43:
-            enc_code = {ops.SPLIT: ops.SPLIT_F43, ops.WINOGRAD: ops.WINOGRAD_F43}.get(enc_code, enc_code)
+        enc_code = ops.SPLIT if self.encoder_precision == 'f16x2' or (self.encoder_precision == 'auto' and self.precision != 'fp32') else ops.WINOGRAD
+        if self.winograd_f43_encoder:
+            enc_code = {ops.SPLIT: ops.SPLIT_F43, ops.WINOGRAD: ops.WINOGRAD_F43}[enc_code]
         lq = self.encoder.forward_nhwc(x, enc_taps, bf16=enc_code)        # (B,16,16,256) channels-last
         T = lq.shape[1] * lq.shape[2]
         tokens = lq.view(B * T, lq.shape[3])
@@ -381,15 +365,9 @@ class CodeFormer(VQAutoEncoder):
 
         if self.precision not in ('fp32', 'f16x2', 'bf16', 'fp16'):
             raise ValueError(f"precision must be 'fp32', 'f16x2', 'bf16' or 'fp16', got {self.precision!r}")
-        bf16 = {'fp32': 0, 'f16x2': ops.SPLIT, 'bf16': 1, 'fp16': 2}[self.precision]   # operand code of the generator + CFT 3x3 convs
-        if bf16 == 0 and self.winograd:
-            bf16 = ops.WINOGRAD
-        if bf16 == ops.SPLIT and not self.winograd:
-            bf16 = ops.SPLIT_DIRECT
-        if bf16 == ops.WINOGRAD and self.winograd_f43:
-            bf16 = ops.WINOGRAD_F43   # the same layers on fp32 operands (four v_mfma_f32_16x16x4_f32 per 16 channels instead of three f16 MFMAs)
-        if bf16 == ops.SPLIT and self.winograd_f43:
-            bf16 = ops.SPLIT_F43   # (the encoder gets this code through winograd_f43_encoder only, above)
+        # operand code of the generator + CFT 3x3 convs; 'fp32': F(4x4,3x3) on fp32 operands (four v_mfma_f32_16x16x4_f32 per 16 channels
+        # instead of three f16 MFMAs); 'f16x2': the encoder gets SPLIT_F43 through winograd_f43_encoder only, above
+        bf16 = {'fp32': ops.WINOGRAD_F43, 'f16x2': ops.SPLIT_F43, 'bf16': 1, 'fp16': 2}[self.precision]
         gen_taps = None
         if w > 0:
             def fuse(t):
@@ -438,7 +416,7 @@ class CodeFormer(VQAutoEncoder):
         """Capture-once / replay-many execution of _forward_hip on the current stream.  Outputs are copies, so callers may
         keep them across calls.  A graph is re-captured when any packed weight was rebuilt since its capture."""
         with _GRAPH_LOCK:   # static buffers per shape: two threads replaying one graph would race on them
-            key = (tuple(x.shape), float(w), bool(code_only), bool(adain), self.precision, bool(self.bf16_storage), self.encoder_precision, self.gemm_precision, bool(self.winograd), bool(self.winograd_encoder), bool(self.winograd_f43), bool(self.winograd_f43_encoder), str(x.device), ops.switches())
+            key = (tuple(x.shape), float(w), bool(code_only), bool(adain), self.precision, bool(self.bf16_storage), self.encoder_precision, self.gemm_precision, bool(self.winograd_f43_encoder), str(x.device), ops.switches())
             ent = self._graphs.get(key)
             sig = self._param_signature()
             if ent is None or ent['epoch'] != PACK_EPOCH[0] or ent['sig'] != sig:

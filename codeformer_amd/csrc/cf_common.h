@@ -92,7 +92,7 @@ __device__ __forceinline__ void cf_split_pair(float x0, float x1, float& hi, flo
 // 128x128 -5 %: no write-allocate traffic through L2).  A host decision per launch (tensor bytes), never a change of the stored bits;
 // one-face calls stay below the threshold, where the next kernel still finds its input in the Infinity Cache.
 constexpr long CF_NT_STORE_BYTES = 100L << 20;
-bool cf_nt_store(long out_bytes);   // cf_misc.hip: out_bytes >= the threshold (CF_NT_STORE_MB in the environment overrides it; 0 = never)
+inline bool cf_nt_store(long out_bytes) { return out_bytes >= CF_NT_STORE_BYTES; }
 __device__ __forceinline__ void cf_store16(float* p, f32x4 v, bool nt) {
   if (nt) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
   else *reinterpret_cast<f32x4*>(p) = v;

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(const GsArgs g) {
   }
 }
 
-// ---- the same GEMM with the token tile staged through LDS (round 4): 128 tokens x BN (64 / 128) columns per workgroup ------------
+// ---- the same GEMM with the token tile staged through LDS (round 4): 128 tokens x BN = 64 NI columns (NI = 1) per workgroup -----
 // The kernel above gathers its A fragments per lane (32 rows x 64 bytes per instruction) and keeps ONE MFMA tile per wave: at 4096 tokens
 // it runs at 50-60 TFLOP/s, bound by the L2 latency of its 32-64 dependent k steps.  Here
 //   * the 128 x 32 token tile of a stage is read coalesced (a row's 128 bytes by 8 threads), split ONCE into hi / lo halves and written
@@ -656,15 +656,10 @@ int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream) {
   g.counters = d->counters;
   g.nsplit = nsplit;
   // token tiles of 128 rows staged through LDS where the shape allows and K is not split (bitwise the same result: see the kernel);
-  // the narrow form keeps a 128 x 64 grid at 256+ workgroups for N = 512
-  // CF_GEMM_TILE (A/B only): 0 the untiled kernel, 1 (default) 128 x 64 tiles, 2 also 128 x 128 tiles where they still give 256 workgroups
-  // (measured inside the step: 26.9 vs 29.6 us on 4096 x 512 x 1024 -- the narrow tile's 512 workgroups keep more loads in flight)
-  static const int tile_mode = getenv("CF_GEMM_TILE") ? atoi(getenv("CF_GEMM_TILE")) : 1;
-  if (nsplit == 1 && g.M % 128 == 0 && g.K % 64 == 0 && tile_mode != 0) {
-    if (tile_mode == 2 && g.N % 128 == 0 && (long)(g.M / 128) * (g.N / 128) >= 256)
-      hipLaunchKernelGGL(gemm_split_tile_kernel<2>, dim3((unsigned)((g.M / 128) * (g.N / 128))), dim3(256), 0, stream, g);
-    else
-      hipLaunchKernelGGL(gemm_split_tile_kernel<1>, dim3((unsigned)((g.M / 128) * (g.N / 64))), dim3(256), 0, stream, g);
+  // the narrow 128 x 64 form: its 256+ workgroups for N = 512 keep more loads in flight than 128 x 128 tiles (measured inside the
+  // step: 26.9 vs 29.6 us on 4096 x 512 x 1024)
+  if (nsplit == 1 && g.M % 128 == 0 && g.K % 64 == 0) {
+    hipLaunchKernelGGL(gemm_split_tile_kernel<1>, dim3((unsigned)((g.M / 128) * (g.N / 64))), dim3(256), 0, stream, g);
     CF_CHECK_LAUNCH("cf_conv2d(1x1, f16x2, token tiles)");
     return CF_OK;
   }
@@ -675,12 +670,11 @@ int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream) {
 
 // Called by cf_conv2d (cf_igemm.hip) for fp32 1x1 / Linear descriptors with split_k == 1 (one workgroup per output tile: large token
 // matrices).  Returns CF_OK after launching, or 1 when the shape is not this kernel's (the caller then runs its split-K instantiation:
-// the same bits).  CF_GEMM_F32_TILE=0 in the environment keeps every launch there (A/B).
+// the same bits).
 int cf_gemm_f32_tile_try(const cf_conv_desc* d, hipStream_t stream) {
-  static const bool on = !(getenv("CF_GEMM_F32_TILE") && atoi(getenv("CF_GEMM_F32_TILE")) == 0);
   const long m = (long)d->batch * d->hout * d->wout;
   const int k = d->c0;
-  if (!on || d->taps != 1 || d->bf16_mfma != CF_OPERAND_F32 || d->split_k != 1 || d->c1 != 0 || d->stride != 1 || d->in_nchw || d->out_nchw ||
+  if (d->taps != 1 || d->bf16_mfma != CF_OPERAND_F32 || d->split_k != 1 || d->c1 != 0 || d->stride != 1 || d->in_nchw || d->out_nchw ||
       d->prologue != CF_PRO_NONE || d->stats_out || d->stats_cpg || m % 128 || k % 128 || d->cout % 64 || d->cout_pad != d->cout ||
       (d->ld_in0 != 0 && d->ld_in0 != d->c0) || (d->ld_out != 0 && d->ld_out != d->cout) || d->pad_mode != CF_PAD_ZERO ||
       !(d->epilogue == CF_EPI_NONE || d->epilogue == CF_EPI_GELU || d->epilogue == CF_EPI_RESIDUAL))

@@ -19,26 +19,6 @@
 
 #include "cf_common.h"
 
-// tuning knobs explored with tools/ab_variants.sh (defaults = the shipped configuration)
-#ifndef CF_LOADA_TAP
-#define CF_LOADA_TAP 0      // tap at which the next halo patch is prefetched into registers (0..8); 0 = a whole slab of cover (+1 % vs 8)
-#endif
-#ifndef CF_WAVES_PER_SIMD
-#define CF_WAVES_PER_SIMD 3  // __launch_bounds__ occupancy target
-#endif
-#ifndef CF_EPI_WAVESYNC
-#define CF_EPI_WAVESYNC 1    // 1: the epilogue transpose is wave-private (no workgroup barriers, operand loads issued first)
-#endif
-#ifndef CF_XCD_SWIZZLE
-#define CF_XCD_SWIZZLE 1     // 1: remap workgroup ids so each XCD (private L2) owns a contiguous run of tiles (shared halos / weights)
-#endif
-#ifndef CF_INTERLEAVE
-#define CF_INTERLEAVE 1      // 1: MFMA-first weave of fetches / LDS traffic into the MFMA stream (sched_group_barrier)
-#endif
-#ifndef CF_FAST_SWISH
-#define CF_FAST_SWISH 1      // 1: fp32 prologue swish on v_exp_f32 / v_rcp_f32 (~3 ulp of x*sigmoid(x)) instead of expf + IEEE divide: +1.2..2.5 % on the GN-swish convs
-#endif
-
 namespace {
 
 struct ConvArgs {
@@ -133,14 +113,14 @@ __device__ __forceinline__ float swishf(float y) { return y * (1.0f / (1.0f + ex
 // 64x64 pixels up exist (direct bf16 3x3 with 64 output channels, folded upsample, fp32 1x1 on images); every other one is untouched.
 template <int TAPS, int STRIDE, int WM, int WN, int MI, int NI, bool IN_NCHW, bool BF16 = false, bool EXT = false, bool F16 = false,
           bool SK = false, bool BIO = false>
-__global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const ArgsOf<EXT, SK> a) {
+__global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) {
   using C = Cfg<TAPS, STRIDE, WM, WN, MI, NI>;
   static_assert(!BIO || (!IN_NCHW && !EXT && !SK && !F16 && STRIDE == 1), "bf16 tensors: dense NHWC stride-1 instantiations only");
   static_assert(!SK || (TAPS == 1 && !EXT && !BF16 && !F16), "split-K: 1x1 / Linear fp32 instantiations");
   constexpr bool LP = BF16 || F16;  // 16-bit MFMA operands
   static_assert(!LP || (TAPS > 1 && STRIDE == 1 && !IN_NCHW), "16-bit operand path: 3x3 stride 1 NHWC only");
   static_assert(!(BF16 && F16), "one operand format");
-  static_assert(!EXT || (TAPS > 1 && !IN_NCHW && !BF16 && CF_EPI_WAVESYNC), "EXT: 3x3 / folded 2x2, NHWC, fp32 or f16");
+  static_assert(!EXT || (TAPS > 1 && !IN_NCHW && !BF16), "EXT: 3x3 / folded 2x2, NHWC, fp32 or f16");
   constexpr int KC = LP ? 32 : CF_BK;  // channels per K slab
   constexpr int AV = LP ? 2 : 1;       // float4 fetched per gather item (8 / 4 channels)
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -158,12 +138,10 @@ __global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const Arg
   // Workgroup b runs on XCD b % 8 (observed dispatch order; speed only, never correctness).  Give every XCD a contiguous
   // run of tile ids so neighbouring tiles -- which share halo rows/columns and the weight slabs -- hit the same L2.
   int bid = blockIdx.x;
-#if CF_XCD_SWIZZLE
   {
     const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;  // bijective for any grid size
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
   }
-#endif
   [[maybe_unused]] int split = 0, sk_tile = 0;
   if constexpr (SK) {
     split = bid % a.nsplit;  // the splits of one tile are neighbours in the tile order
@@ -320,7 +298,7 @@ __global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const Arg
             if (PRO == CF_PRO_AFFINE) y = y * sc[u][e] + sh[u][e];
             if (PRO == CF_PRO_AFFINE_SWISH) {
               y = y * sc[u][e] + sh[u][e];
-              y = (LP || CF_FAST_SWISH) ? y * __frcp_rn(1.0f + __expf(-y)) : swishf(y);  // bf16 operands: fast exp/rcp are far below the rounding
+              y = y * __frcp_rn(1.0f + __expf(-y));  // v_exp_f32 / v_rcp_f32: ~3 ulp of x*sigmoid(x), +1.2..2.5 % on the GN-swish convs
             }
             if (PRO == CF_PRO_LEAKY) y = y > 0.f ? y : 0.2f * y;
             v[u][e] = valid ? y : 0.f;
@@ -479,11 +457,11 @@ __global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const Arg
         const int slot1 = slot == 2 ? 0 : slot + 1;
         const int slot2 = slot1 == 2 ? 0 : slot1 + 1;
         constexpr int NM = LP ? MI * NI : MI * NI * 4;                      // MFMAs per half step
-        constexpr int NA = (CF_LOADA_TAP >= 0) ? C::APT * AV : 0;           // halo-patch fetches riding in one step
-        constexpr bool WEAVE = CF_INTERLEAVE && !LP && NM >= MI + NI + C::BPT + NA;
+        constexpr int NA = C::APT * AV;                                     // halo-patch fetches riding in one step
+        constexpr bool WEAVE = !LP && NM >= MI + NI + C::BPT + NA;
         // ---- first half: fetch slab s+2 (and, once per slab, the next halo patch), read frags(s, k 8..15), MFMA on frags(s, k 0..7)
         load_B(step + 2 < nsteps ? step + 2 : nsteps - 1, rb);  // clamped: the tail prefetches are harmless re-reads
-        if (tap == CF_LOADA_TAP) load_A(chunk + 1 < a.nchunks ? chunk + 1 : chunk, ra);
+        if (tap == 0) load_A(chunk + 1 < a.nchunks ? chunk + 1 : chunk, ra);
         read_frags(ay, by, tap_off(tap), slot, 1);
         if (!WEAVE) __builtin_amdgcn_sched_barrier(0);  // pin the fetches above the MFMA block (hipcc would sink them)
         mma16(ax, bx);
@@ -496,12 +474,12 @@ __global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const Arg
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
           }
 #pragma unroll
-          for (int i = 0; i < C::BPT + (tap == CF_LOADA_TAP ? NA : 0); ++i) {
+          for (int i = 0; i < C::BPT + (tap == 0 ? NA : 0); ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
           }
 #pragma unroll
-          for (int i = 0; i < NM - (MI + NI) - C::BPT - (tap == CF_LOADA_TAP ? NA : 0); ++i)
+          for (int i = 0; i < NM - (MI + NI) - C::BPT - (tap == 0 ? NA : 0); ++i)
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -593,7 +571,7 @@ __global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const Arg
       const int slot2 = slot1 == 2 ? 0 : slot1 + 1;
       const int nxt = kb + (chunk + 2 < n ? chunk + 2 : n - 1);  // clamped: the tail prefetches are harmless re-reads
       constexpr int NM = MI * NI * 4;
-      constexpr bool WEAVE = CF_INTERLEAVE && NM >= MI + NI + C::BPT + C::APT * AV;
+      constexpr bool WEAVE = NM >= MI + NI + C::BPT + C::APT * AV;
       load_B(nxt, rb);
       load_A(nxt, ra);
       read_frags1(ay, by, slot, 1);
@@ -727,7 +705,6 @@ __global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const Arg
         }
       }
 #define CF_LIVE(p) (nvalid && (!EXT || ((inside >> (p)) & 1u)))
-#if CF_EPI_WAVESYNC
       // Residual / SFT operands are requested BEFORE the transpose so their HBM latency overlaps it.  The transpose
       // buffer is private to the wave (LDS operations of one wave complete in issue order), so no workgroup barrier is
       // needed: the main loop's closing barrier already retired every read of this LDS region.
@@ -745,20 +722,13 @@ __global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const Arg
         }
       }
       __builtin_amdgcn_wave_barrier();
-#else
-      __syncthreads();  // main loop (or the previous half) is done with this LDS region
-#endif
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
         for (int r = 0; r < 16; ++r) stage[cf_acc_row(r, lane) * LDW + ni * 32 + l31] = acc[mi][ni][r];
-#if CF_EPI_WAVESYNC
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#else
-      __syncthreads();
-#endif
 #pragma unroll
       for (int p = 0; p < PASSES; ++p) {
         const int trow = p * RPP + rl;
@@ -768,20 +738,11 @@ __global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const Arg
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] += bias4[e];
           if (EPI == CF_EPI_RESIDUAL) {
-#if CF_EPI_WAVESYNC
             const f32x4 rr = r0[p];
-#else
-            const f32x4 rr = *reinterpret_cast<const f32x4*>(a.res + o);
-#endif
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] += rr[e];
           } else if (EPI == CF_EPI_SFT) {
-#if CF_EPI_WAVESYNC
             const f32x4 dec = r0[p], sc = r1[p];
-#else
-            const f32x4 dec = *reinterpret_cast<const f32x4*>(a.res + o);
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(a.sft_scale + o);
-#endif
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = dec[e] + a.sft_w * (dec[e] * sc[e] + v[e]);
           } else if (EPI == CF_EPI_GELU) {
@@ -792,14 +753,12 @@ __global__ __launch_bounds__(256, CF_WAVES_PER_SIMD) void igemm_kernel(const Arg
             for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.2f * v[e];
           } else if (EPI == CF_EPI_AXPY || EPI == CF_EPI_AXPY2) {
             // separately rounded multiply and add, the two ATen ops of `x5 * 0.2 + x` (rrdbnet_arch.py:39,62) -- no FMA contraction
-#if CF_EPI_WAVESYNC
             const f32x4 x = r0[p], xx = r1[p];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               v[e] = __fadd_rn(__fmul_rn(v[e], a.sft_w), x[e]);
               if (EPI == CF_EPI_AXPY2) v[e] = __fadd_rn(__fmul_rn(v[e], a.sft_w), xx[e]);
             }
-#endif
           }
           if constexpr (BIO) cf_store4_bf16(a.out, o, v);   // (rounded here, once; the statistics below see the fp32 values)
           else *reinterpret_cast<f32x4*>(a.out + o) = v;

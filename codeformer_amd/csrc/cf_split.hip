@@ -813,11 +813,7 @@ int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query)
   // layers): 64-wide tiles double the workgroup count of a small batch.  The rule looks at the per-image shape only -- the two tile
   // widths write the same outputs but group the GroupNorm partial sums differently, so a batch-dependent choice would break the
   // bitwise batch invariance of the network.
-  static const int narrow_max_wgs = [] {
-    const char* e = getenv("CODEFORMER_HIP_SPLIT_NARROW_WGS");
-    return e ? atoi(e) : SP_NARROW_MAX_WGS;
-  }();
-  const bool wide = d->cout_pad % 128 == 0 && (long)a.tiles_per_img * (d->cout_pad / 128) > narrow_max_wgs;
+  const bool wide = d->cout_pad % 128 == 0 && (long)a.tiles_per_img * (d->cout_pad / 128) > SP_NARROW_MAX_WGS;
   if (s2) return wide ? split_launch<4, 2, true>(a, d->batch, stream) : split_launch<4, 1, true>(a, d->batch, stream);
   if (one && d->io_bf16) return wide ? split_launch<1, 2, false, true>(a, d->batch, stream) : split_launch<1, 1, false, true>(a, d->batch, stream);
   if (one) return wide ? split_launch<1, 2>(a, d->batch, stream) : split_launch<1, 1>(a, d->batch, stream);

@@ -88,7 +88,6 @@ def _cout_pad(cout):
 
 WINOGRAD = 3   # value of the operand-code argument that selects the Winograd F(2x2,3x3) fp32 evaluation
 SPLIT = 4      # ... the split-half evaluation: fp32 operands as hi + lo IEEE halves, 3 f16 MFMAs per product (cf_split.hip)
-SPLIT_DIRECT = 5   # ... the same, but layers the split kernel does not take run on the direct fp32 kernel instead of Winograd
 WSPLIT = 6     # ... Winograd F(2x2,3x3) with split-half operands in the 16 transform-domain GEMMs (cf_winograd.hip, H2)
 GSPLIT = 7     # ... a Linear / 1x1 weight for the split-half token GEMM (cf_gemm_split.hip)
 WF16 = 8       # ... Winograd F(2x2,3x3) with SINGLE IEEE-half operands (eight-wave kernel of cf_wsplit.hip; precision 'fp16')
@@ -98,10 +97,7 @@ WF43 = 11      # ... Winograd F(4x4,3x3) with split-half operands (cf_wf43.hip; 
 WINOGRAD_F43 = 12   # ... REQUEST: WINOGRAD (exact fp32), with Winograd F(4x4,3x3) on fp32 operands where its kernel applies (generator / CFT only)
 WF43F = 13     # ... Winograd F(4x4,3x3) with IEEE-fp32 operands (cf_wf43.hip on v_mfma_f32_16x16x4_f32; winograd = 2, operand fp32)
 OPERAND_F16X2 = 3   # enum cf_operand value behind SPLIT / WSPLIT / GSPLIT / WF43
-SPLIT_CODES = (SPLIT, SPLIT_DIRECT, SPLIT_F43)   # requested codes that put un-normalised inputs / stride-2 / 1x1 layers on the split-half kernels
-# SPLIT layers that the Winograd kernel covers take its split-half form (4/9 of the MFMA work); CODEFORMER_HIP_SPLIT_WINOGRAD=0
-# keeps them on the direct split-half kernel.
-SPLIT_WINOGRAD = os.environ.get('CODEFORMER_HIP_SPLIT_WINOGRAD', '1') != '0'
+SPLIT_CODES = (SPLIT, SPLIT_F43)   # requested codes that put un-normalised inputs / stride-2 / 1x1 layers on the split-half kernels
 
 
 def split_ok(cin, cout, hin, win, c_split=None):
@@ -126,26 +122,22 @@ def winograd_ok(cin, cout, hout, wout):
     return cin % 16 == 0 and cout % 64 == 0 and hout % 8 == 0 and wout % 16 == 0
 
 
-# Which layers a SPLIT_F43 / WINOGRAD_F43 request puts on the F(4x4,3x3) kernel: 'auto' (default) = the shapes where it pays
+# Which layers a SPLIT_F43 / WINOGRAD_F43 request puts on the F(4x4,3x3) kernel: the shapes where it pays
 # (profiles/r04_f43_per_shape.txt, r04_f43_fp32_check_time.txt, r04_latency_minpix.txt): every covered layer with 64 output channels (the
 # 8-wave form, two workgroups per CU: x1.0-1.17 at sixteen faces) and the layers with a multiple of 128 output channels (the 16-wave form)
 # from F43_WIDE_MIN_PIXELS up.  Split-half operands: 128x128 -- at 64x64 the form wins x1.11 at sixteen faces (0.15 ms of a 36 ms step) but a
 # 64x64 image has 16 patches, and at one face per call its 9 launches cost 0.5 ms of 7.1 (140 -> 150 faces/s with the limit at 128x128);
 # fp32 operands: 64x64 (x1.75 there: the fp32 MFMA work itself is the bound).  At 32x32 it loses at any batch (x0.6: 4 patches per image).
-# 'c64' = the 64-channel group only; 'all' = every covered shape; '0' = none (A/B).  The rule is a function of the per-image shape only:
-# results do not depend on the batch.
-F43_LAYERS = os.environ.get('CODEFORMER_HIP_F43', 'auto')
-F43_WIDE_MIN_PIXELS = int(os.environ.get('CODEFORMER_HIP_F43_MINPIX', 128 * 128))        # smallest image of the 16-wave form under 'auto', split-half operands
-F43_WIDE_MIN_PIXELS_FP32 = int(os.environ.get('CODEFORMER_HIP_F43_MINPIX_FP32', 64 * 64))  # ... fp32 operands
+# The rule is a function of the per-image shape only: results do not depend on the batch.
+F43_WIDE_MIN_PIXELS = 128 * 128        # smallest image of the 16-wave form, split-half operands
+F43_WIDE_MIN_PIXELS_FP32 = 64 * 64     # ... fp32 operands
 
 
 def f43_ok(cin, cout, hout, wout, fp32=False):
     """Shapes the F(4x4,3x3) kernel covers (3x3 stride-1 dense NHWC): whole 16x16 output patches, 64-wide channel tiles, at most 256
-    input channels (512 in the 16-wave form on 32-channel slabs: the GroupNorm rows of an image sit in LDS) -- narrowed by F43_LAYERS to
-    where it pays (fp32: the operand type)."""
-    if F43_LAYERS == '0' or (F43_LAYERS == 'c64' and cout != 64):
-        return False
-    if F43_LAYERS == 'auto' and cout != 64 and (cout % 128 or hout * wout < (F43_WIDE_MIN_PIXELS_FP32 if fp32 else F43_WIDE_MIN_PIXELS)):
+    input channels (512 in the 16-wave form on 32-channel slabs: the GroupNorm rows of an image sit in LDS) -- narrowed to where it
+    pays (fp32: the operand type)."""
+    if cout != 64 and (cout % 128 or hout * wout < (F43_WIDE_MIN_PIXELS_FP32 if fp32 else F43_WIDE_MIN_PIXELS)):
         return False
     cin_max = 512 if (cout % 128 == 0 and cin % 32 == 0) else 256     # GroupNorm rows in LDS: 512 in the 16-wave form on 32-channel slabs (round 6), else 256
     return cin % 16 == 0 and cin <= cin_max and cout % 64 == 0 and hout % 16 == 0 and wout % 16 == 0
@@ -153,20 +145,19 @@ def f43_ok(cin, cout, hout, wout, fp32=False):
 
 # precision 'fp32': the Upsample blocks (nearest x2 + 3x3) on the fp32 F(4x4,3x3) kernel with an UPSAMPLING gather (round 6) instead of the folded
 # sub-pixel form on the direct fp32 kernel, which executes every one of its 4 products per output (0.82 of the fp32 MFMA peak: nothing left
-# to schedule) -- F(4,3) needs 2.25.  CODEFORMER_HIP_F43_UPSAMPLE=0: the folded form everywhere (A/B).
-F43_UPSAMPLE = os.environ.get('CODEFORMER_HIP_F43_UPSAMPLE', '1') != '0'
+# to schedule) -- F(4,3) needs 2.25.
 
 
 def f43_up_ok(cin, cout, hout, wout):
     """Shapes the upsampling form of the fp32 F(4x4,3x3) kernel covers ((hout, wout) = the OUTPUT size): the 16-wave workgroup on
     32-channel slabs, GroupNorm-table limit of 256 input channels, whole 16x16 output patches, from the size where the 16-wave form pays."""
-    return F43_UPSAMPLE and F43_LAYERS in ('auto', 'all') and cin % 32 == 0 and cin <= 256 and cout % 128 == 0 and hout % 16 == 0 and wout % 16 == 0 and \
+    return cin % 32 == 0 and cin <= 256 and cout % 128 == 0 and hout % 16 == 0 and wout % 16 == 0 and \
         hout * wout >= F43_WIDE_MIN_PIXELS_FP32
 
 
 # Smallest per-image input of the DIRECT split-half kernel and of the eight-wave Winograd kernel.  The 16x16 latents are below it: with
 # SPLIT they run the four-wave Winograd kernel on split halves with split-K (conv_code -> WSPLIT: measured on the reference's crops
-# before it became the default, profiles/r02_encoder_split_check.txt), with SPLIT_DIRECT they stay on the exact fp32 kernel.
+# before it became the default, profiles/r02_encoder_split_check.txt).
 SPLIT_MIN_PIXELS = 32 * 32
 TOKEN_IMAGE_MAX = 1024   # CF_TOKEN_IMAGE_MAX of cf_common.h: f16x2 1x1 layers on larger images run the streaming convolution kernel
 
@@ -174,11 +165,6 @@ TOKEN_IMAGE_MAX = 1024   # CF_TOKEN_IMAGE_MAX of cf_common.h: f16x2 1x1 layers o
 def wsingle_ok(cin, cout, h, w):
     """Shapes the eight-wave Winograd kernel covers (the rule of cf_wsplit_covers): 128-wide channel tiles from 32x32 pixels up."""
     return winograd_ok(cin, cout, h, w) and cout % 128 == 0 and h * w >= SPLIT_MIN_PIXELS
-
-
-# Single 16-bit operand modes ('bf16' / 'fp16'): layers the eight-wave Winograd kernel covers run there (one MFMA per transform-domain
-# product); CODEFORMER_HIP_WINOGRAD_16BIT=0 keeps every layer on the direct 16-bit instantiations of cf_igemm.hip.
-WINOGRAD_16BIT = os.environ.get('CODEFORMER_HIP_WINOGRAD_16BIT', '1') != '0'
 
 
 def c_split_ok(c_split, slab):
@@ -199,17 +185,19 @@ def conv_code(code, cin, cout, h, w, up2x=False, c_split=None, plain=True):
         if plain and not up2x and c_split_ok(c_split, f43_slab) and f43_ok(cin, cout, h, w):
             return WF43
         code = SPLIT
-    if code in (SPLIT, SPLIT_DIRECT):
-        if code == SPLIT and SPLIT_WINOGRAD and plain and not up2x and winograd_ok(cin, cout, h, w):
+    if code == SPLIT:
+        if plain and not up2x and winograd_ok(cin, cout, h, w):
             return WSPLIT
         if plain and split_ok(cin, cout, h, w, c_split) and (up2x or h * w >= SPLIT_MIN_PIXELS):   # (the folded upsample has no Winograd form: the direct split kernel beats the fp32 one from 16x16 up, tools/up16_probe.py)
             return SPLIT
-        code = WINOGRAD if code == SPLIT else 0
+        code = WINOGRAD
     if code == WINOGRAD:
         return WINOGRAD if (plain and not up2x and winograd_ok(cin, cout, h, w)) else 0
     if code and not (plain and cin % 32 == 0 and cout % 4 == 0):
         return 0
-    if code in (1, 2) and WINOGRAD_16BIT and plain and not up2x and wsingle_ok(cin, cout, h, w):
+    if code in (1, 2) and plain and not up2x and wsingle_ok(cin, cout, h, w):
+        # single 16-bit operands ('bf16' / 'fp16'): the eight-wave Winograd kernel where it covers the layer (one MFMA per
+        # transform-domain product), else the direct 16-bit instantiations of cf_igemm.hip
         return WBF16 if code == 1 else WF16
     return code
 
@@ -226,8 +214,8 @@ HALF_LIMIT = 65504.0 / 4.0    # largest |activation| a Winograd-domain IEEE-half
 
 
 def switches():
-    """The module-level A/B switches a captured forward depends on (part of the graph-replay key of the arch modules)."""
-    return (SPLIT_WINOGRAD, F43_LAYERS, F43_UPSAMPLE, F43_WIDE_MIN_PIXELS, F43_WIDE_MIN_PIXELS_FP32, WINOGRAD_16BIT, RANGE_SCALE, ACT_FUSED, SPLITK_MAX, GEMM_IN_WG_MAX_OUTPUTS, FINALIZE_FUSED)
+    """The module-level switches a captured forward depends on (part of the graph-replay key of the arch modules)."""
+    return (RANGE_SCALE, FINALIZE_FUSED)
 
 
 def needs_act_scale(pw):
@@ -238,7 +226,6 @@ def needs_act_scale(pw):
 
 
 _ACT_CELLS = {}
-ACT_FUSED = os.environ.get('CODEFORMER_HIP_ACT_FUSED', '1') != '0'   # 0: two launches per table (A/B only)
 
 
 def _act_cells(device, batch):
@@ -284,20 +271,11 @@ def act_scale(x, x2=None, growth=4.0):
     cells = L.ptr(_act_cells(x.device, B), dtype=torch.int32)
     st = getattr(x, '_cf_stats', None)
     st2 = None if x2 is None else getattr(x2, '_cf_stats', None)
-    if x2 is not None and (st is None or st2 is None or not ACT_FUSED):
+    if x2 is not None and (st is None or st2 is None):
         # a half without statistics partials: two single tables combined on the host side of the stream (rare: every conv that feeds a
         # concatenation writes partials)
         a1, a2 = act_scale(x, growth=growth), act_scale(x2, growth=growth)
         return torch.stack((torch.minimum(a1[:, 0], a2[:, 0]), torch.maximum(a1[:, 1], a2[:, 1])), dim=1)
-    if not ACT_FUSED and x2 is None:   # A/B only: the two-launch entry points of ABI v16
-        scratch = torch.empty(B * 32, dtype=torch.float32, device=x.device)
-        if st is not None:
-            L.check(lib.cf_act_scale_from_stats(L.ptr(st.part, dtype=torch.float64), B, st.part.numel() // (2 * B), float(growth), L.ptr(scratch), L.ptr(act), L.stream_ptr()), 'cf_act_scale_from_stats')
-        else:
-            L.check(lib.cf_act_scale_from_tensor(L.ptr(_f32(x)), B, x.numel() // B, float(growth), L.ptr(scratch), L.ptr(act), L.stream_ptr()), 'cf_act_scale_from_tensor')
-        if ver is not None:
-            x._cf_act = ((float(growth), ver), act)
-        return act
     if st is not None:
         nper = st.part.numel() // (2 * B)
         p2, n2 = (L.ptr(st2.part, dtype=torch.float64), st2.part.numel() // (2 * B)) if st2 is not None else (None, 0)
@@ -350,7 +328,7 @@ def gn_range_ok(gmax, bmax, n):
 def exact_code(code):
     """Operand code of the exact-fp32 evaluation that replaces a 16-bit-operand code (range fallback); bf16 has fp32's exponent."""
     code = int(code)
-    return {SPLIT: WINOGRAD, SPLIT_F43: WINOGRAD, SPLIT_DIRECT: 0, 2: WINOGRAD}.get(code, code)
+    return {SPLIT: WINOGRAD, SPLIT_F43: WINOGRAD, 2: WINOGRAD}.get(code, code)
 
 
 def pack_weight(weight, bias=None, bf16=False, up2x=False, f16=False, stride2=False):
@@ -489,21 +467,21 @@ def _nhwc_ld(t, what):
 # Split-K (cf_conv_desc.split_k) for 1x1 / Linear layers on small token images: WHETHER a layer takes the split-K kernel (64x64
 # tiles, K cut into virtual chunks of 128 added in a fixed order) depends on its per-image shape only, so a face's bits are the same
 # alone and inside any batch; HOW MANY workgroups then share a tile's chunks is chosen from the number of tiles in flight and does
-# not change the result (see cf_common.h).  CODEFORMER_HIP_SPLITK = largest split count (0: layers keep the large-tile kernel).
-SPLITK_MAX = int(os.environ.get('CODEFORMER_HIP_SPLITK', '8'))
+# not change the result (see cf_common.h).  SPLITK_MAX = largest split count.
+SPLITK_MAX = 8
 SPLITK_IN_WORKGROUP = -1    # CF_SPLITK_IN_WORKGROUP of the header (ABI v21): split-half token GEMMs of one to a few faces
 # Token GEMMs (split-half operands) of at most this many OUTPUTS (rows x columns) take the in-workgroup split: one to four faces (256 tokens
 # each) for every layer, eight faces for the 512-column layers.  Measured per launch inside a captured graph (tools/gemm_chunk_probe.py):
 # 256 x 512 x 512: 5.6 us against 15.0 (cross-workgroup split), 1024 x 512 x 1024: 13.9 / 17.2, 2048 x 1024 x 512: 22.3 / 30.2 -- and 4096 x 512 x
 # 1024: 34.1 against 26.7 for the token-tile kernel, which keeps the large launches.  In the network (tools/latency.py, graph replay, one
 # box): one face 6.71 -> 6.35 ms, two 8.34 -> 7.93, four 11.66 -> 11.38.
-GEMM_IN_WG_MAX_OUTPUTS = int(os.environ.get('CODEFORMER_HIP_GEMM_IN_WG_OUTPUTS', str(1 << 20)))
+GEMM_IN_WG_MAX_OUTPUTS = 1 << 20
 _COUNTERS = {}
 
 
 def splitk_for(pw, ho, wo, cin, batch=1):
     """Split count for a 1x1 / Linear or a Winograd 3x3 on `batch` images of ho x wo pixels; 0: the layer is not a split-K layer."""
-    if SPLITK_MAX <= 0 or (pw.bf16 and not pw.wino and pw.taps != 1) or ho * wo > 1024 or cin % 128:
+    if (pw.bf16 and not pw.wino and pw.taps != 1) or ho * wo > 1024 or cin % 128:
         return 0
     if pw.wino == 2:
         return 0   # (F(4x4,3x3) has no split-K form)
@@ -732,7 +710,7 @@ def groupnorm_tables(xs, gamma, beta, eps=GN_EPS, groups=GN_GROUPS, act_growth=N
     if FINALIZE_FUSED and len(xs) <= 2:
         # one launch for the tensor (or both halves of the concatenation), and the range-scale table with it when every half carries
         # its producer's statistics (that is where act_scale would take the bound from as well)
-        want_act = act_growth is not None and RANGE_SCALE and ACT_FUSED and all(own for _, own in stats)
+        want_act = act_growth is not None and RANGE_SCALE and all(own for _, own in stats)
         act = torch.empty(B, 2, dtype=torch.float32, device=dev) if want_act else None
         cells = L.ptr(_act_cells(dev, B), dtype=torch.int32) if want_act else None
         sa, ca = stats[0][0], xs[0].shape[3]

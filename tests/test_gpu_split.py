@@ -95,9 +95,8 @@ def test_split_conv_refusals_and_overflow_is_loud(sc):
     x2[0, 3, 3, 5] = 1e6
     assert not torch.isfinite(ops.conv2d(x2, pw)).all()
     # host policy: which layers take the split kernel
-    assert ops.SPLIT_WINOGRAD     # (default; CODEFORMER_HIP_SPLIT_WINOGRAD=0 keeps eligible layers on the direct split-half kernel)
     assert ops.conv_code(ops.SPLIT, 128, 128, 256, 256) == ops.WSPLIT and ops.conv_code(ops.SPLIT, 512, 512, 16, 16) == ops.WSPLIT
-    assert ops.conv_code(ops.SPLIT_DIRECT, 512, 512, 16, 16) == 0 and ops.conv_code(ops.SPLIT, 48, 64, 64, 64) == ops.WSPLIT
+    assert ops.conv_code(ops.SPLIT, 48, 64, 64, 64) == ops.WSPLIT
     assert ops.conv_code(ops.SPLIT, 512, 512, 16, 16, up2x=True) == ops.SPLIT and ops.conv_code(ops.SPLIT, 128, 128, 256, 256, up2x=True) == ops.SPLIT
 
 

@@ -67,7 +67,7 @@ def test_operand_range_host_rules():
     assert ops.gn_range_ok(1.2, 0.3, 4 * 512 * 512)            # reference-like gains on the largest layer: fine
     assert not ops.gn_range_ok(20.0, 0.0, 4 * 512 * 512)       # 20 * 1024 > 16376
     assert ops.gn_range_ok(20.0, 0.0, 16 * 16 * 16)            # ... but fine on a 16x16 latent (sqrt(n) = 64)
-    assert ops.exact_code(ops.SPLIT) == ops.WINOGRAD and ops.exact_code(ops.SPLIT_DIRECT) == 0 and ops.exact_code(2) == ops.WINOGRAD
+    assert ops.exact_code(ops.SPLIT) == ops.WINOGRAD and ops.exact_code(2) == ops.WINOGRAD
     assert ops.exact_code(1) == 1 and ops.exact_code(0) == 0 and ops.exact_code(ops.WINOGRAD) == ops.WINOGRAD
     sd = {'generator.blocks.5.conv2.weight': torch.ones(4, 4, 3, 3), 'generator.blocks.5.conv2.bias': torch.ones(4),
           'generator.blocks.5.norm1.weight': torch.ones(4), 'fuse_convs_dict.32.scale.2.weight': torch.ones(4, 4, 3, 3),
@@ -112,7 +112,7 @@ def test_kernel_selection_host_rules():
     assert not ops.split_1x1_ok(128, 64, 36, 64) and not ops.split_1x1_ok(128, 48, 64, 64) and not ops.split_1x1_ok(96, 64, 64, 64, c_split=48)
     # operand codes: the folded upsample takes the direct split kernel from 16x16 up, plain 3x3 below 32x32 the Winograd form
     assert ops.conv_code(ops.SPLIT, 512, 512, 16, 16, up2x=True) == ops.SPLIT and ops.conv_code(ops.SPLIT, 512, 512, 16, 16) == ops.WSPLIT
-    assert ops.conv_code(ops.SPLIT_DIRECT, 512, 512, 16, 16) == 0 and ops.conv_code(ops.SPLIT, 128, 128, 24, 16, up2x=True) == 0
+    assert ops.conv_code(ops.SPLIT, 128, 128, 24, 16, up2x=True) == 0
     # a stride-2 / 1x1 weight form is tied to its descriptor
     s2 = ops.PackedWeight(None, None, 64, 64, 9, 64, 64, bf16=ops.OPERAND_F16X2, s2=True)
     c1 = ops.PackedWeight(None, None, 64, 128, 1, 64, 128, bf16=ops.OPERAND_F16X2, conv1=True)
