@@ -24,6 +24,7 @@ from torch import nn
 
 from .. import ops
 from ..ops import EPI_GELU, EPI_RESIDUAL, EPI_SFT, PRO_LEAKY
+from ..utils.diagnostics import top2_gap
 from ..utils.registry import ARCH_REGISTRY
 from .hip_module import PACK_EPOCH, HipModule
 from .vqgan_arch import ResBlock, VQAutoEncoder
@@ -33,6 +34,11 @@ from .vqgan_arch import ResBlock, VQAutoEncoder
 # process: module attributes must stay picklable / deep-copyable).  The eager path (more than `graph_max_batch` faces) is re-entrant.
 _GRAPH_LOCK = threading.RLock()
 _CAPTURE_STREAMS = {}    # device -> the stream every graph of this process is captured on (its scratch words exist before the first capture)
+
+
+def _min_nan(a, b):
+    """min of two floats that keeps a NaN once it has one (Python's min() does not)."""
+    return b if (b < a or b != b) else a
 
 
 def calc_mean_std(feat, eps=1e-5):
@@ -271,6 +277,19 @@ class CodeFormer(VQAutoEncoder):
         # the step in the default mode and 9 % in 'fp32'.  Gate: tests/test_gpu_real_images.py::test_encoder_logit_margin (tools/logit_margin.py,
         # profiles/r05_logit_margin.txt).
         self.winograd_f43_encoder = os.environ.get('CODEFORMER_HIP_F43_ENCODER', '1') == '1'
+        # Logit guard (CODEFORMER_HIP_LOGIT_GUARD): the gate above was measured with random-init weights only, so the network can watch the
+        # quantity it was about.  'off' (default): nothing changes.  'report': the launch that takes the code argmax also writes every
+        # token's top-2 logit gap and its minimum per face (cf_argmax_rows_gap) -> `last_min_gap` (B,), no host synchronisation.
+        # 'rerun': the B minima are read back once per call, and every face with `not (min gap >= logit_guard_gap)` (a NaN flags) runs
+        # again, eagerly and in one batch, with the encoder on F(2x2,3x3); its rows of every returned tensor, of `last_indices` and of
+        # `last_min_gap` are replaced.  The forward is bitwise batch-invariant, so an unflagged face is bitwise the guard-off face and a
+        # flagged one bitwise the face of a winograd_f43_encoder=False network.  Totals: `guard_stats` / reset_guard_stats().
+        # logit_guard_gap (CODEFORMER_HIP_LOGIT_GUARD_GAP) is an ABSOLUTE logit difference and comes from that gate, not from a new
+        # measurement: required margin 5 x 2 x the largest F(4x4,3x3) logit error recorded for it (1.1e-5, profiles/r06_logit_margin.txt)
+        # = 1.1e-4 -- an error measured with random-init weights; a trained checkpoint may want another value.
+        self.logit_guard = os.environ.get('CODEFORMER_HIP_LOGIT_GUARD', 'off')
+        self.logit_guard_gap = float(os.environ.get('CODEFORMER_HIP_LOGIT_GUARD_GAP', '1.1e-4'))
+        self.reset_guard_stats()
         # Operand format of the ENCODER's 3x3 stride-1 convolutions: 'fp32' (exact fp32 MFMA, Winograd where eligible), 'f16x2' (split
         # halves on every layer but the first conv -- the 16x16 latents included, on the four-wave Winograd kernel with split-K) or
         # 'auto' = 'fp32' when precision is 'fp32', 'f16x2' otherwise (a 16-bit generator does not ask for an exact-fp32 encoder at 0.54 of the fp32 MFMA peak).  The code indices hang on the encoder, so this was measured before it became the
@@ -326,7 +345,10 @@ class CodeFormer(VQAutoEncoder):
             self.fuse_convs_dict[f_size] = Fuse_sft_block(ch, ch)
 
     # ------------------------------------------------------------------ GPU (HIP) path
-    def _forward_hip(self, x, w, code_only, adain):
+    def _forward_hip(self, x, w, code_only, adain, f43_encoder=None, guard=False):
+        """f43_encoder: the encoder's F(4x4,3x3) choice of THIS call (None: self.winograd_f43_encoder; the logit guard's second pass
+        hands False down instead of flipping the attribute -- two threads may share a network).  guard: take the argmax on
+        cf_argmax_rows_gap and leave the per-face minimum top-2 gap in `last_min_gap` (with code_only too)."""
         B, _, Himg, Wimg = x.shape
         if (Himg, Wimg) != (512, 512):
             raise ValueError(f'CodeFormer expects aligned 512x512 faces, got {Himg}x{Wimg}')
@@ -337,7 +359,7 @@ class CodeFormer(VQAutoEncoder):
         if self.encoder_precision not in ('auto', 'fp32', 'f16x2'):
             raise ValueError(f"encoder_precision must be 'auto', 'fp32' or 'f16x2', got {self.encoder_precision!r}")
         enc_code = ops.SPLIT if self.encoder_precision == 'f16x2' or (self.encoder_precision == 'auto' and self.precision != 'fp32') else ops.WINOGRAD
-        if self.winograd_f43_encoder:
+        if self.winograd_f43_encoder if f43_encoder is None else f43_encoder:
             enc_code = {ops.SPLIT: ops.SPLIT_F43, ops.WINOGRAD: ops.WINOGRAD_F43}[enc_code]
         lq = self.encoder.forward_nhwc(x, enc_taps, bf16=enc_code)        # (B,16,16,256) channels-last
         T = lq.shape[1] * lq.shape[2]
@@ -355,10 +377,15 @@ class CodeFormer(VQAutoEncoder):
         logits2d = ops.linear(ops.layernorm(X, ln.weight, ln.bias, ln.eps), self._pw_conv(head, bf16=ln_code(self, ln, gcode_ln)))
         logits = logits2d.view(B, T, -1)
         lq_feat = ops.to_nchw(lq)
+        if guard:
+            idx, _, self.last_min_gap = ops.argmax_rows_gap(logits2d, T)   # the same indices + each face's smallest top-2 logit gap
+            if code_only:
+                self.last_indices = idx.view(B, T)
         if code_only:
             return logits, lq_feat
 
-        idx = ops.argmax_rows(logits2d)                                     # == topk(softmax(logits), 1)
+        if not guard:
+            idx = ops.argmax_rows(logits2d)                                 # == topk(softmax(logits), 1)
         quant = ops.codebook_gather(idx, self.quantize.embedding.weight, B, T,
                                     lq=tokens.view(B, T, -1) if adain else None)
         quant = quant.view(B, lq.shape[1], lq.shape[2], -1)
@@ -395,6 +422,9 @@ class CodeFormer(VQAutoEncoder):
         for layer in self.ft_layers:
             query = layer(query, query_pos=pos_emb)
         logits = self.idx_pred_layer(query).permute(1, 0, 2)
+        if self.logit_guard != 'off':   # the host path has one encoder: the gap is reported and counted, nothing is run again
+            self.last_min_gap = top2_gap(logits)[0].min(dim=1).values
+            self._guard_count(self.last_min_gap)
         if code_only:
             return logits, lq_feat
         _, top_idx = torch.topk(F.softmax(logits, dim=2), 1, dim=2)
@@ -412,17 +442,17 @@ class CodeFormer(VQAutoEncoder):
                 x = self.fuse_convs_dict[f](enc_feat[f].detach(), x, w)
         return x, logits, lq_feat
 
-    def _forward_graphed(self, x, w, code_only, adain):
+    def _forward_graphed(self, x, w, code_only, adain, guard=False):
         """Capture-once / replay-many execution of _forward_hip on the current stream.  Outputs are copies, so callers may
         keep them across calls.  A graph is re-captured when any packed weight was rebuilt since its capture."""
         with _GRAPH_LOCK:   # static buffers per shape: two threads replaying one graph would race on them
-            key = (tuple(x.shape), float(w), bool(code_only), bool(adain), self.precision, bool(self.bf16_storage), self.encoder_precision, self.gemm_precision, bool(self.winograd_f43_encoder), str(x.device), ops.switches())
+            key = (tuple(x.shape), float(w), bool(code_only), bool(adain), self.precision, bool(self.bf16_storage), self.encoder_precision, self.gemm_precision, bool(self.winograd_f43_encoder), str(x.device), ops.switches(), bool(guard))
             ent = self._graphs.get(key)
             sig = self._param_signature()
             if ent is None or ent['epoch'] != PACK_EPOCH[0] or ent['sig'] != sig:
                 static_x = x.float().contiguous().clone()
                 for _ in range(2):                      # warm-up: packs weights, sets kernel attributes, primes the allocator
-                    self._forward_hip(static_x, w, code_only, adain)
+                    self._forward_hip(static_x, w, code_only, adain, guard=guard)
                 torch.cuda.synchronize(x.device)
                 graph = torch.cuda.CUDAGraph()
                 # The zero-initialised scratch words of the range-scale / split-K kernels are kept per (device, stream).  Created inside the
@@ -440,11 +470,12 @@ class CodeFormer(VQAutoEncoder):
                 gc.disable()
                 try:
                     with torch.cuda.graph(graph, stream=cap):
-                        outs = self._forward_hip(static_x, w, code_only, adain)
+                        outs = self._forward_hip(static_x, w, code_only, adain, guard=guard)
                 finally:
                     if gc_on:
                         gc.enable()
-                ent = {'graph': graph, 'x': static_x, 'outs': outs, 'epoch': PACK_EPOCH[0], 'sig': sig, 'idx': getattr(self, 'last_indices', None)}
+                ent = {'graph': graph, 'x': static_x, 'outs': outs, 'epoch': PACK_EPOCH[0], 'sig': sig, 'idx': getattr(self, 'last_indices', None),
+                       'gap': self.last_min_gap if guard else None}
                 self._graphs.pop(key, None)
                 while len(self._graphs) >= 4:           # oldest first: a graph pins the activations of its shape
                     self._graphs.pop(next(iter(self._graphs)))
@@ -453,6 +484,8 @@ class CodeFormer(VQAutoEncoder):
             ent['graph'].replay()
             if ent['idx'] is not None:
                 self.last_indices = ent['idx'].clone()   # (a fresh tensor per call, as the eager path returns: the next replay overwrites the graph's own)
+            if ent['gap'] is not None:
+                self.last_min_gap = ent['gap'].clone()   # (the same ownership rule)
             return tuple(o.clone() for o in ent['outs'])
 
     def _param_signature(self):
@@ -503,12 +536,85 @@ class CodeFormer(VQAutoEncoder):
         self.__dict__.pop('_sig_modules', None)
         super().invalidate_packed_weights()
 
+    # ------------------------------------------------------------------ logit guard
+    def reset_guard_stats(self):
+        """Zero the running totals of the logit guard (`guard_stats`)."""
+        self._guard_totals = {'calls': 0, 'faces': 0, 'flagged': 0, 'rerun_faces': 0, 'index_changes': 0, 'min_gap': float('inf')}
+        self._guard_pending = []   # 'report' on the device: (last_min_gap, threshold, None) of calls not read back yet
+
+    @property
+    def guard_stats(self):
+        """Running totals of the logit guard: `calls`, `faces`, `flagged` (faces with `not (min gap >= logit_guard_gap)`), `rerun_faces`,
+        `index_changes` (tokens of re-run faces whose code index differs between the two passes) and `min_gap` (the smallest first-pass gap
+        seen; NaN once a NaN was seen).  'report' adds no synchronisation to a call: its minima are read back here."""
+        self._guard_fold(sync=True)
+        return dict(self._guard_totals)
+
+    def _guard_count(self, gmin, thr=None):
+        """Add the faces of one call, given their minima on the host, to the totals; returns the flagged mask."""
+        thr = self.logit_guard_gap if thr is None else thr
+        flag = ~(gmin >= thr)
+        st = self._guard_totals
+        st['calls'] += 1
+        st['faces'] += int(gmin.numel())
+        st['flagged'] += int(flag.sum())
+        st['min_gap'] = _min_nan(st['min_gap'], float(gmin.min()))
+        return flag
+
+    def _guard_fold(self, sync):
+        """Reduce the pending 'report' minima to one (minimum, threshold, flagged count) entry on the device -- no synchronisation;
+        sync=True: read it into the totals."""
+        pend = self._guard_pending
+        if not pend:
+            return
+        flagged = torch.stack([(~(g >= t)).sum() if f is None else f for g, t, f in pend]).sum()
+        gmin = torch.cat([g.reshape(-1) for g, _, _ in pend]).min()           # (torch.min hands a NaN on)
+        pend[:] = [(gmin, None, flagged)]
+        if sync:
+            st = self._guard_totals
+            st['flagged'] += int(flagged)
+            st['min_gap'] = _min_nan(st['min_gap'], float(gmin))
+            pend.clear()
+
+    def _forward_guarded(self, x, w, code_only, adain, graphed):
+        guard = self.logit_guard
+        outs = (self._forward_graphed if graphed else self._forward_hip)(x, w, code_only, adain, guard=True)
+        gmin = self.last_min_gap
+        if guard == 'report':
+            st = self._guard_totals
+            st['calls'] += 1
+            st['faces'] += int(x.shape[0])
+            self._guard_pending.append((gmin, float(self.logit_guard_gap), None))
+            if len(self._guard_pending) >= 64:
+                self._guard_fold(sync=False)
+            return outs
+        flag = self._guard_count(gmin.cpu())            # the one read-back of the call
+        if not bool(flag.any()) or not self.winograd_f43_encoder:
+            return outs                                 # (an F(2x2,3x3) encoder has nothing to fall back to: faces are counted only)
+        sel = flag.nonzero().flatten().to(x.device)
+        idx = self.last_indices
+        # second pass: the flagged faces as one batch, eagerly (it neither captures a graph nor evicts one)
+        outs2 = self._forward_hip(x.index_select(0, sel), w, code_only, adain, f43_encoder=False, guard=True)
+        st = self._guard_totals
+        st['rerun_faces'] += int(sel.numel())
+        st['index_changes'] += int((idx.index_select(0, sel) != self.last_indices).sum())
+        for o, o2 in zip(outs, outs2):
+            o.index_copy_(0, sel, o2)
+        self.last_indices = idx.index_copy_(0, sel, self.last_indices)
+        self.last_min_gap = gmin.index_copy_(0, sel, self.last_min_gap)
+        return outs
+
     def forward(self, x, w=0, detach_16=True, code_only=False, adain=False):
+        if self.logit_guard not in ('off', 'report', 'rerun'):
+            raise ValueError(f"logit_guard must be 'off', 'report' or 'rerun', got {self.logit_guard!r}")
         if x.is_cuda:
             ops.L.ensure_device(x.device)   # kernel attributes on the tensor's device, before (never inside) a capture
             with torch.no_grad(), torch.cuda.device(x.device):
                 graphed = self.use_hip_graphs is True or (self.use_hip_graphs == 'auto' and x.shape[0] <= self.graph_max_batch)
-                if graphed and ops.PROFILE is None and not torch.cuda.is_current_stream_capturing():
+                graphed = graphed and ops.PROFILE is None and not torch.cuda.is_current_stream_capturing()
+                if self.logit_guard != 'off':
+                    return self._forward_guarded(x, w, code_only, adain, graphed)
+                if graphed:
                     return self._forward_graphed(x, w, code_only, adain)
                 return self._forward_hip(x, w, code_only, adain)
         return self._forward_host(x, w, detach_16, code_only, adain)

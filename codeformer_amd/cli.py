@@ -59,7 +59,44 @@ def load_faces(paths, size=None, require=None):
     return faces
 
 
-def build_codeformer(device, ckpt_name, url, codebook_size, connect_list, random_init_seed=None):
+LOGIT_GUARD_CHOICES = ('auto', 'off', 'report', 'rerun')
+
+
+def add_logit_guard_arg(parser):
+    parser.add_argument('--logit_guard', choices=LOGIT_GUARD_CHOICES, default='auto',
+                        help="top-2 logit-gap guard of the code prediction (CodeFormer.logit_guard): 'rerun' runs faces whose smallest gap is "
+                             "below CODEFORMER_HIP_LOGIT_GUARD_GAP (1.1e-4) again with the F(2x2,3x3) encoder, 'report' only measures, "
+                             "'auto' = 'rerun' for weights loaded from a checkpoint, 'off' for --random_init_seed weights "
+                             "(unless CODEFORMER_HIP_LOGIT_GUARD is set)")
+
+
+def resolve_logit_guard(flag, weights_from_checkpoint):
+    """--logit_guard -> CodeFormer.logit_guard.  'auto': trained weights have never been through the F(4x4,3x3) encoder gate, so they get
+    the guard ('rerun'); seeded random weights are what that gate was measured with ('off').  Explicit values pass through."""
+    if flag not in LOGIT_GUARD_CHOICES:
+        raise ValueError(f'--logit_guard must be one of {LOGIT_GUARD_CHOICES}, got {flag!r}')
+    if flag == 'auto':
+        return 'rerun' if weights_from_checkpoint else 'off'
+    return flag
+
+
+def apply_logit_guard(net, flag, weights_from_checkpoint):
+    """Set net.logit_guard from the flag; with 'auto' an explicit CODEFORMER_HIP_LOGIT_GUARD (read by the constructor) is left alone."""
+    if not (flag == 'auto' and 'CODEFORMER_HIP_LOGIT_GUARD' in os.environ):
+        net.logit_guard = resolve_logit_guard(flag, weights_from_checkpoint)
+    return net
+
+
+def guard_summary(net):
+    """The one summary line of a run with the guard on (None when it is off)."""
+    if getattr(net, 'logit_guard', 'off') == 'off':
+        return None
+    st = net.guard_stats
+    return (f"logit guard ({net.logit_guard}, gap < {net.logit_guard_gap:g}): {st['faces']} faces, {st['flagged']} flagged, "
+            f"{st['rerun_faces']} re-run, {st['index_changes']} indices changed, smallest gap {st['min_gap']:.3g}")
+
+
+def build_codeformer(device, ckpt_name, url, codebook_size, connect_list, random_init_seed=None, logit_guard='auto'):
     """ARCH_REGISTRY CodeFormer + checkpoint from weights/CodeFormer (never downloads; optional seeded random init)."""
     from .utils.download_util import load_file_from_url
     from .utils.registry import ARCH_REGISTRY
@@ -72,7 +109,7 @@ def build_codeformer(device, ckpt_name, url, codebook_size, connect_list, random
             raise
         print(f'WARNING: {ckpt_name} not found -- using torch.manual_seed({random_init_seed}) random weights')
         torch.manual_seed(random_init_seed)
-        return ARCH_REGISTRY.get('CodeFormer')(**kw).to(device).eval()
+        return apply_logit_guard(ARCH_REGISTRY.get('CodeFormer')(**kw).to(device).eval(), logit_guard, False)
     net = ARCH_REGISTRY.get('CodeFormer')(**kw)
     net.load_state_dict(torch.load(ckpt, map_location='cpu')['params_ema'])
-    return net.to(device).eval()
+    return apply_logit_guard(net.to(device).eval(), logit_guard, True)

@@ -89,6 +89,61 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   if (lane == 0) idx[row] = bi;
 }
 
+// ---- argmax + top-2 gap: the same wave-per-row scan carrying (best value, best index, second value) ----
+// `second` is the largest value at any index other than the winner's, so a duplicated maximum gives best - second == 0.
+__device__ __forceinline__ void argbest2(float& v, int& i, float& s, float ov, int oi, float os) {
+  if (ov > v || (ov == v && oi < i)) {
+    s = fmaxf(v, os);
+    v = ov;
+    i = oi;
+  } else {
+    s = fmaxf(s, ov);
+  }
+}
+
+__global__ __launch_bounds__(256) void argmax_rows_gap_kernel(const float* __restrict__ x, int rows, int n, int64_t* __restrict__ idx,
+                                                              float* __restrict__ gap) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* xr = x + (size_t)row * n;
+  float best = -INFINITY, second = -INFINITY;
+  int bi = 0x7fffffff;
+  int nan = 0;   // the comparisons skip a NaN element (as in argmax_rows_kernel); the row's gap is made NaN instead
+  for (int c = lane * 4; c < n; c += 256) {  // ascending index within a lane
+    const f32x4 v = *reinterpret_cast<const f32x4*>(xr + c);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      argbest2(best, bi, second, v[e], c + e, -INFINITY);
+      nan |= (v[e] != v[e]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    const float os = __shfl_xor(second, o, 64);
+    nan |= __shfl_xor(nan, o, 64);
+    argbest2(best, bi, second, ov, oi, os);
+  }
+  if (lane == 0) {
+    idx[row] = bi;
+    gap[row] = nan ? __builtin_nanf("") : best - second;   // (-inf) - (-inf) and inf - inf are NaN by themselves
+  }
+}
+
+// minimum of `per` consecutive gaps per group, one wave per group; a NaN gap makes the group's minimum NaN (like torch.min)
+__device__ __forceinline__ float min_nan(float a, float b) { return (b < a || b != b) ? b : a; }
+
+__global__ __launch_bounds__(64) void group_min_kernel(const float* __restrict__ gap, int per, float* __restrict__ out) {
+  const float* g = gap + (size_t)blockIdx.x * per;
+  float m = INFINITY;
+  for (int r = threadIdx.x; r < per; r += 64) m = min_nan(m, g[r]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = min_nan(m, __shfl_xor(m, o, 64));
+  if (threadIdx.x == 0) out[blockIdx.x] = m;
+}
+
 // ---- nearest code: d_j = (zz + ee_j) - 2*s_j in the reference's operation order, argmin ----------
 __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict__ scores, const float* __restrict__ zz,
                                                         const float* __restrict__ ee, int rows, int n,
@@ -461,6 +516,19 @@ extern "C" int cf_argmax_rows(const float* logits, int rows, int n, int64_t* idx
   CF_REQUIRE(logits && idx && rows > 0 && n > 0 && n % 4 == 0, "cf_argmax_rows: bad args (n=%d must be a multiple of 4)", n);
   hipLaunchKernelGGL(argmax_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, rows, n, idx);
   CF_CHECK_LAUNCH("cf_argmax_rows");
+  return CF_OK;
+}
+
+extern "C" int cf_argmax_rows_gap(const float* logits, int rows, int n, int rows_per_group, int64_t* idx, float* gap, float* group_min_gap,
+                                  cf_stream_t stream) {
+  CF_REQUIRE(logits && idx && gap && group_min_gap && rows > 0 && n > 0 && n % 4 == 0,
+             "cf_argmax_rows_gap: bad args (n=%d must be a multiple of 4)", n);
+  CF_REQUIRE(rows_per_group > 0 && rows % rows_per_group == 0, "cf_argmax_rows_gap: rows=%d is not a multiple of rows_per_group=%d", rows,
+             rows_per_group);
+  hipLaunchKernelGGL(argmax_rows_gap_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, rows, n, idx, gap);
+  CF_CHECK_LAUNCH("cf_argmax_rows_gap");
+  hipLaunchKernelGGL(group_min_kernel, dim3(rows / rows_per_group), dim3(64), 0, (hipStream_t)stream, gap, rows_per_group, group_min_gap);
+  CF_CHECK_LAUNCH("cf_argmax_rows_gap (group minimum)");
   return CF_OK;
 }
 

@@ -82,6 +82,7 @@ SIGNATURES = {
     'cf_layernorm': (_I, [_P, _I, _I, _P, _P, _F, _P, _I, _P, _P, _P]),
     'cf_attention': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P]),
     'cf_argmax_rows': (_I, [_P, _I, _I, _P, _P]),
+    'cf_argmax_rows_gap': (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     'cf_codebook_gather_adain': (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _F, _P, _P]),
     'cf_row_sqnorm': (_I, [_P, _I, _I, _P, _P]),
     'cf_vq_argmin': (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),

@@ -787,6 +787,22 @@ def argmax_rows(logits):
     return idx
 
 
+def argmax_rows_gap(logits, rows_per_group):
+    """argmax_rows plus the top-2 gap of every row and its minimum over groups of `rows_per_group` consecutive rows (a face: 256
+    tokens).  Returns (idx int64 (rows,), gap fp32 (rows,), group_min_gap fp32 (rows / rows_per_group,)); a NaN gap makes its group NaN."""
+    lib = L.load()
+    rows, n = logits.shape
+    rows_per_group = int(rows_per_group)
+    if rows_per_group <= 0 or rows % rows_per_group:
+        raise ValueError(f'argmax_rows_gap: {rows} rows are not a multiple of rows_per_group={rows_per_group}')
+    idx = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    gap = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    gmin = torch.empty(rows // rows_per_group, dtype=torch.float32, device=logits.device)
+    L.check(lib.cf_argmax_rows_gap(L.ptr(_f32(logits)), rows, n, rows_per_group, L.ptr(idx, dtype=torch.int64), L.ptr(gap), L.ptr(gmin),
+                                   L.stream_ptr()), 'cf_argmax_rows_gap')
+    return idx, gap, gmin
+
+
 def codebook_gather(idx, codebook, batch, ntok, lq=None, eps=1e-5):
     """idx: (batch*ntok,) int64 -> (batch, ntok, dim); AdaIN against lq (batch, ntok, dim) when given."""
     lib = L.load()

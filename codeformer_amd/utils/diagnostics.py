@@ -9,8 +9,10 @@ def top2_gap(logits):
     the reference's logits to ~1e-5 (7e-6 on the goldens, tolerance 1e-4), so an index can only differ from the reference's where this gap is of
     that order.  The gate that admitted Winograd F(4x4,3x3) into the ENCODER (tests/test_gpu_real_images.py::test_encoder_logit_margin)
     was measured with seed-0 random-init weights -- the reference ships no checkpoint -- on seeded noise, the reference's real crops and
-    synthetic range variants: smallest (gap / 2 x logit error) 7.0.  With a trained checkpoint, look at this number on your own crops: if the
-    smallest gap comes near 1e-4, set CODEFORMER_HIP_F43_ENCODER=0 (F(2x2,3x3) in the encoder: a fifth of the per-layer error, -4 % / -9 % speed).
+    synthetic range variants: smallest (gap / 2 x logit error) 7.0.  The network can act on this number itself: CodeFormer.logit_guard
+    ('report' / 'rerun', CODEFORMER_HIP_LOGIT_GUARD) computes the same gap on the device in the argmax launch (cf_argmax_rows_gap, bitwise this
+    function's values; `net.last_min_gap` is `gaps.min(dim=1)`) and runs the faces below `logit_guard_gap` (1.1e-4) again with the F(2x2,3x3)
+    encoder.  This function stays the host-side statement of the rule, and what CPU tensors are measured with.
     Returns (gaps (B, T), min gap as a Python float)."""
     top = torch.topk(logits.detach().float(), 2, dim=-1).values
     gaps = top[..., 0] - top[..., 1]

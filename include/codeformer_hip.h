@@ -327,6 +327,16 @@ int cf_attention(const float* q, int ldq, const float* k, int ldk, const float* 
 /* ---- code prediction (codeformer_arch.py:257-258 softmax+topk(1)) ------------------------------
  * argmax over each fp32 row, lowest index wins ties; idx is int64 like the reference's top_idx. */
 int cf_argmax_rows(const float* logits, int rows, int n, int64_t* idx, cf_stream_t stream);
+/* The same argmax plus the top-2 logit gap (the logit guard of CodeFormer.forward; entry point added, ABI version unchanged):
+ * idx[row]  bitwise cf_argmax_rows';
+ * gap[row]  = best - second in one fp32 subtraction, `second` the largest value of the row at any index other than idx[row] (a second element
+ *             equal to the maximum gives exactly 0.0f) == torch.topk(row, 2).values[0] - values[1];
+ * group_min_gap[g] = min of gap over rows [g*rows_per_group, (g+1)*rows_per_group) (a face: 256 tokens); rows % rows_per_group == 0.
+ * NaN: a row that holds a NaN element, or whose two largest values are the same infinity, gets gap = NaN, and a NaN gap makes its group's
+ * minimum NaN -- so `!(group_min_gap >= threshold)` flags the group for every threshold.
+ * Two launches on `stream` (the row scan, then one wave per group), no host synchronisation, nothing to initialise, capturable. */
+int cf_argmax_rows_gap(const float* logits, int rows, int n, int rows_per_group, int64_t* idx, float* gap, float* group_min_gap,
+                       cf_stream_t stream);
 
 /* ---- codebook lookup (+ AdaIN) (vqgan_arch.py:72-84, codeformer_arch.py:12-43,266) -------------
  * out[b][p][:] = codebook[idx[b][p]][:]; when adain != 0 the per-(b,c) statistics over the ntok positions

@@ -28,7 +28,7 @@ from basicsr.utils.download_util import load_file_from_url  # noqa: E402
 from basicsr.utils.img_util import imread_bgr, resize_bilinear  # noqa: E402
 from basicsr.utils.misc import get_device  # noqa: E402
 from basicsr.utils.registry import ARCH_REGISTRY  # noqa: E402
-from codeformer_amd.cli import faces_to_tensor, tensor_to_faces  # noqa: E402
+from codeformer_amd.cli import add_logit_guard_arg, apply_logit_guard, faces_to_tensor, guard_summary, tensor_to_faces  # noqa: E402
 from codeformer_amd.utils.face_misc import AlignedFaceHelper, is_gray  # noqa: E402
 
 pretrain_model_url = {
@@ -60,6 +60,7 @@ def parse_args(argv=None):
     p.add_argument('--random_init_seed', type=int, default=None,
                    help='Use torch.manual_seed(SEED) random weights when weights/CodeFormer/codeformer.pth is absent '
                         '(plumbing runs on boxes without the checkpoint)')
+    add_logit_guard_arg(p)
     p.add_argument('--affine_npz', type=str, default=None,
                    help='whole-image inputs: .npz mapping image basename -> (k,2,3) alignment matrices, instead of running the detector')
     p.add_argument('--det_device', type=str, default='auto',
@@ -213,6 +214,8 @@ def restore_whole_images(args, input_img_list, result_root, w):
     print(f"{totals['faces']} faces of {totals['frames']} images in {totals['forward_calls']} forward calls")
     if face_upsampler is not None:
         print(f"faces upsampled in {totals['upsampler_calls']} batched Real-ESRGAN calls")
+    if guard_summary(net):
+        print(guard_summary(net))
     if failed:
         print(f'{len(failed)} image(s) failed: {failed[:8]}{" ..." if len(failed) > 8 else ""}')
     print(f'\nAll results are saved in {result_root}')
@@ -245,7 +248,8 @@ def build_net(device, args):
         torch.manual_seed(args.random_init_seed)
         net = ARCH_REGISTRY.get('CodeFormer')(dim_embd=512, codebook_size=1024, n_head=8, n_layers=9,
                                               connect_list=['32', '64', '128', '256'])
-    return net.to(device).eval()
+        return apply_logit_guard(net.to(device).eval(), getattr(args, 'logit_guard', 'auto'), False)
+    return apply_logit_guard(net.to(device).eval(), getattr(args, 'logit_guard', 'auto'), True)
 
 
 FACE_UPSAMPLER_SCALE = 2   # RealESRGAN_x2plus, the reference's face upsampler (inference_codeformer.py:19-45)
@@ -352,6 +356,8 @@ def main(argv=None):
             restored = tensor_to_faces(x)
         for img_path, face, out, g in zip(chunk, faces, restored, grays):
             imwrite(finish_face(face, out, g), out_name(img_path))
+    if guard_summary(net):
+        print(guard_summary(net))
     if failures:
         print(f'WARNING: {failures} face(s) fell back to the unrestored input')
     print(f'\nAll results are saved in {result_root}')

@@ -26,13 +26,14 @@ def main(argv=None):
     p.add_argument('--batch_size', type=int, default=None)
     p.add_argument('--device', type=str, default=None)
     p.add_argument('--random_init_seed', type=int, default=None)
+    cli.add_logit_guard_arg(p)
     args = p.parse_args(argv)
     device = torch.device(args.device) if args.device else get_device()
     print('[NOTE] The input face images should be aligned and cropped to a resolution of 512x512.')
     paths, folder = cli.list_images(args.input_path)
     result_root = args.output_path or ('results/test_colorization_img' if folder is None else f'results/{folder}')
     net = cli.build_codeformer(device, 'codeformer_colorization.pth', pretrain_model_url, 1024, ['32', '64', '128'],
-                               args.random_init_seed)
+                               args.random_init_seed, args.logit_guard)
     bs = args.batch_size or (16 if device.type == 'cuda' else 1)
     for s in range(0, len(paths), bs):
         chunk = paths[s:s + bs]
@@ -50,6 +51,8 @@ def main(argv=None):
             if args.suffix is not None:
                 base = f'{base}_{args.suffix}'
             imwrite(face.astype('uint8'), os.path.join(result_root, f'{base}.png'))
+    if cli.guard_summary(net):
+        print(cli.guard_summary(net))
     print(f'\nAll results are saved in {result_root}')
 
 
