@@ -17,7 +17,7 @@
 // (MI*32) x (NI*32) sub-tile in MI*NI*16 accumulator registers.
 #include <type_traits>
 
-#include "cf_common.h"
+#include "cf_conv_parts.h"
 
 namespace {
 
@@ -63,6 +63,7 @@ struct ConvArgsSK : ConvArgs {
   unsigned* counters;
   int nsplit;
 };
+static_assert(sizeof(ConvArgs) == 176 && sizeof(ConvArgsExt) == 200 && sizeof(ConvArgsSK) == 200, "the kernarg blocks keep their size: it feeds the register allocation of every instantiation");
 template <bool EXT, bool SK = false>
 using ArgsOf = std::conditional_t<SK, ConvArgsSK, std::conditional_t<EXT, ConvArgsExt, ConvArgs>>;
 template <bool EXT, bool SK = false>
@@ -771,8 +772,9 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
       }
     }
     if (!EXT && a.stats_out) {
-      // GroupNorm statistics of the values just written, for the NEXT norm: one fp64 partial per (image, group,
-      // tile, wave row), combined in a fixed shuffle order -> the later finalize is a deterministic sum.
+      // GroupNorm statistics of the values just written, for the NEXT norm: cf_gn_partials<CF_GN_PAIR> (cf_conv_parts.h) written out, one
+      // partial per (image, group, tile, wave row).  This epilogue keeps its own text (edge-tile mask, dense-block epilogues): with
+      // the shared quad helpers most instantiations compiled to other code.
       const int cpg = a.stats_cpg;
       double d0, q0, d1 = 0, q1 = 0;
       if (cpg == 2) {  // two groups per lane
@@ -797,8 +799,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
       if (rl == 0 && nvalid && (n % cpg) == 0) {
         const int tile_in_img = (TAPS > 1) ? (mt - b * a.tiles_per_img) : (m0 - b * (a.hout * a.wout)) / C::BM;
         const size_t pidx = (size_t)tile_in_img * WM + wm;
-        const int ng = a.cout / cpg;
-        double* o = a.stats_out + (((size_t)b * ng + n / cpg) * a.nparts + pidx) * 2;
+        double* o = cf_gn_partial_ptr(a.stats_out, b, a.cout, cpg, n, a.nparts, pidx);
         o[0] = d0;
         o[1] = q0;
         if (cpg == 2) {
@@ -1277,13 +1278,6 @@ extern "C" int cf_pack_conv_weight(const float* w, int cout, int cin, int taps, 
   return CF_OK;
 }
 
-int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);  // cf_winograd.hip
-int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);      // cf_wf43.hip
-int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream);                     // cf_gemm_split.hip
-int cf_gemm_split_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_part);
-int cf_gemm_f32_tile_try(const cf_conv_desc* d, hipStream_t stream);                     // cf_gemm_split.hip: fp32 token tiles (CF_OK: launched, 1: not its shape)
-int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);     // cf_split.hip
-
 static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
   CF_REQUIRE(d, "cf_conv2d: null descriptor");
   CF_REQUIRE(pq || (d->in0 && d->weight && d->out), "cf_conv2d: null in0/weight/out");
@@ -1396,32 +1390,15 @@ static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
   if (d->bf16_mfma == CF_OPERAND_F16X2) return cf_split_launch(d, stream, pq);
 
   ConvArgsExt a;
-  a.in0 = d->in0;
-  a.in1 = d->in1;
-  a.c0 = d->c0;
-  a.c1 = d->c1;
-  a.cin = d->c0 + d->c1;
+  cf_fill_conv_args(a, d);
   a.nchunks = d->bf16_mfma ? a.cin / 32 : (a.cin + CF_BK - 1) / CF_BK;
-  a.batch = d->batch;
   a.hin = d->hin;
   a.win = d->win;
   a.hout = d->hout;
   a.wout = d->wout;
-  a.cout = d->cout;
   a.cout_pad = d->cout_pad;
   a.upsample = d->upsample ? 1 : 0;
   a.out_nchw = d->out_nchw;
-  a.prologue = d->prologue;
-  a.epilogue = d->epilogue;
-  a.pro_scale = d->pro_scale;
-  a.pro_shift = d->pro_shift;
-  a.weight = d->weight;
-  a.bias = d->bias;
-  a.res = d->res;
-  a.sft_scale = d->sft_scale;
-  a.sft_w = d->sft_w;
-  a.out = d->out;
-  a.stats_out = d->stats_out;
   a.stats_cpg = d->stats_cpg > 0 ? d->stats_cpg : 1;
   a.nparts = 0;
   a.tiles_x = a.tiles_per_img = a.ntn = 0;
@@ -1550,8 +1527,6 @@ static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
 extern "C" int cf_conv2d(const cf_conv_desc* d, cf_stream_t stream) { return conv_dispatch(d, (hipStream_t)stream, nullptr); }
 
 // split-K geometry: output tiles of the launch and accumulator bytes one (tile, split) parks in the workspace
-int cf_winograd_splitk_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_part);  // cf_winograd.hip
-int cf_split_splitk_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_part);     // cf_split.hip
 static int splitk_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_part) {
   *tiles = 0;
   *bytes_per_part = 0;

@@ -44,13 +44,10 @@
 
 #include <cstdlib>
 
-#include "cf_common.h"
+#include "cf_conv_parts.h"
 
 // SP_ABLATE: timing-only ablation builds (tools/split_ab.sh), a bit mask: 1 no epilogue, 2 no weight fetch, 4 no weight LDS write,
 // 8 no fragment reads, 16 no per-step barrier, 32 no MFMA, 64 no activation gather, 128 no prologue/split; 0 in every product build.
-#ifndef SP_FAST_RCP
-#define SP_FAST_RCP 1   // 1: swish reciprocal on the raw v_rcp_f32 (1 ulp) instead of the IEEE-rounded division sequence: +4..8 %
-#endif
 // SP_WEAVE: 1 = fragment reads / weight fetches / weight LDS writes are woven one-by-one into the MFMA stream (sched_group_barrier)
 #ifndef SP_NARROW_OCC
 #define SP_NARROW_OCC 3  // workgroups per CU the 64-wide-tile instantiations are compiled for (47 KB LDS each; 168 VGPRs)
@@ -107,6 +104,7 @@ struct SplitArgs {
   int nt_out;   // non-temporal output stores (cf_common.h: cf_store16)
   int s2_skip;  // stride-2 form: 1 = skip the (tap, parity) steps whose weight block is zero by construction (C % 32 == 0)
 };
+static_assert(sizeof(SplitArgs) == 184, "the kernarg block keeps its size: it feeds the register allocation of every instantiation");
 
 template <int TAPS, int NI, int WM>
 struct SplitCfg {
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
           if (PRO == CF_PRO_AFFINE) v = v * r.sc[u][e] + r.sh[u][e];
           if (PRO == CF_PRO_AFFINE_SWISH) {
             v = v * r.sc[u][e] + r.sh[u][e];
-            v = SP_FAST_RCP ? v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)) : v * __frcp_rn(1.0f + __expf(-v));  // hardware exp / rcp swish
+            v = cf_swish(v);
           }
           if (PRO == CF_PRO_LEAKY) v = v * (v > 0.f ? act_s : act_s02);
           if (PRO == CF_PRO_NONE) v = v * act_s;
@@ -533,7 +531,6 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
     float* stage = smem + wave * (32 * LDW);
     const int cq = lane % Q, rl = lane / Q;
     const int n = n0 + wn * (NI * 32) + cq * 4;  // (always < cout: the host requires cout % 64 == 0)
-    constexpr bool nvalid = true;
     f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
     if (a.bias) bias4 = *reinterpret_cast<const f32x4*>(a.bias + n);
     const float s = a.acc_scale * act_is;  // (a product of powers of two: exact)
@@ -554,13 +551,8 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
           pixel = ((unsigned)b * a.hout + (y0 + (row >> 4))) * a.wout + (x0 + (row & 15));
         offs[mi][p] = pixel * (unsigned)a.cout + n;
         r0[mi][p] = r1[mi][p] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (BIO) {
-          if (EPI == CF_EPI_RESIDUAL || EPI == CF_EPI_SFT) r0[mi][p] = cf_load4_bf16(a.res, offs[mi][p]);
-          if (EPI == CF_EPI_SFT) r1[mi][p] = cf_load4_bf16(a.sft_scale, offs[mi][p]);
-        } else {
-          if (EPI == CF_EPI_RESIDUAL || EPI == CF_EPI_SFT) r0[mi][p] = *reinterpret_cast<const f32x4*>(a.res + offs[mi][p]);
-          if (EPI == CF_EPI_SFT) r1[mi][p] = *reinterpret_cast<const f32x4*>(a.sft_scale + offs[mi][p]);
-        }
+        if (EPI == CF_EPI_RESIDUAL || EPI == CF_EPI_SFT) r0[mi][p] = cf_epi_load4<BIO>(a.res, offs[mi][p]);
+        if (EPI == CF_EPI_SFT) r1[mi][p] = cf_epi_load4<BIO>(a.sft_scale, offs[mi][p]);
       }
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
@@ -577,16 +569,8 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
       for (int p = 0; p < PASSES; ++p) t[p] = *reinterpret_cast<const f32x4*>(stage + (p * RPP + rl) * LDW + cq * 4);
 #pragma unroll
       for (int p = 0; p < PASSES; ++p) {
-        f32x4 v = t[p];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] * s + bias4[e];
-        if (EPI == CF_EPI_RESIDUAL) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += r0[mi][p][e];
-        } else if (EPI == CF_EPI_SFT) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = r0[mi][p][e] + a.sft_w * (r0[mi][p][e] * r1[mi][p][e] + v[e]);
-        }
+        f32x4 v = cf_epi_bias<true>(t[p], s, bias4);
+        v = cf_epi_apply(v, EPI, r0[mi][p], r1[mi][p], a.sft_w);
         t[p] = v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -608,8 +592,8 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
       __builtin_amdgcn_wave_barrier();  // the staging rows are rewritten by the next 32-row block
     }
     if (a.stats_out) {
-      // GroupNorm statistics of the values just written (fp64 partials, fixed shuffle order): one partial per
-      // (image, group, tile, wave row) -- nparts = tiles_per_img * WM
+      // cf_gn_partials<CF_GN_PAIR> (cf_conv_parts.h) written out: one partial per (image, group, tile, wave row) -- nparts =
+      // tiles_per_img * WM.  Called as the helper, the 128-channel instantiations were scheduled with one s_nop / s_waitcnt less.
       const int cpg = a.stats_cpg;
       double d0, q0, d1 = 0, q1 = 0;
       if (cpg == 2) {  // two groups per lane
@@ -631,10 +615,9 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
         d0 += __shfl_xor(d0, o, 64);
         q0 += __shfl_xor(q0, o, 64);
       }
-      if (rl == 0 && nvalid && (n % cpg) == 0) {
+      if (rl == 0 && (n % cpg) == 0) {
         const size_t pidx = (size_t)(mt - b * a.tiles_per_img) * WM + wm;
-        const int ng = a.cout / cpg;
-        double* o = a.stats_out + (((size_t)b * ng + n / cpg) * a.nparts + pidx) * 2;
+        double* o = cf_gn_partial_ptr(a.stats_out, b, a.cout, cpg, n, a.nparts, pidx);
         o[0] = d0;
         o[1] = q0;
         if (cpg == 2) {
@@ -762,10 +745,7 @@ int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query)
   CF_REQUIRE(d->acc_scale > 0.f, "cf_conv2d(f16x2): acc_scale must be the inverse of the pack-time weight scale (got %g)",
              (double)d->acc_scale);
   SplitArgs a;
-  a.in0 = d->in0;
-  a.in1 = d->in1;
-  a.c0 = d->c0;
-  a.c1 = d->c1;
+  cf_fill_conv_args(a, d);
   a.hin = d->hin;
   a.win = d->win;
   if (s2) {  // space-to-depth view: even tensor rows through in0, odd rows through in1, 2C channels (two pixels) each
@@ -776,24 +756,11 @@ int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query)
   }
   a.cin = a.c0 + a.c1;
   a.nchunks = a.cin / SP_KC;
-  a.batch = d->batch;
   a.hout = d->hout;
   a.wout = d->wout;
-  a.cout = d->cout;
   a.cout_pad = d->cout_pad;
-  a.prologue = d->prologue;
-  a.epilogue = d->epilogue;
-  a.pro_scale = d->pro_scale;
-  a.pro_shift = d->pro_shift;
-  a.weight = d->weight;
-  a.bias = d->bias;
-  a.res = d->res;
-  a.sft_scale = d->sft_scale;
-  a.sft_w = d->sft_w;
   a.acc_scale = d->acc_scale;
   a.act_scale = d->act_scale;
-  a.out = d->out;
-  a.stats_out = d->stats_out;
   a.stats_cpg = d->stats_cpg > 0 ? d->stats_cpg : 1;
   a.tiles_x = gw / 16;  // tiles live on the SOURCE grid (== the output grid unless upsample; stride 2: the space-to-depth grid)
   a.tiles_per_img = (d->upsample ? 4 : 1) * a.tiles_x * (gh / TH);

@@ -65,7 +65,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "cf_common.h"
+#include "cf_conv_parts.h"
 
 
 
@@ -137,6 +137,7 @@ struct F4Args {
   int tiles_x, tiles_per_img, ntn;
   int nt_out;   // non-temporal output stores (cf_common.h: cf_store16)
 };
+static_assert(sizeof(F4Args) == 160, "the kernarg block keeps its size: it feeds the register allocation of every instantiation");
 
 // quad swizzle of V: tile row ty -> 0, 2, 3, 1
 __device__ __forceinline__ int f4_vs(int ty) { return (0x78 >> (2 * ty)) & 3; }
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
         if (PRO == CF_PRO_AFFINE) y = y * sc[e] + sh[e];
         if (PRO == CF_PRO_AFFINE_SWISH) {
           y = y * sc[e] + sh[e];
-          y = y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));  // same hardware exp / rcp swish as the other conv kernels
+          y = cf_swish(y);
         }
         if (PRO == CF_PRO_LEAKY) y = y * (y > 0.f ? act_s : act_s02);
         if (PRO == CF_PRO_NONE) y = y * act_s;
@@ -856,8 +857,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
         s0 += sred[((wave + wv) * 32 + (lane & 31)) * 2];
         s1 += sred[((wave + wv) * 32 + (lane & 31)) * 2 + 1];
       }
-      const int ng = a.cout / cpg;
-      double* op = a.stats_out + (((size_t)b * ng + nn / cpg) * a.nparts + rt) * 2;
+      double* op = cf_gn_partial_ptr(a.stats_out, b, a.cout, cpg, nn, a.nparts, rt);
       op[0] = s0;
       op[1] = s1;
     }
@@ -1012,29 +1012,12 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
   CF_REQUIRE(d->stats_cpg == 0 || (d->stats_cpg <= 64 && (d->stats_cpg & (d->stats_cpg - 1)) == 0 && d->stats_cpg >= 2),
              "cf_conv2d(winograd 2): stats_cpg %d (a power of two, 2..64)", d->stats_cpg);
   F4Args a;
-  a.in0 = d->in0;
-  a.in1 = d->in1;
-  a.c0 = d->c0;
-  a.c1 = d->c1;
-  a.cin = d->c0 + d->c1;
+  cf_fill_conv_args(a, d);
   a.nchunks = a.cin / CF_BK;
-  a.batch = d->batch;
   a.h = d->hout;
   a.w = d->wout;
-  a.cout = d->cout;
-  a.prologue = d->prologue;
-  a.epilogue = d->epilogue;
-  a.pro_scale = d->pro_scale;
-  a.pro_shift = d->pro_shift;
-  a.weight = d->weight;
-  a.bias = d->bias;
-  a.res = d->res;
-  a.sft_scale = d->sft_scale;
-  a.sft_w = d->sft_w;
   a.acc_scale = f32 ? 1.f : d->acc_scale;
   a.act_scale = d->act_scale;
-  a.out = d->out;
-  a.stats_out = d->stats_out;
   a.stats_cpg = d->stats_cpg > 0 ? d->stats_cpg : 2;
   a.tiles_x = d->wout / F4_TW;
   a.tiles_per_img = a.tiles_x * (d->hout / F4_TH);

@@ -39,7 +39,7 @@
 //     cannot hide the LDS / transcendental latencies of the A-side work.
 #include <type_traits>
 
-#include "cf_common.h"
+#include "cf_conv_parts.h"
 
 namespace {
 
@@ -86,6 +86,7 @@ struct WinoArgsSK : WinoArgs {
   unsigned* counters;
   int nsplit;
 };
+static_assert(sizeof(WinoArgs) == 168 && sizeof(WinoArgsSK) == 192, "the kernarg blocks keep their size: it feeds the register allocation of every instantiation");
 
 __device__ __forceinline__ f32x4 v4add(f32x4 a, f32x4 b) { return a + b; }
 __device__ __forceinline__ f32x4 v4sub(f32x4 a, f32x4 b) { return a - b; }
@@ -211,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
           if (PRO == CF_PRO_AFFINE) y = y * sc[e] + sh[e];
           if (PRO == CF_PRO_AFFINE_SWISH) {
             y = y * sc[e] + sh[e];
-            y = y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));  // same hardware exp / rcp swish as the direct kernel
+            y = cf_swish(y);
           }
           if (PRO == CF_PRO_LEAKY) y = H2 ? y * (y > 0.f ? act_s : act_s02) : (y > 0.f ? y : 0.2f * y);
           if (H2 && PRO == CF_PRO_NONE) y = y * act_s;
@@ -441,8 +442,8 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
         const unsigned off = e_base + (unsigned)(k * 4 + aa) * e_rowc + pass * 32;
         offs[pass][k * 2 + aa] = off;
         r0[pass][k * 2 + aa] = r1[pass][k * 2 + aa] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (a.epilogue == CF_EPI_RESIDUAL || a.epilogue == CF_EPI_SFT) r0[pass][k * 2 + aa] = *reinterpret_cast<const f32x4*>(a.res + off);
-        if (a.epilogue == CF_EPI_SFT) r1[pass][k * 2 + aa] = *reinterpret_cast<const f32x4*>(a.sft_scale + off);
+        if (a.epilogue == CF_EPI_RESIDUAL || a.epilogue == CF_EPI_SFT) r0[pass][k * 2 + aa] = cf_epi_load4<false>(a.res, off);
+        if (a.epilogue == CF_EPI_SFT) r1[pass][k * 2 + aa] = cf_epi_load4<false>(a.sft_scale, off);
       }
     }
 #pragma unroll
@@ -455,7 +456,6 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
       to_output(pass, o);
     }
     const int nn = n0 + pass * 32 + e_n4 * 4;
-    constexpr bool nvalid = true;
     f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
     if (a.bias) bias4 = *reinterpret_cast<const f32x4*>(a.bias + nn);
     float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f};
@@ -463,16 +463,9 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       f32x4 v = o[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = H2 ? v[e] * acc_s + bias4[e] : v[e] + bias4[e];  // (a power of two: exact)
-      if (a.epilogue == CF_EPI_RESIDUAL) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += r0[pass][i][e];
-      } else if (a.epilogue == CF_EPI_SFT) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = r0[pass][i][e] + a.sft_w * (r0[pass][i][e] * r1[pass][i][e] + v[e]);
-      }
-      *reinterpret_cast<f32x4*>(a.out + offs[pass][i]) = v;
+      v = cf_epi_bias<H2>(v, acc_s, bias4);
+      v = cf_epi_apply(v, a.epilogue, r0[pass][i], r1[pass][i], a.sft_w);
+      cf_epi_store<false>(a.out, offs[pass][i], v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         ssum[e] += v[e];
@@ -480,8 +473,8 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
       }
     }
     if (a.stats_out) {
-      // GroupNorm statistics of the values just written (fp64 partials, fixed shuffle order): one partial per
-      // (image, group, output patch, wave) -- nparts = tiles_per_img * 4
+      // cf_gn_partials<CF_GN_PAIR_IF> (cf_conv_parts.h) written out: one partial per (image, group, output patch, wave) -- nparts =
+      // tiles_per_img * 4.  Called as the helper, the shuffle chain of all four instantiations was scheduled with two more s_nop per pass.
       const int cpg = a.stats_cpg;
       double d0, q0, d1 = 0, q1 = 0;
       if (cpg == 2) {
@@ -507,10 +500,9 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
         d0 += __shfl_xor(d0, o2, 64);
         q0 += __shfl_xor(q0, o2, 64);
       }
-      if ((lane >> 3) == 0 && nvalid && (nn % cpg) == 0) {
+      if ((lane >> 3) == 0 && (nn % cpg) == 0) {
         const size_t pidx = (size_t)rt * 4 + xi;
-        const int ng = a.cout / cpg;
-        double* op = a.stats_out + (((size_t)b * ng + nn / cpg) * a.nparts + pidx) * 2;
+        double* op = cf_gn_partial_ptr(a.stats_out, b, a.cout, cpg, nn, a.nparts, pidx);
         op[0] = d0;
         op[1] = q0;
         if (cpg == 2) {
@@ -634,9 +626,6 @@ extern "C" int cf_pack_conv_weight_winograd(const float* w, int cout, int cin, i
   return CF_OK;
 }
 
-bool cf_wsplit_covers(const cf_conv_desc* d);                                        // cf_wsplit.hip: the eight-wave,
-int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);  // 128-channel split-half form
-
 // Called by cf_conv2d (cf_igemm.hip) for descriptors with winograd != 0; the common argument checks have run there.
 int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {
   CF_REQUIRE(d->taps == 9 && d->stride == 1 && !d->upsample && !d->in_nchw && !d->out_nchw &&
@@ -659,30 +648,13 @@ int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_que
   if (h2 && cf_wsplit_covers(d)) return cf_wsplit_launch(d, stream, parts_query);
   CF_REQUIRE(!h1, "cf_conv2d(winograd, single 16-bit operands): not covered");
   WinoArgs a;
-  a.in0 = d->in0;
-  a.in1 = d->in1;
-  a.c0 = d->c0;
-  a.c1 = d->c1;
-  a.cin = d->c0 + d->c1;
+  cf_fill_conv_args(a, d);
   a.nchunks = a.cin / CF_BK;
-  a.batch = d->batch;
   a.h = d->hout;
   a.w = d->wout;
-  a.cout = d->cout;
   a.cout_pad = d->cout_pad;
-  a.prologue = d->prologue;
-  a.epilogue = d->epilogue;
-  a.pro_scale = d->pro_scale;
-  a.pro_shift = d->pro_shift;
-  a.weight = d->weight;
-  a.bias = d->bias;
-  a.res = d->res;
-  a.sft_scale = d->sft_scale;
-  a.sft_w = d->sft_w;
   a.acc_scale = h2 ? d->acc_scale : 1.f;
   a.act_scale = h2 ? d->act_scale : nullptr;
-  a.out = d->out;
-  a.stats_out = d->stats_out;
   a.stats_cpg = d->stats_cpg > 0 ? d->stats_cpg : 1;
   a.tiles_x = d->wout / WG_TW;
   a.tiles_per_img = a.tiles_x * (d->hout / WG_TH);

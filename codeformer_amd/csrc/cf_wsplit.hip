@@ -32,7 +32,7 @@
 // the patch store (a shift), the epilogue rounds once (RNE) after the GroupNorm partials were taken from the fp32 values.
 #include <type_traits>
 
-#include "cf_common.h"
+#include "cf_conv_parts.h"
 
 // WS_ABLATE: timing-only ablation builds (tools/split_ab.sh); 0 / undefined in every product build.
 // 1 no MFMAs, 2 no MMA stage at all, 4 no transform, 8 no prologue + patch store, 16 no epilogue, 32 no weight fetch
@@ -78,6 +78,7 @@ struct WsArgs {
   int stats_cpg, nparts;
   int tiles_x, tiles_per_img, ntn;
 };
+static_assert(sizeof(WsArgs) == 160, "the kernarg block keeps its size: it feeds the register allocation of every instantiation");
 
 // PRO = the prologue (enum cf_prologue) as a template parameter: with a switch inside the slab loop hipcc's wait-count pass merged the
 // branches into s_waitcnt vmcnt(0) before the patch store, i.e. every iteration waited for the weight fragments it had just requested.
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wsplit_kernel(const WsArgs a) {
         if (PRO == CF_PRO_AFFINE) y = y * sc[e] + sh[e];
         if (PRO == CF_PRO_AFFINE_SWISH) {
           y = y * sc[e] + sh[e];
-          y = y * __builtin_amdgcn_rcpf(1.0f + __expf(-y));  // same hardware exp / rcp swish as the other conv kernels
+          y = cf_swish(y);
         }
         if (PRO == CF_PRO_LEAKY) y = y * (y > 0.f ? act_s : act_s02);
         if (PRO == CF_PRO_NONE) y = y * act_s;
@@ -391,13 +392,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wsplit_kernel(const WsArgs a) {
         const unsigned off = e_base + (unsigned)(k * 4 + aa) * e_rowc + pass * 32;
         offs[pass][k * 2 + aa] = off;
         r0[pass][k * 2 + aa] = r1[pass][k * 2 + aa] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (BIO) {
-          if (a.epilogue == CF_EPI_RESIDUAL || a.epilogue == CF_EPI_SFT) r0[pass][k * 2 + aa] = cf_load4_bf16(a.res, off);
-          if (a.epilogue == CF_EPI_SFT) r1[pass][k * 2 + aa] = cf_load4_bf16(a.sft_scale, off);
-        } else {
-          if (a.epilogue == CF_EPI_RESIDUAL || a.epilogue == CF_EPI_SFT) r0[pass][k * 2 + aa] = *reinterpret_cast<const f32x4*>(a.res + off);
-          if (a.epilogue == CF_EPI_SFT) r1[pass][k * 2 + aa] = *reinterpret_cast<const f32x4*>(a.sft_scale + off);
-        }
+        if (a.epilogue == CF_EPI_RESIDUAL || a.epilogue == CF_EPI_SFT) r0[pass][k * 2 + aa] = cf_epi_load4<BIO>(a.res, off);
+        if (a.epilogue == CF_EPI_SFT) r1[pass][k * 2 + aa] = cf_epi_load4<BIO>(a.sft_scale, off);
       }
     }
 #pragma unroll
@@ -412,45 +408,19 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wsplit_kernel(const WsArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       f32x4 v = o[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = v[e] * acc_s + bias4[e];  // (a power of two: exact)
-      if (a.epilogue == CF_EPI_RESIDUAL) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += r0[pass][i][e];
-      } else if (a.epilogue == CF_EPI_SFT) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = r0[pass][i][e] + a.sft_w * (r0[pass][i][e] * r1[pass][i][e] + v[e]);
-      }
-      if constexpr (BIO) cf_store4_bf16(a.out, offs[pass][i], v);   // (rounded here, once; the statistics below see the fp32 values)
-      else *reinterpret_cast<f32x4*>(a.out + offs[pass][i]) = v;
+      v = cf_epi_bias<true>(v, acc_s, bias4);
+      v = cf_epi_apply(v, a.epilogue, r0[pass][i], r1[pass][i], a.sft_w);
+      cf_epi_store<BIO>(a.out, offs[pass][i], v);   // (bf16 tensors: rounded here, once; the statistics see the fp32 values)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         ssum[e] += v[e];
         ssq[e] += v[e] * v[e];
       }
     }
-    if (a.stats_out) {
-      // GroupNorm statistics of the values just written (fp64 partials, fixed shuffle order): one partial per
-      // (image, group, output patch, xi wave) -- nparts = tiles_per_img * 4, as the four-wave kernel writes them
-      const int cpg = a.stats_cpg;  // >= 4 here (cout >= 128)
-      double d0 = ((double)ssum[0] + ssum[1]) + ((double)ssum[2] + ssum[3]);
-      double q0 = ((double)ssq[0] + ssq[1]) + ((double)ssq[2] + ssq[3]);
-      for (int o2 = 8; o2 < 64; o2 <<= 1) {  // the (tile, bb) items of this wave: lanes with the same channel quad
-        d0 += __shfl_xor(d0, o2, 64);
-        q0 += __shfl_xor(q0, o2, 64);
-      }
-      for (int o2 = 1; o2 * 4 < cpg; o2 <<= 1) {  // adjacent channel quads of one group (cpg >= 8)
-        d0 += __shfl_xor(d0, o2, 64);
-        q0 += __shfl_xor(q0, o2, 64);
-      }
-      if ((lane >> 3) == 0 && (nn % cpg) == 0) {
-        const size_t pidx = (size_t)rt * 4 + xi;
-        const int ng = a.cout / cpg;
-        double* op = a.stats_out + (((size_t)b * ng + nn / cpg) * a.nparts + pidx) * 2;
-        op[0] = d0;
-        op[1] = q0;
-      }
-    }
+    // one partial per (image, group, output patch, xi wave) -- nparts = tiles_per_img * 4, as the four-wave kernel writes them; the (tile,
+    // bb) items of a wave are the lanes with the same channel quad (8 quads per row); cpg >= 4 here (cout >= 128)
+    if (a.stats_out)
+      cf_gn_partials<CF_GN_QUAD>(ssum, ssq, a.stats_out, a.stats_cpg, 8, (lane >> 3) == 0, (size_t)rt * 4 + xi, a.nparts, a.cout, nn, b);
   }
 }
 
@@ -465,29 +435,12 @@ bool cf_wsplit_covers(const cf_conv_desc* d) {
 
 int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {
   WsArgs a;
-  a.in0 = d->in0;
-  a.in1 = d->in1;
-  a.c0 = d->c0;
-  a.c1 = d->c1;
-  a.cin = d->c0 + d->c1;
+  cf_fill_conv_args(a, d);
   a.nchunks = a.cin / CF_BK;
-  a.batch = d->batch;
   a.h = d->hout;
   a.w = d->wout;
-  a.cout = d->cout;
-  a.prologue = d->prologue;
-  a.epilogue = d->epilogue;
-  a.pro_scale = d->pro_scale;
-  a.pro_shift = d->pro_shift;
-  a.weight = d->weight;
-  a.bias = d->bias;
-  a.res = d->res;
-  a.sft_scale = d->sft_scale;
-  a.sft_w = d->sft_w;
   a.acc_scale = d->acc_scale;
   a.act_scale = d->act_scale;
-  a.out = d->out;
-  a.stats_out = d->stats_out;
   a.stats_cpg = d->stats_cpg > 0 ? d->stats_cpg : 4;
   a.tiles_x = d->wout / WS_TW;
   a.tiles_per_img = a.tiles_x * (d->hout / WS_TH);
@@ -498,32 +451,18 @@ int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query
     return CF_OK;
   }
   constexpr size_t lds = WS_LDS_FLOATS * sizeof(float);
-  // (cf_device_init sets the dynamic-LDS attribute of the twelve instantiations on each device)
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_NONE>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_AFFINE>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_AFFINE_SWISH>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_LEAKY>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_NONE, CF_OPERAND_F16>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_AFFINE, CF_OPERAND_F16>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_AFFINE_SWISH, CF_OPERAND_F16>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_LEAKY, CF_OPERAND_F16>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_NONE, CF_OPERAND_BF16>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_AFFINE, CF_OPERAND_BF16>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_AFFINE_SWISH, CF_OPERAND_BF16>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_LEAKY, CF_OPERAND_BF16>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_NONE, CF_OPERAND_BF16, true>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_AFFINE, CF_OPERAND_BF16, true>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_AFFINE_SWISH, CF_OPERAND_BF16, true>), lds);
-  CF_LDS_ATTR((wsplit_kernel<CF_PRO_LEAKY, CF_OPERAND_BF16, true>), lds);
   const dim3 grid(a.tiles_per_img * d->batch * a.ntn), block(WS_THREADS);
   auto launch_op = [&](auto op, auto bio) {
-    constexpr int OP = decltype(op)::value;
-    constexpr bool BIO = decltype(bio)::value;
+    auto go = [&](auto pro) {  // (registered where it is launched: cf_device_init sets the dynamic-LDS attribute of every instantiation on each device)
+      constexpr auto kern = wsplit_kernel<decltype(pro)::value, decltype(op)::value, decltype(bio)::value>;
+      CF_LDS_ATTR(kern, lds);
+      hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
+    };
     switch (d->prologue) {
-      case CF_PRO_AFFINE: hipLaunchKernelGGL((wsplit_kernel<CF_PRO_AFFINE, OP, BIO>), grid, block, lds, stream, a); break;
-      case CF_PRO_AFFINE_SWISH: hipLaunchKernelGGL((wsplit_kernel<CF_PRO_AFFINE_SWISH, OP, BIO>), grid, block, lds, stream, a); break;
-      case CF_PRO_LEAKY: hipLaunchKernelGGL((wsplit_kernel<CF_PRO_LEAKY, OP, BIO>), grid, block, lds, stream, a); break;
-      default: hipLaunchKernelGGL((wsplit_kernel<CF_PRO_NONE, OP, BIO>), grid, block, lds, stream, a); break;
+      case CF_PRO_AFFINE: go(std::integral_constant<int, CF_PRO_AFFINE>{}); break;
+      case CF_PRO_AFFINE_SWISH: go(std::integral_constant<int, CF_PRO_AFFINE_SWISH>{}); break;
+      case CF_PRO_LEAKY: go(std::integral_constant<int, CF_PRO_LEAKY>{}); break;
+      default: go(std::integral_constant<int, CF_PRO_NONE>{}); break;
     }
   };
   CF_REQUIRE(!d->io_bf16 || d->bf16_mfma == CF_OPERAND_BF16, "cf_conv2d(winograd, 8 waves): bf16 tensors (io_bf16) go with CF_OPERAND_BF16 operands");

@@ -5,10 +5,12 @@ A small, purpose-built preprocessor: for a fixed set of experiment macros with t
   * resolves every `#if` / `#else` / `#endif` whose condition mentions only those macros and integer arithmetic, keeping the live branch,
   * deletes the `F4_T(n);` stamp statements, and substitutes the remaining uses of a macro inside ordinary code with its value.
 Everything else (other `#if`s, comments, layout) is left byte for byte.  The default build must be instruction-identical before and after:
-tools/strip_experiment_macros.py --verify compiles both trees' device code to assembly and compares it kernel by kernel.
+tools/strip_experiment_macros.py --verify compiles both trees' device code to assembly and compares it kernel by kernel (it serves any
+later refactor of these files too: a function that is not instruction-identical passes only with the same opcode histogram, registers,
+LDS and scratch as before).
 The reverse patch (tools/experiments/ablation_and_timing_macros.patch) restores the scaffolds for an experiment build.
 
-usage: python tools/strip_experiment_macros.py [--check | --write | --verify OLD_TREE]
+usage: python tools/strip_experiment_macros.py [--check | --write | --verify OLD_CSRC_DIR [FILE.hip ...]]
 """
 import os
 import re
@@ -124,39 +126,66 @@ def asm(path, outdir):
     return '\n'.join(keep)
 
 
+def functions(txt):
+    """kernel name -> its instruction lines (labels, directives and the per-compilation __hip_cuid symbol aside)"""
+    out, cur = {}, None
+    for l in txt.split('\n'):
+        m = re.match(r'^(_Z\w+):', l)
+        if m:
+            cur = m.group(1)
+            out[cur] = []
+        elif cur is not None:
+            if l.startswith('.Lfunc_end'):
+                cur = None
+            elif '__hip_cuid' not in l:
+                l = re.sub(r'\.LBB\d+_', '.LBB_', l.split(';')[0]).rstrip()    # (basic-block labels carry the function's index in the file; comments too)
+                if l:
+                    out[cur].append(l)
+    return out
+
+
+RESOURCES = ('next_free_vgpr', 'next_free_sgpr', 'accum_offset', 'group_segment_fixed_size', 'private_segment_fixed_size')
+
+
+def resources(txt):
+    """kernel name -> the register / LDS / scratch figures of its .amdhsa_kernel block"""
+    out = {}
+    for m in re.finditer(r'\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel', txt, re.S):
+        out[m.group(1)] = tuple(re.search(r'\.amdhsa_' + k + r'\s+(\S+)', m.group(2)).group(1) for k in RESOURCES)
+    return out
+
+
+def same_mix(fa, fb):
+    """the second-best verdict on a function whose text changed: the same count of every opcode (scheduling and register numbers aside)"""
+    from collections import Counter
+    hist = lambda f: Counter(l.split()[0] for l in f if not l.endswith(':') and not l.lstrip().startswith('.'))
+    return hist(fa) == hist(fb)
+
+
+def verify(old, files):
+    """Compare the device code of tree `old` with this tree's, function by function.  Every function must be instruction-identical, or have
+    the same opcode histogram AND the same registers, accumulator offset, LDS and scratch as before (a helper that moved into a header may
+    change where scalar instructions sit, not what is executed)."""
+    ok = True
+    for f in files:
+        ta, tb = asm(os.path.join(old, f), '/tmp/strip_old'), asm(os.path.join(CSRC, f), '/tmp/strip_new')
+        a, b, ra, rb = functions(ta), functions(tb), resources(ta), resources(tb)
+        gone, added = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+        diff = [k for k in b if a.get(k) != b[k]]
+        mix = [k for k in diff if k in a and same_mix(a[k], b[k]) and ra.get(k) == rb.get(k)]
+        bad = [k for k in diff if k not in mix]
+        ok &= not bad
+        print(f'{f}: {len(b)} device functions, {len(b) - len(diff)} instruction-identical to the old tree'
+              + (f', {len(mix)} with the same opcode histogram, registers, LDS and scratch' if mix else '')
+              + (f', {len(gone)} no longer instantiated' if gone else '') + (f', {len(added)} new' if added else '')
+              + (f'; DIFFER: {bad[:3]}' if bad else ''))
+    return ok
+
+
 def main():
     mode = sys.argv[1] if len(sys.argv) > 1 else '--check'
     if mode == '--verify':
-        old = sys.argv[2]
-        ok = True
-
-        def functions(txt):
-            """kernel name -> its instruction lines (labels, directives and the per-compilation __hip_cuid symbol aside)"""
-            out, cur = {}, None
-            for l in txt.split('\n'):
-                m = re.match(r'^(_Z\w+):', l)
-                if m:
-                    cur = m.group(1)
-                    out[cur] = []
-                elif cur is not None:
-                    if l.startswith('.Lfunc_end'):
-                        cur = None
-                    elif '__hip_cuid' not in l:
-                        l = re.sub(r'\.LBB\d+_', '.LBB_', l.split(';')[0]).rstrip()    # (basic-block labels carry the function's index in the file; comments too)
-                        if l:
-                            out[cur].append(l)
-            return out
-        for f in FILES:
-            ta, tb = asm(os.path.join(old, f), '/tmp/strip_old'), asm(os.path.join(CSRC, f), '/tmp/strip_new')
-            # (the F(4,3) kernel lost its last template parameter with the overlapped form: <..., F32, OVL = false> is now <..., F32>)
-            ta = re.sub(r'(wf43_kernelILi\d+ELi\d+ELi\d+ELi\d+ELb[01]E)Lb0E(EEvNS_6F4ArgsE)', r'\1\2', ta)
-            a, b = functions(ta), functions(tb)
-            gone = sorted(set(a) - set(b))
-            diff = [k for k in b if a.get(k) != b[k]]
-            ok &= not diff
-            print(f'{f}: {len(b)} device functions, {len(b) - len(diff)} instruction-identical to the tree with the scaffolds'
-                  + (f', {len(gone)} no longer instantiated' if gone else '') + (f'; DIFFER: {diff[:3]}' if diff else ''))
-        sys.exit(0 if ok else 1)
+        sys.exit(0 if verify(sys.argv[2], sys.argv[3:] or FILES) else 1)
     for f in FILES:
         p = os.path.join(CSRC, f)
         src = open(p).read()
