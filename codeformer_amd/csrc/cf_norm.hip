@@ -6,8 +6,12 @@ namespace {
 
 // ---- GroupNorm stage 1 --------------------------------------------------------------------------
 // x: [batch][hw][C] fp32.  grid (nblk, batch), 256 threads.  Thread t owns channel quad t % (C/4) and
-// walks pixel rows  row0 + t/(C/4), += 1024/C.  Sums are carried in fp64 (the pass is HBM-bound; the fp64
-// adds hide under the loads) so the later mean / E[x^2]-mean^2 is accurate for any |mean|/std.
+// walks pixel rows  row0 + t/(C/4), += 1024/C.  Sums are carried in fp64 from the load on, the squares included (the pass is
+// HBM-bound; the fp64 adds hide under the loads), so the later mean / E[x^2]-mean^2 of THIS pass is accurate for any |mean|/std
+// an fp32 tensor can hold: only the fp32 roundings of the finalize remain.  That is a property of the stand-alone pass alone.  The
+// statistics the network normally uses are the convolution epilogues' (cf_conv_parts.h: n_t = 4..16 fp32 additions of v and v*v
+// per accumulator before the fp64 partials); their rstd is good to (3 n_t + 1) 2^-25 (1 + (mean/std)^2) std^2 / (std^2 + eps) --
+// DESIGN.md, "Accuracy envelope of the GroupNorm statistics".
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, int hw, int C, int cpg,
                                                        int rows_per_blk, double* __restrict__ part, int nblk) {
   __shared__ double red[256][4];
