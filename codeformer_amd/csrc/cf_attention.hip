@@ -264,6 +264,8 @@ extern "C" int cf_attention(const float* q, int ldq, const float* k, int ldk, co
   CF_REQUIRE(nkeys == NKEY, "cf_attention: built for %d keys (got %d)", NKEY, nkeys);
   CF_REQUIRE(batch > 0 && heads > 0 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo >= heads * head_dim,
              "cf_attention: bad dims");
+  CF_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) % 16 == 0,
+             "cf_attention: q, k, v and out must be 16-byte aligned (both kernels read float4)");
   const dim3 grid(NKEY / BQ, heads, batch), block(256);
   if (head_dim == 64) {
     CF_LDS_ATTR(attn64_kernel, A6_LDS_BYTES);  // (cf_device_init sets the dynamic-LDS attribute on each device)

@@ -320,7 +320,9 @@ int cf_layernorm(const float* x, int rows, int c, const float* gamma, const floa
 /* ---- attention over 256 keys (vqgan_arch.py:207-221 AttnBlock bmm/softmax/bmm, and the
  *      nn.MultiheadAttention core called at codeformer_arch.py:126) --------------------------------
  * q,k,v: row (b*256 + i), columns [h*head_dim, (h+1)*head_dim) of matrices with leading dimensions
- * ldq/ldk/ldv; out likewise with ldo.  softmax over keys of (q.k^T * scale).  head_dim in {64, 512}. */
+ * ldq/ldk/ldv; out likewise with ldo.  softmax over keys of (q.k^T * scale).  head_dim in {64, 512}.
+ * q, k, v and out must be 16-byte aligned and ldq/ldk/ldv multiples of 4 (the kernels read float4); ldo >= heads*head_dim
+ * (columns past heads*head_dim of an out row are not written).  Anything else is CF_ERR_ARG before any launch. */
 int cf_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out, int ldo,
                  int batch, int heads, int head_dim, int nkeys, float scale, cf_stream_t stream);
 

@@ -63,6 +63,8 @@ def test_argument_errors_are_reported_without_a_gpu(native):
     assert 'taps' in lib.last_error()
     assert native.cf_attention(1, 512, 1, 512, 1, 512, 1, 512, 1, 8, 64, 128, 1.0, None) == -1
     assert '256 keys' in lib.last_error()
+    for args in ((4, 512, 16, 512, 16, 512, 16, 512), (16, 512, 24, 512, 16, 512, 16, 512), (16, 512, 16, 512, 16, 512, 20, 512)):   # float4 loads
+        assert native.cf_attention(*args, 1, 8, 64, 256, 0.125, None) == -1 and 'aligned' in lib.last_error()
     assert native.cf_packed_weight_elems(64, 9, 128) == 9 * 64 * 128
     # split-half operands (CF_OPERAND_F16X2): shape rules and the pack-time scale are checked before any launch
     d = lib.ConvDesc(in0=1, weight=1, out=1, taps=9, stride=1, batch=1, hin=16, win=16, hout=16, wout=16, c0=48, cout=64,
