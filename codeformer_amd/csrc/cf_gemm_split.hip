@@ -585,7 +585,12 @@ extern "C" int cf_pack_linear_weight_f16x2(const float* w, int n, int k, float s
 // Called by cf_conv2d (cf_igemm.hip) for taps == 1 descriptors with bf16_mfma == CF_OPERAND_F16X2; the common argument checks have run.
 int cf_gemm_split_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_part) {
   const long m = (long)d->batch * d->hout * d->wout;
-  // (the weight packing fixes N % 64 == 0 for every form; the in-workgroup split -- 32 x 32 tiles -- takes M % 32 == 0, the others M % 64 == 0)
+  // The M rules per kernel, in one place (N % 64 == 0 and K % 128 == 0 for every form: the weight packing):
+  //   gemm_split_chunk_kernel<1, 1>  split_k == CF_SPLITK_IN_WORKGROUP: M % 32 == 0 (32 x 32 tiles), K <= 1024
+  //   gemm_split_tile_kernel<1>      split_k <= 1 and M % 128 == 0 (128-token tiles)
+  //   gemm_split_kernel              M % 64 == 0: split_k >= 2 (workspace + counters), or split_k <= 1 where M % 128 != 0 (no workspace)
+  //   gemm_f32_tile_kernel           (fp32 operands, cf_gemm_f32_tile_try) split_k == 1 and M % 128 == 0; else the 64 x 64 split-K instantiation of
+  //                                  cf_igemm.hip, which needs the rows of ONE image % 64 == 0
   const int mq = d->split_k == CF_SPLITK_IN_WORKGROUP ? 32 : 64;
   CF_REQUIRE(d->taps == 1 && m % mq == 0 && d->cout % 64 == 0 && d->cout_pad == d->cout && (d->c0 + d->c1) % 128 == 0,
              "cf_conv2d(1x1, f16x2): M %ld must be a multiple of %d, N %d of 64, K %d of 128", m, mq, d->cout, d->c0 + d->c1);

@@ -331,6 +331,14 @@ def exact_code(code):
     return {SPLIT: WINOGRAD, SPLIT_F43: WINOGRAD, 2: WINOGRAD}.get(code, code)
 
 
+def pack_scale(wmax):
+    """The power of two a split-half packing multiplies its weights by: max|w * scale| lands in [2^14, 2^15), the top binade of IEEE half
+    below its largest finite value, so the lo halves of the largest weights are normal numbers.  ONE scale per matrix: a weight of less
+    than 2^-3 / scale (2^-17 .. 2^-18 of the largest) has a subnormal lo half, one below 2^-14 / scale a subnormal hi half.  1.0 for an
+    all-zero or non-finite matrix."""
+    return 1.0 if wmax == 0.0 or not math.isfinite(wmax) else 2.0 ** (14 - math.frexp(wmax)[1] + 1)
+
+
 def pack_weight(weight, bias=None, bf16=False, up2x=False, f16=False, stride2=False):
     """weight: (cout, cin, 3, 3) | (cout, cin, 1, 1) | (cout, cin) CUDA fp32 -> PackedWeight.
     bf16=True (3x3 only, cin % 32 == 0): bf16 operands for the v_mfma_f32_32x32x16_bf16 path of cf_conv2d.
@@ -353,8 +361,7 @@ def pack_weight(weight, bias=None, bf16=False, up2x=False, f16=False, stride2=Fa
         w2 = w.reshape(cout, cin)
         if w.dim() not in (2, 4) or w.numel() != cout * cin or cout % 64 or cin % 128:
             raise ValueError('f16x2 GEMM packing needs a Linear / 1x1 weight with cout % 64 == 0 and cin % 128 == 0')
-        wmax = float(w2.abs().max())
-        scale = 1.0 if wmax == 0.0 or not math.isfinite(wmax) else 2.0 ** (14 - math.frexp(wmax)[1] + 1)
+        scale = pack_scale(float(w2.abs().max()))
         packed = torch.empty(cout * cin, dtype=torch.float32, device=w.device)
         L.check(lib.cf_pack_linear_weight_f16x2(L.ptr(w2.contiguous()), cout, cin, scale, L.ptr(packed, dtype=None), L.stream_ptr()),
                 'cf_pack_linear_weight_f16x2')
@@ -657,7 +664,14 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
 
 def linear(x, pw, *, epilogue=EPI_NONE, res=None, x_alt=None, alt_from=0):
     """x: (M, K) -> (M, N) through the 1x1 path of the same kernel (M must be a multiple of 256).
-    x_alt / alt_from: see conv2d (columns >= alt_from are x_alt @ W^T: two Linear layers, two inputs, one launch)."""
+    x_alt / alt_from: see conv2d (columns >= alt_from are x_alt @ W^T: two Linear layers, two inputs, one launch).
+    M % 256 is THIS function's rule (it presents the rows as 16x16 token images, the unit splitk_for decides by).  The kernels behind
+    conv2d(split_k=...) take less (K % 128 == 0 and N % 64 == 0 for all of them):
+      fp32 weight    split_k 1, M % 128 == 0, N == cout_pad, not 512 -> 512: gemm_f32_tile_kernel; otherwise the 64x64 split-K instantiation
+                     of igemm_kernel (rows per image % 64 == 0; split_k any divisor of K / 128)
+      GSPLIT weight  split_k 1, M % 128 == 0: gemm_split_tile_kernel; split_k 1 otherwise or split_k >= 2 (a divisor of K / 128): gemm_split_kernel
+                     (M % 64 == 0); split_k SPLITK_IN_WORKGROUP: gemm_split_chunk_kernel (M % 32 == 0, K <= 1024)
+    All of one operand scheme return the same bits (tests/test_gpu_token_gemm.py)."""
     M, K = x.shape
     if M % 256:
         raise ValueError(f'linear: rows {M} must be a multiple of 256')

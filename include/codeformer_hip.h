@@ -242,8 +242,17 @@ int cf_pack_conv_weight_winograd43(const float* w, int cout, int cin, int cout_p
 int cf_pack_conv_weight_winograd_bf16(const float* w, int cout, int cin, int cout_pad, int cin_pad, float scale, void* packed,
                                       cf_stream_t stream);
 /* taps == 1 + CF_OPERAND_F16X2 (Linear / 1x1 on token matrices, codeformer_arch.py:104-106,126,132,183,192): w[n][k] -> scale * w as
- * hi + lo IEEE halves in MFMA-operand order (n*k 32-bit words); n % 64 == 0, k % 128 == 0.  The launch needs M = batch*hout*wout % 64 == 0,
- * a dense single input, no prologue / statistics, epilogue none | GELU | residual; split_k as for the fp32 GEMM (same bits for every count) */
+ * hi + lo IEEE halves in MFMA-operand order (n*k 32-bit words); n % 64 == 0, k % 128 == 0.  The launch needs M = batch*hout*wout % 64 == 0
+ * (split_k == CF_SPLITK_IN_WORKGROUP: M % 32 == 0 and k <= 1024), a dense single input and a dense output (ld_out 0 or cout), no prologue /
+ * statistics, epilogue none | GELU | residual; split_k any divisor of k / 128 (same bits for every count, as for the fp32 GEMM).
+ * Operand range the split-half token GEMM is accurate on (derived in tools/gemm_check.py, tested by tests/test_gpu_token_gemm.py):
+ *   weights: ONE power-of-two scale per matrix puts max|scale * w| into [2^14, 2^15).  A weight carries 22 bits while |scale * w| >= 2^-3,
+ *     i.e. down to 2^-17 .. 2^-18 of the largest weight of the matrix; below that its lo half is a subnormal half and the weight carries an
+ *     ABSOLUTE error of up to 2^-25 / scale (below 2^-14 / scale the hi half is subnormal too; below 2^-25 / scale the weight is zero).
+ *   tokens: split in registers with NO scale.  22 bits for 2^-3 <= |a| <= 65504; below 2^-3 an absolute error of up to 2^-25 per element;
+ *     beyond 65504 the hi half is infinite and the outputs of that row are non-finite, never wrong finite values.
+ *   per output element: |error| <= (396 + k / 128) 2^-24 sum|a w| + 2^-25 (sum|a| / scale + sum|w|) before bias and epilogue.  The host keeps
+ *   a layer whose inputs may leave the token range on fp32 operands (bounded_code, codeformer_arch.py). */
 int cf_pack_linear_weight_f16x2(const float* w, int n, int k, float scale, void* packed, cf_stream_t stream);
 /* bf16 layout [tap][cin_pad/32][cout_pad][32] (round-to-nearest-even); cin_pad % 32 == 0, cout_pad % 64 == 0; the buffer
  * holds cf_packed_weight_elems(cin_pad, taps, cout_pad) bf16 values (half the bytes of the fp32 packing). */
