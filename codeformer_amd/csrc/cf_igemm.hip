@@ -1072,41 +1072,33 @@ __global__ __launch_bounds__(256) void conv3x3_few_cin_kernel(const ConvArgsExt 
   }
 }
 
+// 1x1 / Linear rows in tiles of `bm`: whole tiles, none across two images.  The tile count, or 0 with the error set.
+int conv1x1_mtiles(const ConvArgsExt& a, int bm) {
+  const long m = (long)a.batch * a.hout * a.wout;
+  if (m % bm == 0 && (a.hout * a.wout) % bm == 0) return (int)(m / bm);
+  cf_set_error("cf_conv2d: 1x1 rows %ld (per image %d) not divisible by %d", m, a.hout * a.wout, bm);
+  return 0;
+}
+
 template <int TAPS, int STRIDE, int WM, int WN, int MI, int NI, bool IN_NCHW, bool BF16 = false, bool EXT = false, bool F16 = false, bool BIO = false>
 int launch(const ConvArgsExt& a, hipStream_t stream, int* parts_query) {
   using C = Cfg<TAPS, STRIDE, WM, WN, MI, NI>;
   ArgsOf<EXT> k = a;  // (slices the stride fields off for the CodeFormer instantiations)
   int mtiles;
-  if (EXT) {  // any image size: ceil-divided tile grid (on the SOURCE grid for the folded upsample), edge tiles masked
+  if (TAPS == 1) {
+    k.tiles_x = k.tiles_per_img = 0;
+    mtiles = conv1x1_mtiles(a, C::BM);
+    if (!mtiles) return CF_ERR_ARG;
+  } else {  // the folded upsample's tiles live on the SOURCE grid; each is computed once per output parity class
     const int gh = TAPS == 4 ? a.hin : a.hout, gw = TAPS == 4 ? a.win : a.wout;
+    if (!EXT && (gh % C::TH != 0 || gw % C::TW != 0)) {  // (EXT: any image size, the grid is ceil-divided and edge tiles are masked)
+      cf_set_error(TAPS == 4 ? "cf_conv2d: %dx%d upsample source not divisible by the %dx%d tile"
+                             : "cf_conv2d: %dx%d output not divisible by the %dx%d tile", gh, gw, C::TH, C::TW);
+      return CF_ERR_ARG;
+    }
     k.tiles_x = (gw + C::TW - 1) / C::TW;
     k.tiles_per_img = (TAPS == 4 ? 4 : 1) * k.tiles_x * ((gh + C::TH - 1) / C::TH);
     mtiles = k.tiles_per_img * a.batch;
-  } else if (TAPS == 4) {  // tiles live on the SOURCE grid; each is computed once per output parity class
-    if (a.hin % C::TH != 0 || a.win % C::TW != 0) {
-      cf_set_error("cf_conv2d: %dx%d upsample source not divisible by the %dx%d tile", a.hin, a.win, C::TH, C::TW);
-      return CF_ERR_ARG;
-    }
-    k.tiles_x = a.win / C::TW;
-    k.tiles_per_img = 4 * k.tiles_x * (a.hin / C::TH);
-    mtiles = k.tiles_per_img * a.batch;
-  } else if (TAPS == 9) {
-    if (a.hout % C::TH != 0 || a.wout % C::TW != 0) {
-      cf_set_error("cf_conv2d: %dx%d output not divisible by the %dx%d tile", a.hout, a.wout, C::TH, C::TW);
-      return CF_ERR_ARG;
-    }
-    k.tiles_x = a.wout / C::TW;
-    k.tiles_per_img = k.tiles_x * (a.hout / C::TH);
-    mtiles = k.tiles_per_img * a.batch;
-  } else {
-    const long m = (long)a.batch * a.hout * a.wout;
-    if (m % C::BM != 0 || (a.hout * a.wout) % C::BM != 0) {
-      cf_set_error("cf_conv2d: 1x1 rows %ld (per image %d) not divisible by %d", m, a.hout * a.wout, C::BM);
-      return CF_ERR_ARG;
-    }
-    k.tiles_x = 0;
-    k.tiles_per_img = 0;
-    mtiles = (int)(m / C::BM);
   }
   k.nparts = (mtiles / a.batch) * WM;  // statistics partials per (image, group): tiles per image x wave rows
   if (parts_query) {
@@ -1128,12 +1120,8 @@ int launch_sk(const ConvArgsExt& a, float* ws, unsigned* counters, int nsplit, h
   using C = Cfg<1, 1, WM, WN, MI, NI>;
   ConvArgsSK k;
   static_cast<ConvArgs&>(k) = a;
-  const long m = (long)a.batch * a.hout * a.wout;
-  if (m % C::BM != 0 || (a.hout * a.wout) % C::BM != 0) {
-    cf_set_error("cf_conv2d: 1x1 rows %ld (per image %d) not divisible by %d", m, a.hout * a.wout, C::BM);
-    return CF_ERR_ARG;
-  }
-  const int mtiles = (int)(m / C::BM);
+  const int mtiles = conv1x1_mtiles(a, C::BM);
+  if (!mtiles) return CF_ERR_ARG;
   k.tiles_x = k.tiles_per_img = 0;
   k.nparts = (mtiles / a.batch) * WM;
   if (parts_query) {
@@ -1248,16 +1236,23 @@ extern "C" int cf_pack_conv_weight_up2x_f16(const float* w, int cout, int cin, i
   return pack_bf16(w, cout, cin, 1, cout_pad, cin_pad, packed, stream, 1);
 }
 
+// fp32 layout [slab][cin_pad/16][cout_pad][16]: the plain taps, or (fold) the 16 folded slabs of the nearest-x2 + 3x3 convolution
+static int pack_f32(const char* name, const float* w, int cout, int cin, int taps, int fold, int cout_pad, int cin_pad, float* packed,
+                    cf_stream_t stream) {
+  CF_REQUIRE(w && packed, "%s: null pointer", name);
+  CF_REQUIRE(taps == 1 || taps == 9, "%s: taps must be 1 or 9 (got %d)", name, taps);
+  CF_REQUIRE(cin_pad % CF_BK == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % 32 == 0,
+             "%s: bad padding cin %d->%d cout %d->%d", name, cin, cin_pad, cout, cout_pad);
+  const long total = (long)(fold ? 16 : taps) * cin_pad * cout_pad;
+  hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
+                     taps, fold, cout_pad, cin_pad / CF_BK, packed, total);
+  CF_CHECK_LAUNCH(name);
+  return CF_OK;
+}
+
 extern "C" int cf_pack_conv_weight_up2x(const float* w, int cout, int cin, int cout_pad, int cin_pad, float* packed,
                                         cf_stream_t stream) {
-  CF_REQUIRE(w && packed, "cf_pack_conv_weight_up2x: null pointer");
-  CF_REQUIRE(cin_pad % CF_BK == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % 32 == 0,
-             "cf_pack_conv_weight_up2x: bad padding cin %d->%d cout %d->%d", cin, cin_pad, cout, cout_pad);
-  const long total = 16L * cin_pad * cout_pad;
-  hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
-                     9, 1, cout_pad, cin_pad / CF_BK, packed, total);
-  CF_CHECK_LAUNCH("cf_pack_conv_weight_up2x");
-  return CF_OK;
+  return pack_f32("cf_pack_conv_weight_up2x", w, cout, cin, 9, 1, cout_pad, cin_pad, packed, stream);
 }
 
 extern "C" int64_t cf_packed_weight_elems(int cin_pad, int taps, int cout_pad) {
@@ -1266,19 +1261,14 @@ extern "C" int64_t cf_packed_weight_elems(int cin_pad, int taps, int cout_pad) {
 
 extern "C" int cf_pack_conv_weight(const float* w, int cout, int cin, int taps, int cout_pad, int cin_pad,
                                    float* packed, cf_stream_t stream) {
-  CF_REQUIRE(w && packed, "cf_pack_conv_weight: null pointer");
-  CF_REQUIRE(taps == 1 || taps == 9, "cf_pack_conv_weight: taps must be 1 or 9 (got %d)", taps);
-  CF_REQUIRE(cin_pad % CF_BK == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % 32 == 0,
-             "cf_pack_conv_weight: bad padding cin %d->%d cout %d->%d", cin, cin_pad, cout, cout_pad);
-  const long total = (long)taps * cin_pad * cout_pad;
-  const int blocks = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, cout, cin, taps, 0,
-                     cout_pad, cin_pad / CF_BK, packed, total);
-  CF_CHECK_LAUNCH("cf_pack_conv_weight");
-  return CF_OK;
+  return pack_f32("cf_pack_conv_weight", w, cout, cin, taps, 0, cout_pad, cin_pad, packed, stream);
 }
 
-static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
+// What conv_validate derives for the pieces below (ext: the general instantiations, narrow: 64-wide N tiles of a small-M layer).
+struct ConvFacts { int ld0, ld1, ldo; bool ext, few_cout, narrow; };
+
+// Every argument check of cf_conv2d; the first failing one decides the error text.  The direct kernels' own come last, each under its route.
+static int conv_validate(const cf_conv_desc* d, const int* pq, ConvFacts& f) {
   CF_REQUIRE(d, "cf_conv2d: null descriptor");
   CF_REQUIRE(pq || (d->in0 && d->weight && d->out), "cf_conv2d: null in0/weight/out");
   CF_REQUIRE(d->taps == 1 || d->taps == 9, "cf_conv2d: taps must be 1 or 9 (got %d)", d->taps);
@@ -1351,7 +1341,6 @@ static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
   CF_REQUIRE(!(d->out_nchw && (d->taps != 9 || d->epilogue != CF_EPI_NONE)), "cf_conv2d: out_nchw needs 3x3, no epilogue");
   CF_REQUIRE(d->cout_pad >= d->cout && d->cout_pad % 32 == 0, "cf_conv2d: cout_pad %d invalid for cout %d", d->cout_pad,
              d->cout);
-
   CF_REQUIRE(!d->in0_alt || (d->taps == 1 && d->bf16_mfma == CF_OPERAND_F16X2 && (long)d->hout * d->wout <= CF_TOKEN_IMAGE_MAX && !d->io_bf16),
              "cf_conv2d: in0_alt (a second token matrix for the columns >= alt_cout0) belongs to the split-half token GEMM");
   if (d->io_bf16) {   // bf16 tensors (ABI v22): exactly the launches the bf16 mode makes from 64x64 pixels up; anything else is refused, never reinterpreted
@@ -1377,19 +1366,26 @@ static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
                "cf_conv2d: act_scale is applied by the Winograd / split-half convolution kernels only (operand %d, winograd %d, taps %d)",
                d->bf16_mfma, d->winograd, d->taps);
   }
-  if (d->taps == 1 && d->bf16_mfma == CF_OPERAND_F16X2) {
-    CF_REQUIRE(!pq, "cf_conv2d(1x1, f16x2): no statistics epilogue");
-    // images of more than CF_TOKEN_IMAGE_MAX pixels: the streaming 1x1 form of the split-half convolution kernel (weight: form 3 of
-    // cf_pack_conv_weight_f16x2); token matrices (the Transformer's 16x16 "images"): the token GEMM (cf_pack_linear_weight_f16x2)
-    if ((long)d->hout * d->wout > CF_TOKEN_IMAGE_MAX) return cf_split_launch(d, stream, pq);
-    return cf_gemm_split_launch(d, stream);
+  if (d->taps == 1 && d->bf16_mfma == CF_OPERAND_F16X2) CF_REQUIRE(!pq, "cf_conv2d(1x1, f16x2): no statistics epilogue");
+  else CF_REQUIRE(d->winograd >= 0 && d->winograd <= 2, "cf_conv2d: winograd must be 0, 1 (F(2x2,3x3)) or 2 (F(4x4,3x3)), got %d", d->winograd);
+  const bool direct = !d->winograd && d->bf16_mfma != CF_OPERAND_F16X2;  // the kernels of this file (ext implies it)
+  const int cp = d->cout_pad;
+  CF_REQUIRE(!(ext && d->upsample) || cp % 64 == 0, "cf_conv2d: general upsample path needs cout_pad %% 64 == 0 (got %d)", cp);
+  CF_REQUIRE(!(direct && d->in_nchw) || cp == 64, "cf_conv2d: in_nchw path is built for cout_pad 64 (got %d)", cp);
+  if (direct && d->taps == 1 && d->split_k >= 1) {  // small token matrices: 64x64 tiles, split_k workgroups per tile
+    const int K = d->c0 + d->c1, V = K / (CF_BK * CF_SK_SLABS);  // virtual chunks: the summation order is out = ((0 + P0) + P1) + ... whatever split_k is
+    CF_REQUIRE(cp % 64 == 0 && K % (CF_BK * CF_SK_SLABS) == 0 && V >= 1 && V % d->split_k == 0,
+               "cf_conv2d: split_k %d needs cout_pad %% 64 == 0, K %% 128 == 0 and split_k dividing K/128 = %d", d->split_k, V);
+    CF_REQUIRE(pq || d->split_k == 1 || (d->workspace && d->counters), "cf_conv2d: split_k > 1 needs workspace and counters");
   }
-  if (d->winograd == 2) return cf_wf43_launch(d, stream, pq);  // F(4x4,3x3), split-half operands (cf_wf43.hip)
-  CF_REQUIRE(d->winograd == 0 || d->winograd == 1, "cf_conv2d: winograd must be 0, 1 (F(2x2,3x3)) or 2 (F(4x4,3x3)), got %d", d->winograd);
-  if (d->winograd) return cf_winograd_launch(d, stream, pq);  // fp32 or split-half operands
-  if (d->bf16_mfma == CF_OPERAND_F16X2) return cf_split_launch(d, stream, pq);
+  // narrow, for small-M layers (16x16 / 32x32 latents): at batch 16 a 128x128 tiling yields only 128-256 workgroups for 256 CUs; halving the N
+  // tile doubles the count at the price of gathering the halo patch twice.  It depends on the per-image shape ONLY, never on the batch: tiling
+  // (and with it the order of the statistics partials) must be the same for a face alone or inside any batch / shard: bitwise batch-invariant.
+  f = {ld0, ld1, ldo, ext, few_cout, cp % 128 == 0 && (long)d->hout * d->wout <= 1024};
+  return CF_OK;
+}
 
-  ConvArgsExt a;
+static void conv_fill_args(ConvArgsExt& a, const cf_conv_desc* d, const ConvFacts& f) {
   cf_fill_conv_args(a, d);
   a.nchunks = d->bf16_mfma ? a.cin / 32 : (a.cin + CF_BK - 1) / CF_BK;
   a.hin = d->hin;
@@ -1400,128 +1396,128 @@ static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
   a.upsample = d->upsample ? 1 : 0;
   a.out_nchw = d->out_nchw;
   a.stats_cpg = d->stats_cpg > 0 ? d->stats_cpg : 1;
-  a.nparts = 0;
-  a.tiles_x = a.tiles_per_img = a.ntn = 0;
-  a.ld0 = ld0;
-  a.ld1 = ld1;
-  a.ldo = ldo;
+  a.nparts = a.tiles_x = a.tiles_per_img = a.ntn = 0;
+  a.ld0 = f.ld0;
+  a.ld1 = f.ld1;
+  a.ldo = f.ldo;
   a.pad_mode = d->pad_mode;
   a.pad_lo = d->pad_lo;
   a.nt_out = cf_nt_store((long)d->batch * d->hout * d->wout * d->cout * 4);
+}
 
+constexpr int CF_NOT_MINE = 1;  // (as cf_gemm_f32_tile_try: no rung takes the shape; the caller goes on or reports)
+// The tile ladder of the direct stride-1 kernels: narrow -> 128x64 tiles, cout_pad % 128 == 0 -> 128x128, else 256x64 -- for cout_pad 64 only
+// (exact64: fp32 operands) or for whatever is left (16-bit operands).  Instantiate it for the (TAPS, BF16, F16) that have all three shapes only.
+template <int TAPS, bool BF16, bool F16>
+static int launch_ladder(const ConvArgsExt& a, bool narrow, bool exact64, hipStream_t stream, int* pq) {
+  if (narrow) return launch<TAPS, 1, 2, 2, 2, 1, false, BF16, false, F16>(a, stream, pq);
+  if (a.cout_pad % 128 == 0) return launch<TAPS, 1, 2, 2, 2, 2, false, BF16, false, F16>(a, stream, pq);
+  if (!exact64 || a.cout_pad == 64) return launch<TAPS, 1, 4, 1, 2, 2, false, BF16, false, F16>(a, stream, pq);
+  return CF_NOT_MINE;
+}
+
+// The vector-ALU first conv (write-bound layer): 16x16 pixel tiles, four statistics partials per tile.
+static int launch_few_cin(ConvArgsExt& a, const cf_conv_desc* d, hipStream_t stream, int* pq) {
+  a.tiles_x = d->wout / 16;
+  a.tiles_per_img = a.tiles_x * (d->hout / 16);
+  a.nparts = a.tiles_per_img * 4;
+  if (pq) {
+    *pq = a.nparts;
+    return CF_OK;
+  }
+  const auto kern = d->c0 != 3 ? conv3x3_few_cin_kernel<0> : a.nt_out ? conv3x3_few_cin_kernel<3, true> : conv3x3_few_cin_kernel<3>;
+  hipLaunchKernelGGL(kern, dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
+  CF_CHECK_LAUNCH("cf_conv2d");
+  return CF_OK;
+}
+
+// The vector-ALU NCHW <=4-channel output conv, any image size (edge tiles are masked).  No statistics: a parts query goes on to the next rung.
+static int launch_few_cout(ConvArgsExt& a, const cf_conv_desc* d, hipStream_t stream, int* pq) {
+  if (pq) return CF_NOT_MINE;
+  a.tiles_x = (d->wout + 15) / 16;
+  a.tiles_per_img = a.tiles_x * ((d->hout + 15) / 16);
+  const auto kern = d->cout != 3 ? conv3x3_few_cout_kernel<4> : d->io_bf16 ? conv3x3_few_cout_kernel<3, true> : conv3x3_few_cout_kernel<3>;
+  hipLaunchKernelGGL(kern, dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
+  CF_CHECK_LAUNCH("cf_conv2d");
+  return CF_OK;
+}
+
+// The direct kernels of this file.  Single-shape combinations are direct calls; the seven with three shapes go through launch_ladder.
+static int launch_direct(ConvArgsExt& a, const cf_conv_desc* d, const ConvFacts& f, hipStream_t stream, int* pq) {
   const int cp = d->cout_pad;
-  // Small-M layers (16x16 / 32x32 latents): at batch 16 a 128x128 tiling yields only 128-256 workgroups for 256 CUs;
-  // halving the N tile doubles the workgroup count at the price of gathering the halo patch twice.  The choice depends
-  // on the per-image shape ONLY, never on the batch: tiling (and with it the order of the statistics partials) must be
-  // the same for a face whether it is restored alone or inside any batch / shard, so results stay bitwise batch-invariant.
-  const bool narrow = cp % 128 == 0 && (long)d->hout * d->wout <= 1024;
-  if (ext) {
-    const bool f16 = d->bf16_mfma == CF_OPERAND_F16;
+  const bool f16 = d->bf16_mfma == CF_OPERAND_F16, bf16 = d->bf16_mfma == CF_OPERAND_BF16;
+  if (f.ext) {  // the general instantiations; their rungs follow no common ladder
     if (d->stride == 2) return launch<9, 2, 2, 2, 2, 2, false, false, true>(a, stream, pq);  // fp32, cout_pad % 128 == 0 (checked)
     if (d->upsample) {
-      CF_REQUIRE(cp % 64 == 0, "cf_conv2d: general upsample path needs cout_pad %% 64 == 0 (got %d)", cp);
       if (f16) return launch<4, 1, 4, 1, 2, 2, false, false, true, true>(a, stream, pq);
       if (cp % 128 == 0) return launch<4, 1, 2, 2, 2, 2, false, false, true>(a, stream, pq);
       return launch<4, 1, 4, 1, 2, 2, false, false, true>(a, stream, pq);
     }
-    if (f16) {
-      if (cp % 64 == 0) return launch<9, 1, 4, 1, 2, 2, false, false, true, true>(a, stream, pq);
-      return launch<9, 1, 4, 1, 2, 1, false, false, true, true>(a, stream, pq);
-    }
+    if (f16 && cp % 64 == 0) return launch<9, 1, 4, 1, 2, 2, false, false, true, true>(a, stream, pq);
+    if (f16) return launch<9, 1, 4, 1, 2, 1, false, false, true, true>(a, stream, pq);
     if (cp % 128 == 0) return launch<9, 1, 2, 2, 2, 2, false, false, true>(a, stream, pq);
     if (cp % 64 == 0) return launch<9, 1, 4, 1, 2, 2, false, false, true>(a, stream, pq);
-    return launch<9, 1, 4, 1, 2, 1, false, false, true>(a, stream, pq);  // cout_pad % 32 == 0 (checked above)
+    return launch<9, 1, 4, 1, 2, 1, false, false, true>(a, stream, pq);  // cout_pad % 32 == 0 (checked)
   }
+  int rc = CF_NOT_MINE;
   if (d->upsample) {  // nearest x2 + 3x3 as four 2x2 sub-pixel convolutions; weight packed by cf_pack_conv_weight_up2x[_bf16]
-    if (d->bf16_mfma == CF_OPERAND_F16) {
-      if (narrow) return launch<4, 1, 2, 2, 2, 1, false, false, false, true>(a, stream, pq);
-      if (cp % 128 == 0) return launch<4, 1, 2, 2, 2, 2, false, false, false, true>(a, stream, pq);
-      return launch<4, 1, 4, 1, 2, 2, false, false, false, true>(a, stream, pq);
-    }
-    if (d->bf16_mfma && d->io_bf16) return launch<4, 1, 2, 2, 2, 2, false, true, false, false, true>(a, stream, pq);   // (cout_pad % 128 == 0, > 1024 pixels: checked above)
-    if (d->bf16_mfma) {
-      if (narrow) return launch<4, 1, 2, 2, 2, 1, false, true>(a, stream, pq);
-      if (cp % 128 == 0) return launch<4, 1, 2, 2, 2, 2, false, true>(a, stream, pq);
-      return launch<4, 1, 4, 1, 2, 2, false, true>(a, stream, pq);
-    }
-    if (narrow) return launch<4, 1, 2, 2, 2, 1, false>(a, stream, pq);
-    if (cp % 128 == 0) return launch<4, 1, 2, 2, 2, 2, false>(a, stream, pq);
-    if (cp == 64) return launch<4, 1, 4, 1, 2, 2, false>(a, stream, pq);
+    if (f16) return launch_ladder<4, false, true>(a, f.narrow, false, stream, pq);
+    if (bf16 && d->io_bf16) return launch<4, 1, 2, 2, 2, 2, false, true, false, false, true>(a, stream, pq);   // (cout_pad % 128 == 0, > 1024 pixels: checked)
+    if (bf16) return launch_ladder<4, true, false>(a, f.narrow, false, stream, pq);
+    rc = launch_ladder<4, false, false>(a, f.narrow, true, stream, pq);
+    if (rc != CF_NOT_MINE) return rc;
     cf_set_error("cf_conv2d: upsample path needs cout_pad 64 or a multiple of 128 (got %d)", cp);
     return CF_ERR_ARG;
   }
-  if (d->bf16_mfma == CF_OPERAND_F16) {
-    if (narrow) return launch<9, 1, 2, 2, 2, 1, false, false, false, true>(a, stream, pq);
-    if (cp % 128 == 0) return launch<9, 1, 2, 2, 2, 2, false, false, false, true>(a, stream, pq);
-    return launch<9, 1, 4, 1, 2, 2, false, false, false, true>(a, stream, pq);  // cout_pad == 64
-  }
-  if (d->bf16_mfma && d->io_bf16) return launch<9, 1, 4, 1, 2, 2, false, true, false, false, true>(a, stream, pq);   // (cout_pad == 64: checked above)
-  if (d->bf16_mfma) {
-    if (narrow) return launch<9, 1, 2, 2, 2, 1, false, true>(a, stream, pq);
-    if (cp % 128 == 0) return launch<9, 1, 2, 2, 2, 2, false, true>(a, stream, pq);
-    return launch<9, 1, 4, 1, 2, 2, false, true>(a, stream, pq);  // cout_pad == 64
-  }
+  if (f16) return launch_ladder<9, false, true>(a, f.narrow, false, stream, pq);
+  if (bf16 && d->io_bf16) return launch<9, 1, 4, 1, 2, 2, false, true, false, false, true>(a, stream, pq);   // (cout_pad == 64: checked)
+  if (bf16) return launch_ladder<9, true, false>(a, f.narrow, false, stream, pq);
   if (d->taps == 9 && d->stride == 1) {
     if (d->in_nchw && d->cout == 64 && cp == 64 && d->hout % 16 == 0 && d->wout % 16 == 0 && (!d->stats_cpg || d->stats_cpg == 2) &&
-        d->epilogue == CF_EPI_NONE) {  // the vector-ALU first conv (write-bound layer)
-      a.tiles_x = d->wout / 16;
-      a.tiles_per_img = a.tiles_x * (d->hout / 16);
-      a.nparts = a.tiles_per_img * 4;
-      if (pq) {
-        *pq = a.nparts;
-        return CF_OK;
-      }
-      if (d->c0 == 3 && a.nt_out) hipLaunchKernelGGL((conv3x3_few_cin_kernel<3, true>), dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
-      else if (d->c0 == 3) hipLaunchKernelGGL(conv3x3_few_cin_kernel<3>, dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL(conv3x3_few_cin_kernel<0>, dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
-      CF_CHECK_LAUNCH("cf_conv2d");
-      return CF_OK;
-    }
-    if (d->in_nchw) {
-      CF_REQUIRE(cp == 64, "cf_conv2d: in_nchw path is built for cout_pad 64 (got %d)", cp);
-      return launch<9, 1, 4, 1, 2, 2, true>(a, stream, pq);
-    }
-    if (narrow) return launch<9, 1, 2, 2, 2, 1, false>(a, stream, pq);
-    if (cp % 128 == 0) return launch<9, 1, 2, 2, 2, 2, false>(a, stream, pq);
-    if (cp == 64) return launch<9, 1, 4, 1, 2, 2, false>(a, stream, pq);
-    if (few_cout && !pq) {  // any image size: edge tiles are masked
-      a.tiles_x = (d->wout + 15) / 16;
-      a.tiles_per_img = a.tiles_x * ((d->hout + 15) / 16);
-      if (d->cout == 3 && d->io_bf16) hipLaunchKernelGGL((conv3x3_few_cout_kernel<3, true>), dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
-      else if (d->cout == 3) hipLaunchKernelGGL(conv3x3_few_cout_kernel<3>, dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL(conv3x3_few_cout_kernel<4>, dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
-      CF_CHECK_LAUNCH("cf_conv2d");
-      return CF_OK;
-    }
-    if (cp == 32) return launch<9, 1, 4, 1, 2, 1, false>(a, stream, pq);
-  } else if (d->taps == 9 && d->stride == 2) {
+        d->epilogue == CF_EPI_NONE)
+      return launch_few_cin(a, d, stream, pq);
+    if (d->in_nchw) return launch<9, 1, 4, 1, 2, 2, true>(a, stream, pq);  // (cout_pad == 64: checked)
+    rc = launch_ladder<9, false, false>(a, f.narrow, true, stream, pq);
+    if (rc == CF_NOT_MINE && f.few_cout) rc = launch_few_cout(a, d, stream, pq);
+    if (rc == CF_NOT_MINE && cp == 32) rc = launch<9, 1, 4, 1, 2, 1, false>(a, stream, pq);
+  } else if (d->taps == 9) {  // stride 2
     // 128-wide channel tiles unless the layer is small (at most 64 of them per image): 64-wide tiles double the workgroup count of a
     // small batch.  Per-image shape only: the two widths group the statistics partials differently (see cf_split_launch)
     const long wide_wgs = ((long)d->hout * d->wout / 128) * (cp / 128);
     if (cp % 128 == 0 && wide_wgs > 64) return launch<9, 2, 2, 2, 2, 2, false>(a, stream, pq);
     if (cp % 64 == 0) return launch<9, 2, 2, 2, 2, 1, false>(a, stream, pq);
+  } else if (d->split_k >= 1) {  // small token matrices: 64x64 tiles, split_k workgroups per tile (its rules: checked)
+    if (!pq && d->split_k == 1) {   // one workgroup per tile on a large token matrix: the 128-token tile kernel (bitwise the same result)
+      rc = cf_gemm_f32_tile_try(d, stream);
+      if (rc != 1) return rc;
+    }
+    return launch_sk<2, 2, 1, 1>(a, d->workspace, d->counters, d->split_k, stream, pq);
+  } else if (d->io_bf16) {   // (images of more than 1024 pixels, cout_pad 64 or a multiple of 128: checked)
+    if (cp % 128 == 0) return launch<1, 1, 2, 2, 2, 2, false, false, false, false, true>(a, stream, pq);
+    return launch<1, 1, 4, 1, 2, 2, false, false, false, false, true>(a, stream, pq);
   } else {
-    if (d->split_k >= 1) {  // small token matrices: 64x64 tiles, split_k workgroups per tile
-      const int V = a.nchunks / CF_SK_SLABS;  // virtual chunks: the summation order is out = ((0 + P0) + P1) + ... whatever split_k is
-      CF_REQUIRE(cp % 64 == 0 && a.nchunks % CF_SK_SLABS == 0 && V >= 1 && V % d->split_k == 0,
-                 "cf_conv2d: split_k %d needs cout_pad %% 64 == 0, K %% 128 == 0 and split_k dividing K/128 = %d", d->split_k, V);
-      CF_REQUIRE(pq || d->split_k == 1 || (d->workspace && d->counters), "cf_conv2d: split_k > 1 needs workspace and counters");
-      if (!pq && d->split_k == 1) {   // one workgroup per tile on a large token matrix: the 128-token tile kernel (bitwise the same result)
-        const int rc = cf_gemm_f32_tile_try(d, stream);
-        if (rc != 1) return rc;
-      }
-      return launch_sk<2, 2, 1, 1>(a, d->workspace, d->counters, d->split_k, stream, pq);
-    }
-    if (d->io_bf16) {   // (images of more than 1024 pixels, cout_pad 64 or a multiple of 128: checked above)
-      if (cp % 128 == 0) return launch<1, 1, 2, 2, 2, 2, false, false, false, false, true>(a, stream, pq);
-      return launch<1, 1, 4, 1, 2, 2, false, false, false, false, true>(a, stream, pq);
-    }
-    if (narrow) return launch<1, 1, 2, 2, 2, 1, false>(a, stream, pq);
-    if (cp % 128 == 0) return launch<1, 1, 2, 2, 2, 2, false>(a, stream, pq);
-    if (cp == 64) return launch<1, 1, 4, 1, 2, 2, false>(a, stream, pq);
+    rc = launch_ladder<1, false, false>(a, f.narrow, true, stream, pq);
   }
+  if (rc != CF_NOT_MINE) return rc;
   cf_set_error("cf_conv2d: no kernel for taps=%d stride=%d cout_pad=%d", d->taps, d->stride, cp);
   return CF_ERR_ARG;
+}
+
+static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
+  ConvFacts f;
+  if (const int rc = conv_validate(d, pq, f); rc != CF_OK) return rc;
+  if (d->taps == 1 && d->bf16_mfma == CF_OPERAND_F16X2) {  // (the other four kernel families first)
+    // images of more than CF_TOKEN_IMAGE_MAX pixels: the streaming 1x1 form of the split-half convolution kernel (weight: form 3 of
+    // cf_pack_conv_weight_f16x2); token matrices (the Transformer's 16x16 "images"): the token GEMM (cf_pack_linear_weight_f16x2)
+    if ((long)d->hout * d->wout > CF_TOKEN_IMAGE_MAX) return cf_split_launch(d, stream, pq);
+    return cf_gemm_split_launch(d, stream);
+  }
+  if (d->winograd == 2) return cf_wf43_launch(d, stream, pq);  // F(4x4,3x3), split-half operands (cf_wf43.hip)
+  if (d->winograd) return cf_winograd_launch(d, stream, pq);   // F(2x2,3x3), fp32 or split-half operands
+  if (d->bf16_mfma == CF_OPERAND_F16X2) return cf_split_launch(d, stream, pq);
+  ConvArgsExt a;
+  conv_fill_args(a, d, f);
+  return launch_direct(a, d, f, stream, pq);
 }
 
 extern "C" int cf_conv2d(const cf_conv_desc* d, cf_stream_t stream) { return conv_dispatch(d, (hipStream_t)stream, nullptr); }

@@ -339,117 +339,112 @@ def pack_scale(wmax):
     return 1.0 if wmax == 0.0 or not math.isfinite(wmax) else 2.0 ** (14 - math.frexp(wmax)[1] + 1)
 
 
+def _f23_max(w):
+    """max |G g G^T| of Winograd F(2x2,3x3) in fp64 (elementwise: G's rows are g0, (g0 + g1 + g2)/2, (g0 - g1 + g2)/2, g2), all 16 positions
+    in one tensor and ONE reduction / host read-back per weight."""
+    g = w.double()
+    r = torch.stack((g[:, :, 0], 0.5 * (g[:, :, 0] + g[:, :, 1] + g[:, :, 2]), 0.5 * (g[:, :, 0] - g[:, :, 1] + g[:, :, 2]), g[:, :, 2]), dim=2)
+    u = torch.stack((r[..., 0], 0.5 * (r[..., 0] + r[..., 1] + r[..., 2]), 0.5 * (r[..., 0] - r[..., 1] + r[..., 2]), r[..., 2]), dim=3)
+    return float(u.abs().max())
+
+
+def _f43_max(w):
+    """max |G' g G'^T| of Winograd F(4x4,3x3) in fp64; G' = D^-1 G of the points (0, +-1/2, +-2, inf), the matrix cf_wf43.hip documents."""
+    Gm = torch.tensor([[4.0, 0.0, 0.0], [-32 / 15, -16 / 15, -8 / 15], [-32 / 15, 16 / 15, -8 / 15], [1 / 15, 2 / 15, 4 / 15],
+                       [1 / 15, -2 / 15, 4 / 15], [0.0, 0.0, 4.0]], dtype=torch.float64, device=w.device)
+    return float(torch.einsum('xa,kcab,yb->kcxy', Gm, w.double(), Gm).abs().max())
+
+
+def _require_3x3(w, cin_mult, cout_mult, what, up2x):
+    """The shape rule of the 3x3 layouts: whole K slabs and channel tiles; up2x is refused (pass False for a layout with a folded form)."""
+    if up2x or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[1] % cin_mult or w.shape[0] % cout_mult:
+        raise ValueError(f'{what} packing needs a 3x3 weight with cin % {cin_mult} == 0 and cout % {cout_mult} == 0 (and has no up2x form)')
+
+
+def _packed(name, n, w, *args, dtype=torch.float32):
+    """An n-element buffer that the C packer `name`(w, *args, buffer, stream) fills."""
+    packed = torch.empty(n, dtype=dtype, device=w.device)
+    L.check(getattr(L.load(), name)(L.ptr(w), *args, L.ptr(packed, dtype=None), L.stream_ptr()), name)
+    return packed
+
+
+# One packer per layout: (w contiguous fp32, bias, code, up2x, stride2) -> PackedWeight.  The Winograd-domain layouts differ in this row only:
+# code -> (name in messages, C packer, transform-domain positions, domain maximum (None: fp32 operands, no scale), operand, wino)
+_WINO = {WINOGRAD: ('winograd', 'cf_pack_conv_weight_winograd', 16, None, False, True),
+         WSPLIT: ('winograd f16x2', 'cf_pack_conv_weight_winograd_f16x2', 16, _f23_max, OPERAND_F16X2, True),
+         WF16: ('winograd f16x2', 'cf_pack_conv_weight_winograd_f16x2', 16, _f23_max, 2, True),   # (reads the hi slot)
+         WBF16: ('winograd f16x2', 'cf_pack_conv_weight_winograd_bf16', 16, _f23_max, 1, True),
+         WF43F: ('winograd F(4,3)', 'cf_pack_conv_weight_winograd43', 36, None, False, 2),
+         WF43: ('winograd F(4,3) f16x2', 'cf_pack_conv_weight_winograd43_f16x2', 36, _f43_max, OPERAND_F16X2, 2)}
+
+
+def _pack_winograd(w, b, code, up2x, stride2):
+    what, fn, npos, domain_max, operand, wino = _WINO[code]
+    _require_3x3(w, 16, 64, what, up2x)
+    cout, cin = w.shape[:2]
+    scale = () if domain_max is None else (pack_scale(domain_max(w)),)
+    return PackedWeight(_packed(fn, npos * cin * cout, w, cout, cin, cout, cin, *scale), b, cout, cin, 9, cout, cin, bf16=operand, wino=wino, scale=(*scale, 1.0)[0])
+
+
+def _pack_split(w, b, code, up2x, stride2):
+    """Split-half convolution kernel, form 0 plain 3x3 / 1 folded upsample / 2 stride 2 (a 2x2 convolution of the space-to-depth input) / 3 streaming 1x1 on images."""
+    cout, cin, conv1 = w.shape[0], w.shape[1], w.dim() == 2 or tuple(w.shape[2:]) == (1, 1)
+    if conv1 and (up2x or cin % 32 or cout % 64):
+        raise ValueError('f16x2 1x1 packing needs cin % 32 == 0 and cout % 64 == 0')
+    if not conv1:
+        _require_3x3(w, 16 if stride2 else 32, 64, 'f16x2', False)
+    form = 3 if conv1 else 2 if stride2 else int(bool(up2x))
+    scale = pack_scale(float(w.abs().max()) * (4.0 if up2x else 1.0))   # (folded taps: at most 4 summed)
+    packed = _packed('cf_pack_conv_weight_f16x2', (9, 16, 16, 1)[form] * cin * cout, w, cout, cin, form, cout, cin, scale)
+    return PackedWeight(packed, b, cout, cin, 1 if conv1 else 9, cout, cin, bf16=OPERAND_F16X2, up2x=bool(up2x), scale=scale, s2=bool(stride2) and not conv1, conv1=conv1)
+
+
+def _pack_gemm_split(w, b, code, up2x, stride2):
+    cout, cin = w.shape[:2]
+    w2 = w.reshape(cout, cin)
+    if w.dim() not in (2, 4) or w.numel() != cout * cin or cout % 64 or cin % 128:
+        raise ValueError('f16x2 GEMM packing needs a Linear / 1x1 weight with cout % 64 == 0 and cin % 128 == 0')
+    scale = pack_scale(float(w2.abs().max()))
+    return PackedWeight(_packed('cf_pack_linear_weight_f16x2', cout * cin, w2, cout, cin, scale), b, cout, cin, 1, cout, cin, bf16=OPERAND_F16X2, scale=scale)
+
+
+def _pack_plain(w, b, code, up2x, stride2):
+    if w.dim() not in (2, 4):
+        raise ValueError('weight must be 2-D or 4-D')
+    if w.dim() == 4 and (w.shape[2] != w.shape[3] or w.shape[2] not in (1, 3)):
+        raise ValueError(f'unsupported kernel size {tuple(w.shape[2:])}')
+    cout, cin, taps = w.shape[0], w.shape[1], 1 if w.dim() == 2 else w.shape[2] * w.shape[3]
+    cout_pad, cin_pad = _cout_pad(cout), (cin + 15) // 16 * 16
+    packed = _packed('cf_pack_conv_weight', L.load().cf_packed_weight_elems(cin_pad, taps, cout_pad), w, cout, cin, taps, cout_pad, cin_pad)
+    return PackedWeight(packed, b, cout, cin, taps, cout_pad, cin_pad)
+
+
+def _pack_16_or_folded(w, b, code, up2x, stride2):
+    """bf16 / IEEE-half operands and the folded upsample (of any of the three operand types): 3x3 convs whose channels fill whole K slabs."""
+    cout, cin, slab = w.shape[0], w.shape[1], 32 if code else 16
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or cin % slab:
+        raise ValueError(f"{('fp32', 'bf16', 'f16')[code]}{' up2x' if up2x else ''} packing needs a 3x3 weight with cin % {slab} == 0")
+    # bf16 kernels and every upsample kernel have N tiles of at least 64; the f16 general instantiation also has a 32-wide one
+    cout_pad = _cout_pad(cout) if (code == 2 and not up2x) else max(64, _cout_pad(cout))
+    name = 'cf_pack_conv_weight' + ('_up2x' if up2x else '') + ('', '_bf16', '_f16')[code]
+    packed = _packed(name, (16 if up2x else 9) * cin * cout_pad, w, cout, cin, *(() if up2x else (9,)), cout_pad, cin, dtype=(torch.float32, torch.bfloat16, torch.float16)[code])
+    return PackedWeight(packed, b, cout, cin, 9, cout_pad, cin, bf16=code, up2x=bool(up2x))
+
+
 def pack_weight(weight, bias=None, bf16=False, up2x=False, f16=False, stride2=False):
     """weight: (cout, cin, 3, 3) | (cout, cin, 1, 1) | (cout, cin) CUDA fp32 -> PackedWeight.
     bf16=True (3x3 only, cin % 32 == 0): bf16 operands for the v_mfma_f32_32x32x16_bf16 path of cf_conv2d.
     f16=True (3x3 only, cin % 32 == 0): IEEE-half operands (general instantiations; RRDBNet's half mode).
     up2x=True (3x3 only): taps folded for conv2d(upsample=True) -- nearest x2 + 3x3 as four 2x2 sub-pixel convolutions.
     stride2=True (code SPLIT only): the stride-2 form of the split-half kernel -- a 2x2 convolution of the space-to-depth input."""
-    lib = L.load()
     code = 2 if f16 else int(bf16)   # callers may pass the operand code (0 fp32 / 1 bf16 / 2 f16 / 3 winograd) through `bf16`
     w = _f32(weight.detach()).contiguous()
     b = None if bias is None else _f32(bias.detach()).contiguous().clone()
-    cout, cin = w.shape[0], w.shape[1]
-    if code == WINOGRAD:
-        if up2x or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or cin % 16 or cout % 64:
-            raise ValueError('winograd packing needs a 3x3 weight with cin % 16 == 0 and cout % 64 == 0 (no up2x)')
-        packed = torch.empty(16 * cin * cout, dtype=torch.float32, device=w.device)
-        L.check(lib.cf_pack_conv_weight_winograd(L.ptr(w), cout, cin, cout, cin, L.ptr(packed, dtype=None), L.stream_ptr()),
-                'cf_pack_conv_weight_winograd')
-        return PackedWeight(packed, b, cout, cin, 9, cout, cin, wino=True)
-    if code == GSPLIT:
-        w2 = w.reshape(cout, cin)
-        if w.dim() not in (2, 4) or w.numel() != cout * cin or cout % 64 or cin % 128:
-            raise ValueError('f16x2 GEMM packing needs a Linear / 1x1 weight with cout % 64 == 0 and cin % 128 == 0')
-        scale = pack_scale(float(w2.abs().max()))
-        packed = torch.empty(cout * cin, dtype=torch.float32, device=w.device)
-        L.check(lib.cf_pack_linear_weight_f16x2(L.ptr(w2.contiguous()), cout, cin, scale, L.ptr(packed, dtype=None), L.stream_ptr()),
-                'cf_pack_linear_weight_f16x2')
-        return PackedWeight(packed, b, cout, cin, 1, cout, cin, bf16=OPERAND_F16X2, scale=scale)
-    if code == WF43F:
-        if up2x or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or cin % 16 or cout % 64:
-            raise ValueError('winograd F(4,3) packing needs a 3x3 weight with cin % 16 == 0 and cout % 64 == 0 (no up2x)')
-        packed = torch.empty(36 * cin * cout, dtype=torch.float32, device=w.device)
-        L.check(lib.cf_pack_conv_weight_winograd43(L.ptr(w), cout, cin, cout, cin, L.ptr(packed, dtype=None), L.stream_ptr()),
-                'cf_pack_conv_weight_winograd43')
-        return PackedWeight(packed, b, cout, cin, 9, cout, cin, wino=2)
-    if code == WF43:
-        if up2x or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or cin % 16 or cout % 64:
-            raise ValueError('winograd F(4,3) f16x2 packing needs a 3x3 weight with cin % 16 == 0 and cout % 64 == 0 (no up2x)')
-        # max |G' g G'^T| for the power-of-two scale; G' = D^-1 G of the points (0, +-1/2, +-2, inf), the matrix cf_wf43.hip documents
-        Gm = torch.tensor([[4.0, 0.0, 0.0], [-32 / 15, -16 / 15, -8 / 15], [-32 / 15, 16 / 15, -8 / 15], [1 / 15, 2 / 15, 4 / 15],
-                           [1 / 15, -2 / 15, 4 / 15], [0.0, 0.0, 4.0]], dtype=torch.float64, device=w.device)
-        umax = float(torch.einsum('xa,kcab,yb->kcxy', Gm, w.double(), Gm).abs().max())
-        scale = 1.0 if umax == 0.0 or not math.isfinite(umax) else 2.0 ** (14 - math.frexp(umax)[1] + 1)
-        packed = torch.empty(36 * cin * cout, dtype=torch.float32, device=w.device)
-        L.check(lib.cf_pack_conv_weight_winograd43_f16x2(L.ptr(w), cout, cin, cout, cin, scale, L.ptr(packed, dtype=None), L.stream_ptr()),
-                'cf_pack_conv_weight_winograd43_f16x2')
-        return PackedWeight(packed, b, cout, cin, 9, cout, cin, bf16=OPERAND_F16X2, wino=2, scale=scale)
-    if code in (WSPLIT, WF16, WBF16):
-        if up2x or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or cin % 16 or cout % 64:
-            raise ValueError('winograd f16x2 packing needs a 3x3 weight with cin % 16 == 0 and cout % 64 == 0 (no up2x)')
-        # max |G g G^T| for the power-of-two scale (elementwise: G's rows are g0, (g0 + g1 + g2)/2, (g0 - g1 + g2)/2, g2), all 16 positions
-        # in one tensor and ONE reduction / host read-back per weight
-        g = w.double()
-        r = torch.stack((g[:, :, 0], 0.5 * (g[:, :, 0] + g[:, :, 1] + g[:, :, 2]), 0.5 * (g[:, :, 0] - g[:, :, 1] + g[:, :, 2]), g[:, :, 2]), dim=2)
-        u = torch.stack((r[..., 0], 0.5 * (r[..., 0] + r[..., 1] + r[..., 2]), 0.5 * (r[..., 0] - r[..., 1] + r[..., 2]), r[..., 2]), dim=3)
-        umax = float(u.abs().max())
-        scale = 1.0 if umax == 0.0 or not math.isfinite(umax) else 2.0 ** (14 - math.frexp(umax)[1] + 1)
-        packed = torch.empty(16 * cin * cout, dtype=torch.float32, device=w.device)
-        fn = 'cf_pack_conv_weight_winograd_bf16' if code == WBF16 else 'cf_pack_conv_weight_winograd_f16x2'   # (WF16 reads the hi slot)
-        L.check(getattr(lib, fn)(L.ptr(w), cout, cin, cout, cin, scale, L.ptr(packed, dtype=None), L.stream_ptr()), fn)
-        operand = {WSPLIT: OPERAND_F16X2, WF16: 2, WBF16: 1}[code]
-        return PackedWeight(packed, b, cout, cin, 9, cout, cin, bf16=operand, wino=True, scale=scale)
-    if stride2 and (code != SPLIT or up2x):
+    if stride2 and (code != SPLIT or up2x) and code != GSPLIT and code not in _WINO:   # (those two never looked at the flag)
         raise ValueError('stride2 packing exists for the split-half kernel (bf16=SPLIT) only')
-    if code == SPLIT and (w.dim() == 2 or tuple(w.shape[2:]) == (1, 1)):
-        # 1x1 on images (the ResBlock skip convolutions): the streaming form of the split-half convolution kernel
-        if up2x or cin % 32 or cout % 64:
-            raise ValueError('f16x2 1x1 packing needs cin % 32 == 0 and cout % 64 == 0')
-        wmax = float(w.abs().max())
-        scale = 1.0 if wmax == 0.0 or not math.isfinite(wmax) else 2.0 ** (14 - math.frexp(wmax)[1] + 1)
-        packed = torch.empty(cin * cout, dtype=torch.float32, device=w.device)
-        L.check(lib.cf_pack_conv_weight_f16x2(L.ptr(w), cout, cin, 3, cout, cin, scale, L.ptr(packed, dtype=None), L.stream_ptr()),
-                'cf_pack_conv_weight_f16x2')
-        return PackedWeight(packed, b, cout, cin, 1, cout, cin, bf16=OPERAND_F16X2, scale=scale, conv1=True)
-    if code == SPLIT:
-        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or cin % (16 if stride2 else 32) or cout % 64:
-            raise ValueError('f16x2 packing needs a 3x3 weight with cin % 32 == 0 (stride 2: % 16) and cout % 64 == 0')
-        # power-of-two scale that puts max|w'| (folded taps: at most 4 summed) into [2^14, 2^15): lo halves stay normal
-        wmax = float(w.abs().max()) * (4.0 if up2x else 1.0)
-        scale = 1.0 if wmax == 0.0 or not math.isfinite(wmax) else 2.0 ** (14 - math.frexp(wmax)[1] + 1)
-        packed = torch.empty((16 if (up2x or stride2) else 9) * cin * cout, dtype=torch.float32, device=w.device)
-        form = 2 if stride2 else int(bool(up2x))
-        L.check(lib.cf_pack_conv_weight_f16x2(L.ptr(w), cout, cin, form, cout, cin, scale, L.ptr(packed, dtype=None), L.stream_ptr()),
-                'cf_pack_conv_weight_f16x2')
-        return PackedWeight(packed, b, cout, cin, 9, cout, cin, bf16=OPERAND_F16X2, up2x=bool(up2x), scale=scale, s2=bool(stride2))
-    if w.dim() == 4:
-        if w.shape[2] != w.shape[3] or w.shape[2] not in (1, 3):
-            raise ValueError(f'unsupported kernel size {tuple(w.shape[2:])}')
-        taps = w.shape[2] * w.shape[3]
-    elif w.dim() == 2:
-        taps = 1
-    else:
-        raise ValueError('weight must be 2-D or 4-D')
-    if code or up2x:   # 16-bit operands and the folded upsample exist for 3x3 convs whose channels fill whole K slabs
-        slab = 32 if code else 16
-        if taps != 9 or cin % slab:
-            raise ValueError(f"{('fp32', 'bf16', 'f16')[code]}{' up2x' if up2x else ''} packing needs a 3x3 weight with "
-                             f'cin % {slab} == 0')
-    if not code and not up2x:
-        cout_pad, cin_pad = _cout_pad(cout), (cin + 15) // 16 * 16
-        packed = torch.empty(lib.cf_packed_weight_elems(cin_pad, taps, cout_pad), dtype=torch.float32, device=w.device)
-        L.check(lib.cf_pack_conv_weight(L.ptr(w), cout, cin, taps, cout_pad, cin_pad, L.ptr(packed, dtype=None), L.stream_ptr()),
-                'cf_pack_conv_weight')
-        return PackedWeight(packed, b, cout, cin, taps, cout_pad, cin_pad)
-    # bf16 kernels and every upsample kernel have N tiles of at least 64; the f16 general instantiation also has a 32-wide one
-    cout_pad = _cout_pad(cout) if (code == 2 and not up2x) else max(64, _cout_pad(cout))
-    dtype = (torch.float32, torch.bfloat16, torch.float16)[code]
-    packed = torch.empty((16 if up2x else 9) * cin * cout_pad, dtype=dtype, device=w.device)
-    name = 'cf_pack_conv_weight' + ('_up2x' if up2x else '') + ('', '_bf16', '_f16')[code]
-    args = (L.ptr(w), cout, cin) + (() if up2x else (9,)) + (cout_pad, cin, L.ptr(packed, dtype=None), L.stream_ptr())
-    L.check(getattr(lib, name)(*args), name)
-    return PackedWeight(packed, b, cout, cin, 9, cout_pad, cin, bf16=code, up2x=bool(up2x))
+    packer = _pack_gemm_split if code == GSPLIT else _pack_winograd if code in _WINO else _pack_split if code == SPLIT else \
+        _pack_16_or_folded if (code or up2x) else _pack_plain
+    return packer(w, b, code, up2x, stride2)
 
 
 def pack_weight_cat(weights, biases):
@@ -520,6 +515,23 @@ def _counters(device, n):
         t = torch.zeros(max(n, 4096), dtype=torch.int32, device=device)   # every split-K launch leaves its counters at zero again
         _COUNTERS[key] = t
     return t
+
+
+def _roofline_kind(pw, io, stride, upsample, c0, in_nchw, out_nchw, out_pixels, split_k):
+    """The name bench.py's roofline leg books a conv2d launch under."""
+    kind = ('conv3x3_s2' if stride == 2 else ('conv_up2x' if upsample else ('conv3x3_wino' if pw.wino else 'conv3x3'))) if pw.taps == 9 else 'gemm1x1'
+    if pw.taps == 9 and stride == 1 and ((in_nchw and c0 <= 4) or (out_nchw and pw.cout <= 4)):
+        kind = 'conv3x3_io'   # the network's first / last conv: vector-ALU kernels, HBM-bound (conv3x3_few_cin / few_cout)
+    if pw.bf16:
+        kind += ('', '_bf16', '_f16', '_f16x2')[int(pw.bf16)]
+    if io == torch.bfloat16 and not pw.bf16:
+        kind += '_bf16io'     # fp32 operands on bf16 tensors (the 1x1 skips and the RGB head of the bf16 mode)
+    if pw.conv1:
+        kind = 'conv1x1_stream_f16x2'   # 1x1 on images through the split-half convolution kernel (HBM-bound), not the token GEMM
+    if pw.wino == 2:
+        return 'conv3x3_wino43_f16x2' if pw.bf16 else 'conv3x3_wino43'   # F(4x4,3x3) on split halves / on fp32 operands (cf_wf43.hip)
+    # the eight-wave 128-channel kernel (cf_wsplit.hip; the rule of cf_wsplit_covers)
+    return kind + ('_8w' if pw.wino and pw.bf16 and pw.cout % 128 == 0 and out_pixels >= 1024 and not split_k else '')
 
 
 def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale=None, shift=None,
@@ -644,20 +656,7 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     esz = x.element_size()
     nbytes = float(esz * (x.numel() + (0 if x2 is None else x2.numel()) + (0 if res is None else res.numel()) + (0 if sft_scale is None else sft_scale.numel()))
                    + 4 * pw.cout * cin * pw.taps + out.element_size() * out.numel())
-    kind = ('conv3x3_s2' if stride == 2 else ('conv_up2x' if upsample else ('conv3x3_wino' if pw.wino else 'conv3x3'))) \
-        if pw.taps == 9 else 'gemm1x1'
-    if pw.taps == 9 and stride == 1 and ((in_nchw and c0 <= 4) or (out_nchw and pw.cout <= 4)):
-        kind = 'conv3x3_io'   # the network's first / last conv: vector-ALU kernels, HBM-bound (conv3x3_few_cin / few_cout)
-    if pw.bf16:
-        kind += ('', '_bf16', '_f16', '_f16x2')[int(pw.bf16)]
-    if io == torch.bfloat16 and not pw.bf16:
-        kind += '_bf16io'     # fp32 operands on bf16 tensors (the 1x1 skips and the RGB head of the bf16 mode)
-    if pw.conv1:
-        kind = 'conv1x1_stream_f16x2'   # 1x1 on images through the split-half convolution kernel (HBM-bound), not the token GEMM
-    if pw.wino == 2:
-        kind = 'conv3x3_wino43_f16x2' if pw.bf16 else 'conv3x3_wino43'   # F(4x4,3x3) on split halves / on fp32 operands (cf_wf43.hip)
-    elif pw.wino and pw.bf16 and pw.cout % 128 == 0 and Ho * Wo >= 1024 and not split_k:
-        kind += '_8w'      # the eight-wave 128-channel kernel (cf_wsplit.hip; the rule of cf_wsplit_covers)
+    kind = _roofline_kind(pw, io, stride, upsample, c0, in_nchw, out_nchw, Ho * Wo, split_k)
     PROFILE.append((kind, flops, nbytes, e0, e1, (B, H, W, cin, pw.cout)))
     return out
 
