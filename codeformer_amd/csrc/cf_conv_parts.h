@@ -1,9 +1,25 @@
-// The tail that the convolution kernels behind cf_conv2d share (cf_igemm.hip, cf_split.hip, cf_winograd.hip, cf_wsplit.hip, cf_wf43.hip):
-// the swish of the GroupNorm prologue, the epilogue arithmetic on a quad of channels, the GroupNorm partials of the output, and -- host
-// side -- the descriptor fields every argument struct has and the prototypes by which the files call each other.
+// What the convolution kernels behind cf_conv2d share (cf_igemm.hip, cf_split.hip, cf_winograd.hip, cf_wsplit.hip, cf_wf43.hip; the token
+// GEMMs of cf_gemm_split.hip take the split-half product from here):
+//   head   the XCD-contiguous workgroup order, the range scale of an un-normalised input, the gather prologue on a value or a quad, the
+//          runtime -> compile-time dispatch of the prologue and of the epilogue triple, the three-MFMA split-half product;
+//   tail   the swish of the GroupNorm prologue, the epilogue arithmetic on a quad of channels, the GroupNorm partials of the output;
+//   host   the descriptor fields every argument struct has, the checks the launchers repeat, the prototypes by which the files call each other.
 // Pieces, all forceinline: a kernel keeps its own loops, staging and store order and calls these for the arithmetic, so that the order of
 // every addition is written down once.
+//
+// A site uses a piece only where the compiled function stayed instruction-identical to the one with the text written out
+// (tools/strip_experiment_macros.py --verify).  Sites that keep their own text, each with a comment naming the piece it spells out:
+//   cf_act_scales     cf_winograd.hip, cf_wsplit.hip, cf_split.hip (the helper changed the branch structure around the null test; it
+//                     serves cf_wf43.hip)
+//   cf_pro_apply4     cf_split.hip convert_mode;  cf_pro_apply: cf_igemm.hip store_A_mode (another swish: see cf_swish)
+//   cf_with_prologue  cf_split.hip, cf_igemm.hip;  cf_with_epilogue: cf_split.hip (device switches; the host ones all use the helpers)
+//   cf_mma3_f16x2     cf_split.hip `mma` (each of the three products is taken over all mi / ni tiles before the next, so consecutive
+//                     MFMAs go to different accumulators); cf_wf43.hip has other MFMA shapes and interleaves two positions
+//   cf_gn_partials    cf_winograd.hip, cf_split.hip, cf_wf43.hip;  cf_epi_*: the vector epilogue of cf_igemm.hip, cf_wf43.hip (pairs)
+// The halo index loop, the column pass and the nu-axis contraction that cf_winograd.hip and cf_wsplit.hip have in common are still two copies.
 #pragma once
+#include <type_traits>
+
 #include "cf_common.h"
 
 // ---- launchers and geometry queries of the kernel families (conv_dispatch / splitk_geometry in cf_igemm.hip call them) --------------------
@@ -44,11 +60,103 @@ inline void cf_fill_conv_args(A& a, const cf_conv_desc* d) {
   a.stats_out = d->stats_out;
 }
 
+// ---- host checks the launchers repeat --------------------------------------------------------------------------------------------------
+// Each launcher keeps the place of a check among its other checks (the first failing one decides the message) and, where the families
+// word a refusal differently, its text.
+inline bool cf_epi_is_quad_triple(const cf_conv_desc* d) {  // the epilogues cf_epi_apply knows
+  return d->epilogue == CF_EPI_NONE || d->epilogue == CF_EPI_RESIDUAL || d->epilogue == CF_EPI_SFT;
+}
+inline bool cf_dense_zero_pad(const cf_conv_desc* d) {  // dense NHWC tensors (no channel stride), zero padding
+  return d->pad_mode == CF_PAD_ZERO && (d->ld_in0 == 0 || d->ld_in0 == d->c0) && (d->ld_in1 == 0 || d->ld_in1 == d->c1) &&
+         (d->ld_out == 0 || d->ld_out == d->cout);
+}
+inline int cf_require_acc_scale(const cf_conv_desc* d, const char* family) {  // family: "cf_conv2d(f16x2)", ..
+  CF_REQUIRE(d->acc_scale > 0.f, "%s: acc_scale must be the inverse of the pack-time weight scale (got %g)", family, (double)d->acc_scale);
+  return CF_OK;
+}
+
+// ---- workgroup order -------------------------------------------------------------------------------------------------------------------
+// Workgroup b runs on XCD b % 8 (observed dispatch order; speed only, never correctness).  Give every XCD a contiguous run of tile ids
+// so neighbouring tiles -- which share halo rows / columns and the weight slabs -- hit the same L2.  Bijective for any grid size.
+__device__ __forceinline__ int cf_xcd_tile(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+
+// ---- runtime value -> template parameter -----------------------------------------------------------------------------------------------
+// f(std::integral_constant<int, P>{}) for the prologue (enum cf_prologue) / for the epilogue triple of cf_epi_apply; host and device.
+template <class F>
+__host__ __device__ __forceinline__ void cf_with_prologue(int prologue, F&& f) {
+  switch (prologue) {
+    case CF_PRO_AFFINE: f(std::integral_constant<int, CF_PRO_AFFINE>{}); break;
+    case CF_PRO_AFFINE_SWISH: f(std::integral_constant<int, CF_PRO_AFFINE_SWISH>{}); break;
+    case CF_PRO_LEAKY: f(std::integral_constant<int, CF_PRO_LEAKY>{}); break;
+    default: f(std::integral_constant<int, CF_PRO_NONE>{}); break;
+  }
+}
+template <class F>
+__host__ __device__ __forceinline__ void cf_with_epilogue(int epilogue, F&& f) {
+  switch (epilogue) {
+    case CF_EPI_RESIDUAL: f(std::integral_constant<int, CF_EPI_RESIDUAL>{}); break;
+    case CF_EPI_SFT: f(std::integral_constant<int, CF_EPI_SFT>{}); break;
+    default: f(std::integral_constant<int, CF_EPI_NONE>{}); break;
+  }
+}
+
 // ---- prologue --------------------------------------------------------------------------------------------------------------------------
 // x * sigmoid(x) on the hardware exp and the hardware reciprocal (v_exp_f32 / v_rcp_f32, ~1 ulp each): the GroupNorm-swish gather of the
 // split-half and Winograd kernels.  cf_igemm.hip keeps two other forms (__frcp_rn in its MFMA gather, a true division in the vector-ALU
 // first conv): the three differ in the last bits and are not interchangeable.
 __device__ __forceinline__ float cf_swish(float y) { return y * __builtin_amdgcn_rcpf(1.0f + __expf(-y)); }
+
+// Range scale of an un-normalised input of the 16-bit-operand kernels (cf_conv_desc.act_scale, [image][2] = (s, 1 / s), powers of two:
+// x * s and acc / s are exact); 1 when unused.  s02 is the LeakyReLU slope folded with the scale: fl(y * (0.2 s)) == fl(0.2 y) * s,
+// because s only moves the exponent.
+template <bool USE>
+__device__ __forceinline__ void cf_act_scales(const float* act_scale, int b, float& s, float& inv_s, float& s02) {
+  s = 1.f;
+  inv_s = 1.f;
+  if (USE && act_scale) {
+    s = act_scale[2 * b];
+    inv_s = act_scale[2 * b + 1];
+  }
+  s02 = 0.2f * s;
+}
+
+// The gather prologue on one value: GroupNorm apply (sc, sh), the same with swish, LeakyReLU(0.2), none.  SCALED: the kernel multiplies
+// an un-normalised input (LEAKY, NONE) by its range scale s (cf_act_scales); SCALED = false is the fp32 form -- no multiply for NONE.
+template <int PRO, bool SCALED>
+__device__ __forceinline__ float cf_pro_apply(float y, float sc, float sh, float s, float s02) {
+  if (PRO == CF_PRO_AFFINE) y = y * sc + sh;
+  if (PRO == CF_PRO_AFFINE_SWISH) {
+    y = y * sc + sh;
+    y = cf_swish(y);
+  }
+  if (PRO == CF_PRO_LEAKY) y = SCALED ? y * (y > 0.f ? s : s02) : (y > 0.f ? y : 0.2f * y);
+  if (SCALED && PRO == CF_PRO_NONE) y = y * s;
+  return y;
+}
+// ... on a quad of channels of one pixel.  Zero padding pads the conv INPUT, i.e. the post-activation tensor: an out-of-image value
+// (`valid` false; its load came from a clamped address) is an exact zero whatever the prologue would make of it.
+template <int PRO, bool SCALED>
+__device__ __forceinline__ f32x4 cf_pro_apply4(f32x4 v, f32x4 sc, f32x4 sh, float s, float s02, bool valid) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float y = cf_pro_apply<PRO, SCALED>(v[e], sc[e], sh[e], s, s02);
+    v[e] = valid ? y : 0.f;
+  }
+  return v;
+}
+
+// ---- split-half product ----------------------------------------------------------------------------------------------------------------
+// a * b with both operands as hi + lo IEEE halves (8 per lane: the 32x32x16 shape): lo*hi, then hi*lo, then hi*hi into one fp32
+// accumulator (the dropped lo*lo term is <= 2^-22 |a b|).  The order is part of every default-mode result.
+typedef _Float16 cf_f16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void cf_mma3_f16x2(f32x16& acc, f32x4 ah, f32x4 al, f32x4 bh, f32x4 bl) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cf_f16x8, al), __builtin_bit_cast(cf_f16x8, bh), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cf_f16x8, ah), __builtin_bit_cast(cf_f16x8, bl), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cf_f16x8, ah), __builtin_bit_cast(cf_f16x8, bh), acc, 0, 0, 0);
+}
 
 // ---- epilogue on a quad of channels ----------------------------------------------------------------------------------------------------
 // A thread owns four consecutive output channels of a pixel at element offset `off` (the same offset in res, sft_scale and out: dense

@@ -17,11 +17,9 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "cf_common.h"
+#include "cf_conv_parts.h"
 
 namespace {
-
-typedef _Float16 gs_f16x8 __attribute__((ext_vector_type(8)));
 
 struct GsArgs {
   const float* a;     // [M][K] dense tokens
@@ -92,9 +90,7 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(const GsArgs g) {
         ah[e] = hh;
         al[e] = ll;
       }
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gs_f16x8, al), __builtin_bit_cast(gs_f16x8, rb[BUF][s][0]), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gs_f16x8, ah), __builtin_bit_cast(gs_f16x8, rb[BUF][s][1]), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gs_f16x8, ah), __builtin_bit_cast(gs_f16x8, rb[BUF][s][0]), acc, 0, 0, 0);
+      cf_mma3_f16x2(acc, ah, al, rb[BUF][s][0], rb[BUF][s][1]);
     }
   };
 
@@ -230,11 +226,7 @@ __global__ __launch_bounds__(256) void gemm_split_tile_kernel(const GsArgs g) {
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gs_f16x8, al[mi]), __builtin_bit_cast(gs_f16x8, rb[BUF][s][ni][0]), acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gs_f16x8, ah[mi]), __builtin_bit_cast(gs_f16x8, rb[BUF][s][ni][1]), acc[mi][ni], 0, 0, 0);
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gs_f16x8, ah[mi]), __builtin_bit_cast(gs_f16x8, rb[BUF][s][ni][0]), acc[mi][ni], 0, 0, 0);
-        }
+        for (int ni = 0; ni < NI; ++ni) cf_mma3_f16x2(acc[mi][ni], ah[mi], al[mi], rb[BUF][s][ni][0], rb[BUF][s][ni][1]);
     }
   };
   using R0 = std::integral_constant<int, 0>;
@@ -372,11 +364,7 @@ __global__ __launch_bounds__(256, MI * NI == 1 ? 1 : 2) void gemm_split_chunk_ke
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) {
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gs_f16x8, al[mi]), __builtin_bit_cast(gs_f16x8, rb[s][ni][0]), acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gs_f16x8, ah[mi]), __builtin_bit_cast(gs_f16x8, rb[s][ni][1]), acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gs_f16x8, ah[mi]), __builtin_bit_cast(gs_f16x8, rb[s][ni][0]), acc[mi][ni], 0, 0, 0);
-          }
+          for (int ni = 0; ni < NI; ++ni) cf_mma3_f16x2(acc[mi][ni], ah[mi], al[mi], rb[s][ni][0], rb[s][ni][1]);
       }
     }
 #pragma unroll

@@ -136,13 +136,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
   const int half = lane >> 5;
   const int l31 = lane & 31;
 
-  // Workgroup b runs on XCD b % 8 (observed dispatch order; speed only, never correctness).  Give every XCD a contiguous
-  // run of tile ids so neighbouring tiles -- which share halo rows/columns and the weight slabs -- hit the same L2.
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;  // bijective for any grid size
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  int bid = cf_xcd_tile(blockIdx.x, gridDim.x);
   [[maybe_unused]] int split = 0, sk_tile = 0;
   if constexpr (SK) {
     split = bid % a.nsplit;  // the splits of one tile are neighbours in the tile order
@@ -295,7 +289,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
           v[u] = ra[j * AV + u];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            float y = v[u][e];
+            float y = v[u][e];  // (cf_pro_apply<PRO, false> of cf_conv_parts.h written out: this gather has its own swish)
             if (PRO == CF_PRO_AFFINE) y = y * sc[u][e] + sh[u][e];
             if (PRO == CF_PRO_AFFINE_SWISH) {
               y = y * sc[u][e] + sh[u][e];
@@ -335,7 +329,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
     }
   };
   auto store_A = [&](int buf, const f32x4(&ra)[C::APT * AV], int chunk) {
-    switch (a.prologue) {
+    switch (a.prologue) {  // (cf_with_prologue of cf_conv_parts.h written out: through the helper three 1x1 instantiations were scheduled differently)
       case CF_PRO_AFFINE: store_A_mode(buf, ra, chunk, std::integral_constant<int, CF_PRO_AFFINE>{}); break;
       case CF_PRO_AFFINE_SWISH: store_A_mode(buf, ra, chunk, std::integral_constant<int, CF_PRO_AFFINE_SWISH>{}); break;
       case CF_PRO_LEAKY: store_A_mode(buf, ra, chunk, std::integral_constant<int, CF_PRO_LEAKY>{}); break;

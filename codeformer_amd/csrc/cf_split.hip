@@ -155,11 +155,7 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
   const int half = lane >> 5;
   const int l31 = lane & 31;
 
-  int bid = blockIdx.x;
-  {  // XCD-contiguous tile order (see cf_igemm.hip): neighbouring tiles share halos and weight slabs in one L2
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int bid = cf_xcd_tile(blockIdx.x, gridDim.x);
   const int nt = bid % a.ntn;
   const int mt = bid / a.ntn;
   const int n0 = nt * C::BN;
@@ -206,13 +202,14 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
   }
 
   const bool affine = a.prologue == CF_PRO_AFFINE || a.prologue == CF_PRO_AFFINE_SWISH;
-  // range scale of an un-normalised input (cf_conv_desc.act_scale): powers of two, x * s and acc / s are exact; 1 when unused
+  // cf_act_scales (cf_conv_parts.h) written out: the prologue is a runtime value here, and behind a runtime flag the helper compiled to
+  // another branch structure
   float act_s = 1.f, act_is = 1.f;
   if (!affine && a.act_scale) {
     act_s = a.act_scale[2 * b];
     act_is = a.act_scale[2 * b + 1];
   }
-  const float act_s02 = 0.2f * act_s;  // LeakyReLU slope folded with the scale: fl(y * (0.2 s)) == fl(0.2 y) * s
+  const float act_s02 = 0.2f * act_s;
   const float* const tab_sc = affine ? a.pro_scale + (size_t)b * a.cin : a.in0;  // (any valid address when unused)
   const float* const tab_sh = affine ? a.pro_shift + (size_t)b * a.cin : a.in0;
 
@@ -255,7 +252,7 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
 #pragma unroll
     for (int j = 0; j < C::APT; ++j) {
       const bool valid = pix[j] >= 0;
-      float y[8];
+      float y[8];  // (cf_pro_apply4<PRO, true> of cf_conv_parts.h written out, with the other head helpers of this kernel)
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -283,7 +280,7 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
     }
   };
   auto convert = [&](ASet& r) __attribute__((always_inline)) {
-    switch (a.prologue) {
+    switch (a.prologue) {  // (cf_with_prologue of cf_conv_parts.h written out, as cf_with_epilogue below: through the helpers five instantiations lost or moved a wait)
       case CF_PRO_AFFINE: convert_mode(r, std::integral_constant<int, CF_PRO_AFFINE>{}); break;
       case CF_PRO_AFFINE_SWISH: convert_mode(r, std::integral_constant<int, CF_PRO_AFFINE_SWISH>{}); break;
       case CF_PRO_LEAKY: convert_mode(r, std::integral_constant<int, CF_PRO_LEAKY>{}); break;
@@ -363,7 +360,8 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
       f.bl[ni] = *reinterpret_cast<const f32x4*>(Bs + slot * C::B_SLOT + b_adr[2 + kk] + ni * (32 * 32));
     }
   };
-  // lo*hi + hi*lo + hi*hi; consecutive MFMAs go to different accumulators
+  // cf_mma3_f16x2 (cf_conv_parts.h) written out -- lo*hi + hi*lo + hi*hi -- with each product taken over all mi / ni tiles before the next:
+  // consecutive MFMAs go to different accumulators
   auto mma = [&](const Frags& f) __attribute__((always_inline)) {
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
@@ -737,13 +735,9 @@ int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query)
   constexpr int TH = SP_WM * 4;
   const int gh = s2 ? d->hin / 2 : d->hin, gw = s2 ? d->win / 2 : d->win;  // the grid the tiles live on
   CF_REQUIRE(gh % TH == 0 && gw % 16 == 0, "cf_conv2d(f16x2): %dx%d %s is not a multiple of the %dx16 tile", gh, gw, s2 ? "output" : "input", TH);
-  CF_REQUIRE(d->epilogue == CF_EPI_NONE || d->epilogue == CF_EPI_RESIDUAL || d->epilogue == CF_EPI_SFT,
-             "cf_conv2d(f16x2): epilogues are none / residual / SFT");
-  CF_REQUIRE(d->pad_mode == CF_PAD_ZERO && (d->ld_in0 == 0 || d->ld_in0 == d->c0) && (d->ld_in1 == 0 || d->ld_in1 == d->c1) &&
-                 (d->ld_out == 0 || d->ld_out == d->cout),
-             "cf_conv2d(f16x2): dense tensors with zero padding only");
-  CF_REQUIRE(d->acc_scale > 0.f, "cf_conv2d(f16x2): acc_scale must be the inverse of the pack-time weight scale (got %g)",
-             (double)d->acc_scale);
+  CF_REQUIRE(cf_epi_is_quad_triple(d), "cf_conv2d(f16x2): epilogues are none / residual / SFT");
+  CF_REQUIRE(cf_dense_zero_pad(d), "cf_conv2d(f16x2): dense tensors with zero padding only");
+  if (const int e = cf_require_acc_scale(d, "cf_conv2d(f16x2)")) return e;
   SplitArgs a;
   cf_fill_conv_args(a, d);
   a.hin = d->hin;

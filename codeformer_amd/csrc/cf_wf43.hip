@@ -183,11 +183,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave-uniform by construction: keeps what depends on it in SGPRs)
 
-  int bid = blockIdx.x;
-  {  // XCD-contiguous tile order (see cf_igemm.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int bid = cf_xcd_tile(blockIdx.x, gridDim.x);
   const int ntile = bid % a.ntn;
   const int mt = bid / a.ntn;
   const int n0 = ntile * F4_BN;
@@ -205,12 +201,8 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
       tab[TABN + i] = a.pro_shift[(size_t)b * a.cin + i];
     }
   }
-  float act_s = 1.f, act_is = 1.f;
-  if (!affine && a.act_scale) {
-    act_s = a.act_scale[2 * b];
-    act_is = a.act_scale[2 * b + 1];
-  }
-  const float act_s02 = 0.2f * act_s;  // LeakyReLU slope folded with the scale: fl(y * (0.2 s)) == fl(0.2 y) * s
+  float act_s, act_is, act_s02;
+  cf_act_scales<!affine>(a.act_scale, b, act_s, act_is, act_s02);
 
   // ---- gather (waves 4..7; waves 0..3 spend the same interval on the input transform): item j of a thread is float4 #k4 of halo pixel
   //      p = u + PSTEP j, u = (tid - 256) >> 2.  Everything per item -- the pixel's offset from the patch origin, whether it lies inside the
@@ -280,19 +272,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
       unsigned rel;
       bool valid;
       item(slot, j, rel, valid);
-      f32x4 v = HALVES && j >= RAN ? rb[j % RAN] : ra[j % RAN];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float y = v[e];
-        if (PRO == CF_PRO_AFFINE) y = y * sc[e] + sh[e];
-        if (PRO == CF_PRO_AFFINE_SWISH) {
-          y = y * sc[e] + sh[e];
-          y = cf_swish(y);
-        }
-        if (PRO == CF_PRO_LEAKY) y = y * (y > 0.f ? act_s : act_s02);
-        if (PRO == CF_PRO_NONE) y = y * act_s;
-        v[e] = valid ? y : 0.f;
-      }
+      const f32x4 v = cf_pro_apply4<PRO, true>(HALVES && j >= RAN ? rb[j % RAN] : ra[j % RAN], sc, sh, act_s, act_s02, valid);
       // the last item covers pixels up to 383 of which 0..323 exist (+ four spare slots); the others would land past the buffer: skipped
       if (j < F4_APT - 1 || slot + (unsigned)(PSTEP * j) < (unsigned)F4_NPIX) *reinterpret_cast<f32x4*>(pb + j * (PSTEP * SLOTB)) = v;
     }
@@ -993,7 +973,8 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
   CF_REQUIRE(!d->upsample || (f32 && d->prologue == CF_PRO_NONE && d->epilogue == CF_EPI_NONE && d->c1 == 0 && d->cout % 128 == 0 && d->c0 % 32 == 0 &&
                               f4_k32_enabled()),
              "cf_conv2d(winograd 2, upsample): fp32 operands, one input with c0 %% 32 == 0, cout %% 128 == 0, no prologue / epilogue operand");
-  CF_REQUIRE(f32 || d->acc_scale > 0.f, "cf_conv2d(winograd 2): acc_scale must be the inverse of the pack-time weight scale (got %g)", (double)d->acc_scale);
+  if (!f32)
+    if (const int e = cf_require_acc_scale(d, "cf_conv2d(winograd 2)")) return e;
   CF_REQUIRE(!f32 || !d->act_scale, "cf_conv2d(winograd 2): fp32 operands take no activation range scale");
   CF_REQUIRE(d->hout % F4_TH == 0 && d->wout % F4_TW == 0, "cf_conv2d(winograd 2): needs an output of %dx%d multiples (got %dx%d)", F4_TH,
              F4_TW, d->hout, d->wout);
@@ -1004,11 +985,8 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
              "cf_conv2d(winograd 2): an image of a tensor must stay below 2^31 bytes (%dx%d, %d / %d / %d channels)", d->hout, d->wout, d->c0, d->c1, d->cout);
   const int tab_max = (d->cout % 128 == 0 && (d->c0 + d->c1) % 32 == 0 && f4_k32_enabled()) ? F4_TAB_32 : F4_TAB;   // (the 32-channel-slab form holds 512 GroupNorm rows)
   CF_REQUIRE(d->c0 + d->c1 <= tab_max, "cf_conv2d(winograd 2): at most %d input channels in this form (got %d)", tab_max, d->c0 + d->c1);
-  CF_REQUIRE(d->epilogue == CF_EPI_NONE || d->epilogue == CF_EPI_RESIDUAL || d->epilogue == CF_EPI_SFT,
-             "cf_conv2d(winograd 2): epilogues are none / residual / SFT");
-  CF_REQUIRE(d->pad_mode == CF_PAD_ZERO && (d->ld_in0 == 0 || d->ld_in0 == d->c0) && (d->ld_in1 == 0 || d->ld_in1 == d->c1) &&
-                 (d->ld_out == 0 || d->ld_out == d->cout) && d->split_k < 1,
-             "cf_conv2d(winograd 2): reads / writes dense tensors with zero padding, no split_k");
+  CF_REQUIRE(cf_epi_is_quad_triple(d), "cf_conv2d(winograd 2): epilogues are none / residual / SFT");
+  CF_REQUIRE(cf_dense_zero_pad(d) && d->split_k < 1, "cf_conv2d(winograd 2): reads / writes dense tensors with zero padding, no split_k");
   CF_REQUIRE(d->stats_cpg == 0 || (d->stats_cpg <= 64 && (d->stats_cpg & (d->stats_cpg - 1)) == 0 && d->stats_cpg >= 2),
              "cf_conv2d(winograd 2): stats_cpg %d (a power of two, 2..64)", d->stats_cpg);
   F4Args a;
@@ -1034,41 +1012,29 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
   const size_t lds = (k32 ? F4_LDS_FLOATS_32 : wide ? F4_LDS_FLOATS_16 : F4_LDS_FLOATS) * sizeof(float);
   const dim3 grid(a.tiles_per_img * d->batch * a.ntn), block(wide ? 1024 : 512);
   // (cf_device_init sets the dynamic-LDS attribute of every instantiation on each device)
-#define F4_LAUNCH_OP(P, E, O)                                                                                                 \
-  do {                                                                                                                        \
-    CF_LDS_ATTR((wf43_kernel<P, E, 8, 16, O>), F4_LDS_FLOATS * sizeof(float));                                            \
-    CF_LDS_ATTR((wf43_kernel<P, E, 16, 16, O>), F4_LDS_FLOATS_16 * sizeof(float));                                            \
-    CF_LDS_ATTR((wf43_kernel<P, E, 16, 32, O>), F4_LDS_FLOATS_32 * sizeof(float));                                            \
-    if (k32) hipLaunchKernelGGL((wf43_kernel<P, E, 16, 32, O>), grid, block, lds, stream, a);                                 \
-    else if (wide) hipLaunchKernelGGL((wf43_kernel<P, E, 16, 16, O>), grid, block, lds, stream, a);                           \
-    else hipLaunchKernelGGL((wf43_kernel<P, E, 8, 16, O>), grid, block, lds, stream, a);                                      \
-  } while (0)
-#define F4_LAUNCH(P, E)                  \
-  do {                                   \
-    if (f32) F4_LAUNCH_OP(P, E, true);   \
-    else F4_LAUNCH_OP(P, E, false);      \
-  } while (0)
-#define F4_LAUNCH_EPI(P)                                                           \
-  do {                                                                             \
-    if (d->epilogue == CF_EPI_RESIDUAL) F4_LAUNCH(P, CF_EPI_RESIDUAL);             \
-    else if (d->epilogue == CF_EPI_SFT) F4_LAUNCH(P, CF_EPI_SFT);                  \
-    else F4_LAUNCH(P, CF_EPI_NONE);                                                \
-  } while (0)
   if (d->upsample) {
     CF_LDS_ATTR((wf43_kernel<CF_PRO_NONE, CF_EPI_NONE, 16, 32, true, true>), F4_LDS_FLOATS_32 * sizeof(float));
     hipLaunchKernelGGL((wf43_kernel<CF_PRO_NONE, CF_EPI_NONE, 16, 32, true, true>), grid, block, lds, stream, a);
     CF_CHECK_LAUNCH("cf_conv2d(winograd F(4,3) fp32, upsampling gather)");
     return CF_OK;
   }
-  switch (d->prologue) {
-    case CF_PRO_AFFINE: F4_LAUNCH_EPI(CF_PRO_AFFINE); break;
-    case CF_PRO_AFFINE_SWISH: F4_LAUNCH_EPI(CF_PRO_AFFINE_SWISH); break;
-    case CF_PRO_LEAKY: F4_LAUNCH_EPI(CF_PRO_LEAKY); break;
-    default: F4_LAUNCH_EPI(CF_PRO_NONE); break;
-  }
-#undef F4_LAUNCH_EPI
-#undef F4_LAUNCH
-#undef F4_LAUNCH_OP
+  // one (PRO, EPI, operand) -> its three forms, of which the layer's shape picks one
+  auto launch = [&](auto pro, auto epi, auto op) {
+    constexpr int P = decltype(pro)::value, E = decltype(epi)::value;
+    constexpr bool O = decltype(op)::value;
+    CF_LDS_ATTR((wf43_kernel<P, E, 8, 16, O>), F4_LDS_FLOATS * sizeof(float));
+    CF_LDS_ATTR((wf43_kernel<P, E, 16, 16, O>), F4_LDS_FLOATS_16 * sizeof(float));
+    CF_LDS_ATTR((wf43_kernel<P, E, 16, 32, O>), F4_LDS_FLOATS_32 * sizeof(float));
+    if (k32) hipLaunchKernelGGL((wf43_kernel<P, E, 16, 32, O>), grid, block, lds, stream, a);
+    else if (wide) hipLaunchKernelGGL((wf43_kernel<P, E, 16, 16, O>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((wf43_kernel<P, E, 8, 16, O>), grid, block, lds, stream, a);
+  };
+  cf_with_prologue(d->prologue, [&](auto pro) {
+    cf_with_epilogue(d->epilogue, [&](auto epi) {
+      if (f32) launch(pro, epi, std::true_type{});
+      else launch(pro, epi, std::false_type{});
+    });
+  });
   CF_CHECK_LAUNCH("cf_conv2d(winograd F(4,3) f16x2)");
   return CF_OK;
 }

@@ -106,8 +106,6 @@ __device__ __forceinline__ f32x4 v4sub(f32x4 a, f32x4 b) { return a - b; }
 // once by the input transform, which writes it to LDS in operand format -- and
 // hi*hi + lo*hi + hi*lo accumulated in fp32: 3 MFMAs of 8 passes per 16-channel slab and MFMA tile instead of 8 of 16 passes.
 // Gather, transform, epilogue and the split-K protocol are shared with the fp32 form.
-typedef _Float16 wg_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 wg_f16x2 __attribute__((ext_vector_type(2)));
 
 template <bool SK, bool H2>
 __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional_t<SK, WinoArgsSK, WinoArgs> a) {
@@ -126,11 +124,7 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
   float* const patch = smem;
   float* const V = patch + WG_PATCH_FLOATS;
 
-  int bid = blockIdx.x;
-  {  // XCD-contiguous tile order (see cf_igemm.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  int bid = cf_xcd_tile(blockIdx.x, gridDim.x);
   [[maybe_unused]] int split = 0, sk_tile = 0;
   if constexpr (SK) {
     split = bid % a.nsplit;
@@ -172,13 +166,13 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
   // The GroupNorm scale / shift rows of the slab travel with the activations (fetched a slab ahead): loading them inside
   // store_patch put an s_waitcnt vmcnt(0) there, which also drained the weight fragments requested just before.
   const bool affine = a.prologue == CF_PRO_AFFINE || a.prologue == CF_PRO_AFFINE_SWISH;
-  // H2: range scale of an un-normalised input (cf_conv_desc.act_scale): powers of two, x * s and acc / s are exact; 1 when unused
+  // cf_act_scales (cf_conv_parts.h) written out: called as the helper, the two H2 instantiations got another branch structure
   float act_s = 1.f, act_is = 1.f;
   if (H2 && !affine && a.act_scale) {
     act_s = a.act_scale[2 * b];
     act_is = a.act_scale[2 * b + 1];
   }
-  const float act_s02 = 0.2f * act_s;  // LeakyReLU slope folded with the scale: fl(y * (0.2 s)) == fl(0.2 y) * s
+  const float act_s02 = 0.2f * act_s;
   const float* const tab_sc = affine ? a.pro_scale + (size_t)b * a.cin : a.weight;  // (any valid address when unused)
   const float* const tab_sh = affine ? a.pro_shift + (size_t)b * a.cin : a.weight;
   f32x4 rsc, rsh;
@@ -203,32 +197,11 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
 #pragma unroll
     for (int j = 0; j < APT; ++j) {
       const int p = (gtid >> 2) + (GT / 4) * j;  // (p >= 180: padding rows of the patch buffer, written as zeros -- no branch)
-      {
-        const bool valid = pix[j] >= 0;
-        f32x4 v = ra[j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float y = v[e];
-          if (PRO == CF_PRO_AFFINE) y = y * sc[e] + sh[e];
-          if (PRO == CF_PRO_AFFINE_SWISH) {
-            y = y * sc[e] + sh[e];
-            y = cf_swish(y);
-          }
-          if (PRO == CF_PRO_LEAKY) y = H2 ? y * (y > 0.f ? act_s : act_s02) : (y > 0.f ? y : 0.2f * y);
-          if (H2 && PRO == CF_PRO_NONE) y = y * act_s;
-          v[e] = valid ? y : 0.f;
-        }
-        *reinterpret_cast<f32x4*>(patch + p * CF_LDK + k4 * 4) = v;
-      }
+      *reinterpret_cast<f32x4*>(patch + p * CF_LDK + k4 * 4) = cf_pro_apply4<PRO, H2>(ra[j], sc, sh, act_s, act_s02, pix[j] >= 0);
     }
   };
   auto store_patch = [&](const f32x4(&ra)[APT], int chunk) {
-    switch (a.prologue) {
-      case CF_PRO_AFFINE: store_patch_mode(ra, chunk, std::integral_constant<int, CF_PRO_AFFINE>{}); break;
-      case CF_PRO_AFFINE_SWISH: store_patch_mode(ra, chunk, std::integral_constant<int, CF_PRO_AFFINE_SWISH>{}); break;
-      case CF_PRO_LEAKY: store_patch_mode(ra, chunk, std::integral_constant<int, CF_PRO_LEAKY>{}); break;
-      default: store_patch_mode(ra, chunk, std::integral_constant<int, CF_PRO_NONE>{}); break;
-    }
+    cf_with_prologue(a.prologue, [&](auto mode) { store_patch_mode(ra, chunk, mode); });
   };
   // input transform: item -> (tile, channel quad, xi row): 8 ds_read_b128, 8 vector adds, 4 ds_write_b128; 2 items per thread
   auto transform = [&]() {
@@ -305,14 +278,7 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
       const f32x4 ah = *reinterpret_cast<const f32x4*>(alane + nu * WG_PS);      // 8 hi halves
       const f32x4 al = *reinterpret_cast<const f32x4*>(alane + nu * WG_PS + 8);  // 8 lo halves
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
-        acc[nu][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wg_f16x8, al), __builtin_bit_cast(wg_f16x8, bq[nu][ni][0]),
-                                                             acc[nu][ni], 0, 0, 0);
-        acc[nu][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wg_f16x8, ah), __builtin_bit_cast(wg_f16x8, bq[nu][ni][1]),
-                                                             acc[nu][ni], 0, 0, 0);
-        acc[nu][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wg_f16x8, ah), __builtin_bit_cast(wg_f16x8, bq[nu][ni][0]),
-                                                             acc[nu][ni], 0, 0, 0);
-      }
+      for (int ni = 0; ni < NI; ++ni) cf_mma3_f16x2(acc[nu][ni], ah, al, bq[nu][ni][0], bq[nu][ni][1]);
     } else {
       f32x4 aq[2];
 #pragma unroll
@@ -634,17 +600,14 @@ int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_que
   const bool h1 = d->bf16_mfma == CF_OPERAND_F16 || d->bf16_mfma == CF_OPERAND_BF16;  // single 16-bit operands: the eight-wave kernel only
   CF_REQUIRE(!h1 || cf_wsplit_covers(d), "cf_conv2d(winograd, single 16-bit operands): needs cout %% 128 == 0 and at least 32x32 pixels per image");
   const bool h2 = d->bf16_mfma == CF_OPERAND_F16X2 || h1;
-  CF_REQUIRE(!h2 || d->acc_scale > 0.f, "cf_conv2d(winograd, f16x2): acc_scale must be the inverse of the pack-time weight scale (got %g)",
-             (double)d->acc_scale);
+  if (h2)
+    if (const int e = cf_require_acc_scale(d, "cf_conv2d(winograd, f16x2)")) return e;
   CF_REQUIRE(d->hout % WG_TH == 0 && d->wout % WG_TW == 0, "cf_conv2d: winograd needs an output of %dx%d multiples (got %dx%d)",
              WG_TH, WG_TW, d->hout, d->wout);
   CF_REQUIRE(d->cout % 64 == 0 && d->cout_pad == d->cout, "cf_conv2d: winograd needs cout == cout_pad, a multiple of 64 (got %d / %d)", d->cout,
              d->cout_pad);
-  CF_REQUIRE(d->epilogue == CF_EPI_NONE || d->epilogue == CF_EPI_RESIDUAL || d->epilogue == CF_EPI_SFT,
-             "cf_conv2d: winograd epilogues are none / residual / SFT");
-  CF_REQUIRE(d->pad_mode == CF_PAD_ZERO && (d->ld_in0 == 0 || d->ld_in0 == d->c0) && (d->ld_in1 == 0 || d->ld_in1 == d->c1) &&
-                 (d->ld_out == 0 || d->ld_out == d->cout),
-             "cf_conv2d: winograd reads / writes dense tensors with zero padding");
+  CF_REQUIRE(cf_epi_is_quad_triple(d), "cf_conv2d: winograd epilogues are none / residual / SFT");
+  CF_REQUIRE(cf_dense_zero_pad(d), "cf_conv2d: winograd reads / writes dense tensors with zero padding");
   if (h2 && cf_wsplit_covers(d)) return cf_wsplit_launch(d, stream, parts_query);
   CF_REQUIRE(!h1, "cf_conv2d(winograd, single 16-bit operands): not covered");
   WinoArgs a;

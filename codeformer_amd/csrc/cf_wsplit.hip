@@ -100,11 +100,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wsplit_kernel(const WsArgs a) {
   const int half = lane >> 5;
   const int l31 = lane & 31;
 
-  int bid = blockIdx.x;
-  {  // XCD-contiguous tile order (see cf_igemm.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int bid = cf_xcd_tile(blockIdx.x, gridDim.x);
   const int nt = bid % a.ntn;
   const int mt = bid / a.ntn;
   const int n0 = nt * WS_BN + nh * 64;  // first output channel of this wave's half
@@ -132,13 +128,13 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wsplit_kernel(const WsArgs a) {
     pix[j] = v;
   }
   constexpr bool affine = PRO == CF_PRO_AFFINE || PRO == CF_PRO_AFFINE_SWISH;
-  // range scale of an un-normalised input (cf_conv_desc.act_scale): powers of two, so x * s and acc / s are exact; 1 when unused
+  // cf_act_scales (cf_conv_parts.h) written out: called as the helper, the branch on the null pointer came out with the other polarity
   float act_s = 1.f, act_is = 1.f;
   if (!affine && a.act_scale) {
     act_s = a.act_scale[2 * b];
     act_is = a.act_scale[2 * b + 1];
   }
-  const float act_s02 = 0.2f * act_s;  // LeakyReLU slope folded with the scale: fl(y * (0.2 s)) == fl(0.2 y) * s
+  const float act_s02 = 0.2f * act_s;
   const float* const tab_sc = affine ? a.pro_scale + (size_t)b * a.cin : a.weight;  // (any valid address when unused)
   const float* const tab_sh = affine ? a.pro_shift + (size_t)b * a.cin : a.weight;
   f32x4 rsc, rsh;
@@ -164,23 +160,10 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wsplit_kernel(const WsArgs a) {
 #pragma unroll
     for (int j = 0; j < APT; ++j) {
       const int p = (tid >> 2) + 128 * j;  // (p >= 180: padding rows of the patch buffer, written as zeros -- no branch)
-      const bool valid = pix[j] >= 0;
       f32x4 v;
       if constexpr (BIO) v = cf_bf16x4_widen(ra[j]);
       else v = ra[j];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float y = v[e];
-        if (PRO == CF_PRO_AFFINE) y = y * sc[e] + sh[e];
-        if (PRO == CF_PRO_AFFINE_SWISH) {
-          y = y * sc[e] + sh[e];
-          y = cf_swish(y);
-        }
-        if (PRO == CF_PRO_LEAKY) y = y * (y > 0.f ? act_s : act_s02);
-        if (PRO == CF_PRO_NONE) y = y * act_s;
-        v[e] = valid ? y : 0.f;
-      }
-      *reinterpret_cast<f32x4*>(patch + p * CF_LDK + k4 * 4) = v;
+      *reinterpret_cast<f32x4*>(patch + p * CF_LDK + k4 * 4) = cf_pro_apply4<PRO, true>(v, sc, sh, act_s, act_s02, pix[j] >= 0);
     }
   };
 
@@ -274,14 +257,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wsplit_kernel(const WsArgs a) {
     } else {
       const f32x4 ah = va[nu & 1][0], al = va[nu & 1][NPART - 1];
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
-        acc[nu][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ws_f16x8, al), __builtin_bit_cast(ws_f16x8, bq[nu][ni][0]),
-                                                             acc[nu][ni], 0, 0, 0);
-        acc[nu][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ws_f16x8, ah), __builtin_bit_cast(ws_f16x8, bq[nu][ni][NPART - 1]),
-                                                             acc[nu][ni], 0, 0, 0);
-        acc[nu][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ws_f16x8, ah), __builtin_bit_cast(ws_f16x8, bq[nu][ni][0]),
-                                                             acc[nu][ni], 0, 0, 0);
-      }
+      for (int ni = 0; ni < NI; ++ni) cf_mma3_f16x2(acc[nu][ni], ah, al, bq[nu][ni][0], bq[nu][ni][NPART - 1]);
     }
   };
   auto mma_stage = [&](const float* V, int next_chunk) __attribute__((always_inline)) {
@@ -458,12 +434,7 @@ int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query
       CF_LDS_ATTR(kern, lds);
       hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
     };
-    switch (d->prologue) {
-      case CF_PRO_AFFINE: go(std::integral_constant<int, CF_PRO_AFFINE>{}); break;
-      case CF_PRO_AFFINE_SWISH: go(std::integral_constant<int, CF_PRO_AFFINE_SWISH>{}); break;
-      case CF_PRO_LEAKY: go(std::integral_constant<int, CF_PRO_LEAKY>{}); break;
-      default: go(std::integral_constant<int, CF_PRO_NONE>{}); break;
-    }
+    cf_with_prologue(d->prologue, go);
   };
   CF_REQUIRE(!d->io_bf16 || d->bf16_mfma == CF_OPERAND_BF16, "cf_conv2d(winograd, 8 waves): bf16 tensors (io_bf16) go with CF_OPERAND_BF16 operands");
   if (d->bf16_mfma == CF_OPERAND_F16) launch_op(std::integral_constant<int, CF_OPERAND_F16>{}, std::false_type{});

@@ -82,6 +82,24 @@ ROWS = [
     ('route: streaming 1x1 writes no statistics', D(64, 64, 64, 64, 64, taps=1, bf16_mfma=3, acc_scale=1.0), 'cf_conv2d(1x1, f16x2): no statistics epilogue'),
     ('bad operand format', D(64, 64, 64, 64, 64, bf16_mfma=7), 'bad operand format 7'),
     ('winograd must be', D(64, 64, 64, 64, 64, winograd=3), 'winograd must be 0, 1 (F(2x2,3x3)) or 2 (F(4x4,3x3)), got 3'),
+    # the checks the four launchers share (dense tensors, zero padding, epilogue triple, acc_scale), per family: answers of the commit
+    # before the launchers took them from cf_conv_parts.h
+    ('F(2,3) fp32: channel stride on the output', D(32, 32, 64, 64, 64, winograd=1, ld_out=192), 'cf_conv2d: winograd reads / writes dense tensors with zero padding'),
+    ('F(2,3) fp32: reflect padding', D(32, 32, 64, 64, 64, winograd=1, pad_mode=1), 'cf_conv2d: winograd reads / writes dense tensors with zero padding'),
+    ('F(2,3) fp32: LEAKY epilogue', D(32, 32, 64, 64, 64, winograd=1, epilogue=4), 'cf_conv2d: winograd epilogues are none / residual / SFT'),
+    ('F(2,3) fp32: acc_scale 0', D(32, 32, 64, 64, 64, winograd=1, acc_scale=0.0), 32),
+    ('F(2,3) split-half, eight waves: channel stride on the output', D(32, 32, 64, 128, 128, bf16_mfma=3, winograd=1, stats_cpg=4, acc_scale=1.0, ld_out=192), 'cf_conv2d: winograd reads / writes dense tensors with zero padding'),
+    ('F(2,3) split-half, eight waves: reflect padding', D(32, 32, 64, 128, 128, bf16_mfma=3, winograd=1, stats_cpg=4, acc_scale=1.0, pad_mode=1), 'cf_conv2d: winograd reads / writes dense tensors with zero padding'),
+    ('F(2,3) split-half, eight waves: LEAKY epilogue', D(32, 32, 64, 128, 128, bf16_mfma=3, winograd=1, stats_cpg=4, acc_scale=1.0, epilogue=4), 'cf_conv2d: winograd epilogues are none / residual / SFT'),
+    ('F(2,3) split-half, eight waves: acc_scale 0', D(32, 32, 64, 128, 128, bf16_mfma=3, winograd=1, stats_cpg=4, acc_scale=0.0), 'cf_conv2d(winograd, f16x2): acc_scale must be the inverse of the pack-time weight scale (got 0)'),
+    ('F(4,3) split-half: channel stride on the output', D(32, 32, 64, 64, 64, bf16_mfma=3, winograd=2, acc_scale=1.0, ld_out=192), 'cf_conv2d(winograd 2): reads / writes dense tensors with zero padding, no split_k'),
+    ('F(4,3) split-half: reflect padding', D(32, 32, 64, 64, 64, bf16_mfma=3, winograd=2, acc_scale=1.0, pad_mode=1), 'cf_conv2d(winograd 2): reads / writes dense tensors with zero padding, no split_k'),
+    ('F(4,3) split-half: LEAKY epilogue', D(32, 32, 64, 64, 64, bf16_mfma=3, winograd=2, acc_scale=1.0, epilogue=4), 'cf_conv2d(winograd 2): epilogues are none / residual / SFT'),
+    ('F(4,3) split-half: acc_scale 0', D(32, 32, 64, 64, 64, bf16_mfma=3, winograd=2, acc_scale=0.0), 'cf_conv2d(winograd 2): acc_scale must be the inverse of the pack-time weight scale (got 0)'),
+    ('split-half direct: channel stride on the output', D(64, 64, 64, 64, 64, bf16_mfma=3, acc_scale=1.0, ld_out=192), 'cf_conv2d(f16x2): dense tensors with zero padding only'),
+    ('split-half direct: reflect padding', D(64, 64, 64, 64, 64, bf16_mfma=3, acc_scale=1.0, pad_mode=1), 'cf_conv2d(f16x2): dense tensors with zero padding only'),
+    ('split-half direct: LEAKY epilogue', D(64, 64, 64, 64, 64, bf16_mfma=3, acc_scale=1.0, epilogue=4), 'cf_conv2d(f16x2): epilogues are none / residual / SFT'),
+    ('split-half direct: acc_scale 0', D(64, 64, 64, 64, 64, bf16_mfma=3, acc_scale=0.0), 'cf_conv2d(f16x2): acc_scale must be the inverse of the pack-time weight scale (got 0)'),
 ]
 
 
@@ -92,7 +110,7 @@ def native():
 
 
 def test_table_is_within_its_size():
-    assert 40 <= len(ROWS) <= 60 and len({r[0] for r in ROWS}) == len(ROWS)
+    assert 40 <= len(ROWS) <= 76 and len({r[0] for r in ROWS}) == len(ROWS)
 
 
 @pytest.mark.parametrize('note,fields,expected', ROWS, ids=[r[0] for r in ROWS])
