@@ -10,20 +10,14 @@ For every input family of tools/attn_check.py and both flavours (8 heads x 64, 1
     +90 on, in every row;
   * the peak families' largest logits and probabilities lie where the tool's docstring says.
 """
-import importlib.util
-import os
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _tools import load_script
 
 
 @pytest.fixture(scope='module')
 def ac():
-    spec = importlib.util.spec_from_file_location('attn_check', os.path.join(ROOT, 'tools', 'attn_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_script('tools/attn_check.py')
 
 
 def test_the_family_table_is_what_the_issue_lists(ac):

@@ -31,12 +31,10 @@ The kernels needed no change.  Scratch builds with one edit each (not committed)
 this file fail (onehot, offset+90 / -300 / +3000, big, P offset+90, ones), of attn512_kernel 5 (onehot, the three offsets, P offset+90),
 and g_attn of tools/gpu_check.py passes both; with the V halves or the key groups of attn64_kernel's phase 3 swapped on the P side 19 fail.
 """
-import importlib.util
-import os
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _tools import load_script
+
 pytestmark = pytest.mark.gpu
 
 FLAVOURS = ('8x64', '1x512')
@@ -50,9 +48,7 @@ def ac():
     assert torch.cuda.is_available(), 'gpu tests need an MI355X'
     from codeformer_amd import lib
     lib.load()
-    spec = importlib.util.spec_from_file_location('attn_check', os.path.join(ROOT, 'tools', 'attn_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
+    m = load_script('tools/attn_check.py')
     assert m.FAMILIES == FAMILIES and tuple(m.FLAVOURS) == FLAVOURS
     return m
 

@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+from _tools import load_script
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
@@ -150,10 +152,7 @@ def test_bf16_tensors_are_refused_by_kernels_without_the_storage_form(ops):
 
 @pytest.fixture(scope='module')
 def net():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('gpu_check', os.path.join(ROOT, 'tools', 'gpu_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
+    m = load_script('tools/gpu_check.py')
     return m.build_net().cuda()
 
 

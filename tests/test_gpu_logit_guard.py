@@ -3,7 +3,6 @@ contract on whole forwards: every unflagged face is bitwise the face a guard-off
 winograd_f43_encoder=False network returns (the forward is bitwise batch-invariant), in every precision mode, eagerly and under graph
 replay.  Assertions on which golden face is flagged use only faces more than ten times the 1e-5 logit error away from the threshold:
 real_0342 (reference minimum gap 5.5e-6: flagged) and the seeded face 0 (1.37e-3: not flagged)."""
-import importlib.util
 import os
 import re
 import subprocess
@@ -11,6 +10,8 @@ import sys
 
 import numpy as np
 import pytest
+
+from _tools import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
@@ -24,10 +25,7 @@ def chk():
     assert torch.cuda.is_available(), 'gpu tests need an MI355X'
     from codeformer_amd import lib
     lib.load()
-    spec = importlib.util.spec_from_file_location('gpu_check', os.path.join(ROOT, 'tools', 'gpu_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_script('tools/gpu_check.py')
 
 
 @pytest.fixture(scope='module')

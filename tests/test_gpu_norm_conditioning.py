@@ -22,11 +22,12 @@ sigma = 0 exactly) assert finiteness, sign, the 1 / sqrt(eps) cap and the mean o
 Apart from u, the kernels' eps values, FACTOR and ENVELOPE no kernel tolerance here is a literal (the 1e-9 / 1e-300 of the checks that the
 host's own fp64 reference agrees with F.group_norm / F.layer_norm / adain, and the count of GroupNorm calls of a forward, bound no kernel).
 """
-import importlib.util
 import os
 
 import numpy as np
 import pytest
+
+from _tools import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
@@ -598,9 +599,7 @@ def test_network_operating_point_is_inside_the_strict_envelope(ops, monkeypatch)
     sigma^2 / eps, recovered from the statistics partials the call was handed (from the tensor itself where it carries none), and the bound on
     the relative rstd error they imply at the largest n_t of the table -- every call must lie inside the strict envelope."""
     import torch
-    spec = importlib.util.spec_from_file_location('gpu_check', os.path.join(ROOT, 'tools', 'gpu_check.py'))
-    chk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(chk)
+    chk = load_script('tools/gpu_check.py')
     calls = []
     real = ops.groupnorm_tables
 

@@ -15,10 +15,11 @@ The checks themselves live in tools/gpu_check.py (also runnable stand-alone with
           the stated bf16 gate of the fp32 reference (max|d| <= 0.25, mean|d| <= 0.02 on outputs of std 0.5); precision='fp16'
           (IEEE-half operands, same split): same logits / indices conditions, pixel gate max|d| <= 0.04, mean|d| <= 0.003
 """
-import importlib.util
 import os
 
 import pytest
+
+from _tools import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -30,10 +31,7 @@ def chk():
     assert torch.cuda.is_available(), 'gpu tests need an MI355X'
     from codeformer_amd import lib
     lib.load()   # loud failure if the native library did not travel
-    spec = importlib.util.spec_from_file_location('gpu_check', os.path.join(ROOT, 'tools', 'gpu_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_script('tools/gpu_check.py')
 
 
 @pytest.mark.parametrize('group', ['basic', 'conv', 'attn', 'blocks', 'net', 'bf16'])
@@ -330,12 +328,9 @@ def test_winograd_conv_kernel(chk):
     prologue / epilogue / concat combination the network uses and for all its layer widths: tolerance 2e-5 + 1e-5*|ref| (the bound
     of the direct kernel; measured errors are 1-6e-6, below the direct kernel's), epilogue GroupNorm partials relative 1e-5,
     run-to-run and batch bitwise.  Shapes the kernel does not cover are refused by the C ABI, not silently rerouted."""
-    import importlib.util
     import torch
     from codeformer_amd import ops
-    spec = importlib.util.spec_from_file_location('wino_check', os.path.join(ROOT, 'tools', 'wino_check.py'))
-    wc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(wc)
+    wc = load_script('tools/wino_check.py')
     cases = [dict(B=1, H=16, W=16, cin=16, cout=64),
              dict(B=2, H=16, W=32, cin=32, cout=64, seed=1),
              dict(B=2, H=16, W=16, cin=64, cout=128, prologue=ops.PRO_AFFINE_SWISH, epilogue=ops.EPI_RESIDUAL, stats=True, seed=2),

@@ -8,11 +8,12 @@ The HIP path must meet the north-star gates in the default split-half mode AND t
 Without the per-image power-of-two range scale (cf_conv_desc.act_scale) the 'big' case is inf / NaN and the 'small' case loses the
 lo halves; the last test measures that (informational print + the assertion that the scale is what fixes it).
 """
-import importlib.util
 import os
 
 import numpy as np
 import pytest
+
+from _tools import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
@@ -27,10 +28,7 @@ def chk():
     assert torch.cuda.is_available(), 'gpu tests need an MI355X'
     from codeformer_amd import lib
     lib.load()
-    spec = importlib.util.spec_from_file_location('gpu_check', os.path.join(ROOT, 'tools', 'gpu_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_script('tools/gpu_check.py')
 
 
 @pytest.fixture(scope='module')

@@ -7,11 +7,12 @@ logit gap is below 1e-5 (there the reference's own thread-count 
 such a token must still pick one of the reference's top two).  uint8 images: at most 1 LSB, on at most 0.1 % of the bytes
 (a float that sits within 1e-4 of a rounding boundary may land on either side).
 """
-import importlib.util
 import os
 
 import numpy as np
 import pytest
+
+from _tools import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
@@ -30,10 +31,7 @@ def chk():
     assert torch.cuda.is_available(), 'gpu tests need an MI355X'
     from codeformer_amd import lib
     lib.load()
-    spec = importlib.util.spec_from_file_location('gpu_check', os.path.join(ROOT, 'tools', 'gpu_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_script('tools/gpu_check.py')
 
 
 @pytest.fixture(scope='module')
@@ -82,9 +80,7 @@ def test_encoder_logit_margin(chk, precision):
     32-face sweep (tests/golden/logit_sweep32.npz, the reference's top-8 codes per token) -- and every token whose reference top-2 gap is
     >= 1e-5:   (reference gap) / (2 x max |our logit - reference logit|)  >=  5,   no index differs, and no code outside the reference's
     top-8 comes anywhere near the winner.  Measured on MI355X: 7.0 ('f16x2') / 7.3 ('fp32') with the switch on, 9.9 / 8.7 with it off."""
-    spec = importlib.util.spec_from_file_location('logit_margin', os.path.join(ROOT, 'tools', 'logit_margin.py'))
-    lm = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(lm)
+    lm = load_script('tools/logit_margin.py')
     default_on = chk.build_net().winograd_f43_encoder
     r = lm.measure(lm.Nets(chk), chk, precision, default_on)
     rows = {k: v for k, v in r.items() if not k.startswith('_')}

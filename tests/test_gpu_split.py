@@ -8,10 +8,11 @@ within 5x of the exact-fp32 kernel's on the same case (measured: 1-2.3x max, equ
 512-channel 16x16 layer, which the network gives to the Winograd form).  The Winograd form of the split-half scheme
 (cf_winograd.hip H2, cf_wsplit.hip) is held to the same bounds (measured: 0.5-0.9x of the exact Winograd kernel's error).
 """
-import importlib.util
 import os
 
 import pytest
+
+from _tools import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -23,10 +24,7 @@ def sc():
     assert torch.cuda.is_available(), 'gpu tests need an MI355X'
     from codeformer_amd import lib
     lib.load()
-    spec = importlib.util.spec_from_file_location('split_check', os.path.join(ROOT, 'tools', 'split_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_script('tools/split_check.py')
 
 
 def test_split_conv_against_fp64(sc):
@@ -104,18 +102,13 @@ def test_split_half_token_gemm(sc):
     """cf_gemm_split.hip (CodeFormer.gemm_precision = 'f16x2', off by default): against fp64 at least as close as the exact fp32 GEMM
     (bias / GELU / residual epilogues, extreme weight magnitudes), bitwise the same for split counts 1 / 2 / 4 / 8, and the network's
     logits and indices with it against the reference golden."""
-    import importlib.util
     import numpy as np
     import torch
-    spec = importlib.util.spec_from_file_location('gemm_split_check', os.path.join(ROOT, 'tools', 'gemm_split_check.py'))
-    gc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gc)
+    gc = load_script('tools/gemm_split_check.py')
     for c in gc.CASES:
         es, ef, rmax, same = gc.case(**c)
         assert same and es <= 2e-5 + 1e-5 * rmax and es <= 2.0 * ef + 1e-7 * rmax, (c, es, ef)
-    spec = importlib.util.spec_from_file_location('gpu_check', os.path.join(ROOT, 'tools', 'gpu_check.py'))
-    chk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(chk)
+    chk = load_script('tools/gpu_check.py')
     from oracle.synth import seeded_input
     net = chk.build_net().cuda()
     net.gemm_precision = 'f16x2'
@@ -268,8 +261,8 @@ def test_splitk_winograd_bits_do_not_depend_on_the_split_count(sc):
     """The Winograd kernel on images of at most 32x32 pixels: virtual chunks of 128 channels are taken to the output domain and added
     in a fixed order -- 1, 2 or 4 workgroups per patch give the same bits; errors vs fp64 as the unsplit kernel's."""
     import torch
-    import torch.nn.functional as F
     from codeformer_amd import ops
+    reference = load_script('tools/conv_case.py').reference
     g = torch.Generator().manual_seed(9)
     for (B, H, W, cin, cout, epi) in ((1, 16, 16, 512, 512, ops.EPI_RESIDUAL), (2, 32, 32, 256, 256, ops.EPI_NONE), (1, 16, 16, 256, 512, ops.EPI_NONE)):
         x = torch.randn(B, H, W, cin, generator=g)
@@ -285,11 +278,7 @@ def test_splitk_winograd_bits_do_not_depend_on_the_split_count(sc):
             outs.append(y)
             stats.append(y._cf_stats.part.clone())
         assert all(torch.equal(o, outs[0]) for o in outs[1:]) and all(torch.equal(t, stats[0]) for t in stats[1:]), (H, cin, cout)
-        xd = x.double() * sc_.double()[:, None, None, :] + sh_.double()[:, None, None, :]
-        xd = xd * torch.sigmoid(xd)
-        ref = F.conv2d(xd.permute(0, 3, 1, 2), w.double(), b.double(), padding=1).permute(0, 2, 3, 1)
-        if epi:
-            ref = ref + res.double()
+        ref = reference(x, w, b, prologue=ops.PRO_AFFINE_SWISH, epilogue=epi, sc=sc_, sh=sh_, res=res)
         assert float((outs[0].cpu().double() - ref).abs().max()) <= 2e-5 + 1e-5 * float(ref.abs().max())
         # one image of the batch alone: same bits (the split count follows the tiles in flight, the association does not)
         if B > 1:
@@ -315,9 +304,7 @@ def test_winograd_single_16bit_operands(sc):
     b = torch.randn(C, generator=g)
     sc_, sh_ = torch.rand(B, C, generator=g) + 0.5, torch.randn(B, C, generator=g) * 0.1
     res = torch.randn(B, H, W, C, generator=g)
-    y = x.double() * sc_.double()[:, None, None, :] + sh_.double()[:, None, None, :]
-    y = y * torch.sigmoid(y)
-    ref = F.conv2d(y.permute(0, 3, 1, 2), w.double(), b.double(), padding=1).permute(0, 2, 3, 1) + res.double()
+    ref = load_script('tools/conv_case.py').reference(x, w, b, prologue=ops.PRO_AFFINE_SWISH, epilogue=ops.EPI_RESIDUAL, sc=sc_, sh=sh_, res=res)
     rms = float(ref.pow(2).mean().sqrt())
     xs, ws_, bs, scd, shd, resd = (t.cuda() for t in (x, w, b, sc_, sh_, res))
     outs = {}
@@ -439,12 +426,9 @@ def test_winograd_f43_forms_against_fp64(sc):
     the pack-time weight scale and the per-image activation scale -- against fp64: max error <= 2e-5 * max(|ref| / 4, 1) (measured
     0.8-1.5e-5: 5-8x the F(2,3) kernels, the conditioning of the larger transform), GroupNorm partials to 2e-6, bitwise repeatable;
     and the per-image bits do not depend on the batch."""
-    import importlib.util
     import torch
     from codeformer_amd import ops
-    spec = importlib.util.spec_from_file_location('f43_check', os.path.join(ROOT, 'tools', 'f43_check.py'))
-    fc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fc)
+    fc = load_script('tools/f43_check.py')
     assert len(fc.SMALL) >= 12
     for c in fc.SMALL:
         assert fc.case(**c), c
@@ -484,12 +468,9 @@ def test_winograd_f43_fp32_operands_against_fp64(sc):
     """The same kernel with IEEE-fp32 operands (CF_OPERAND_F32 + winograd = 2, ABI v20: precision 'fp32' of the generator / fusion layers):
     the same cases and batch invariance, bound 4e-5 * max(|ref| / 4, 1) (measured 1.1-2.8e-5); no weight / activation scale is involved
     (act tables are ignored)."""
-    import importlib.util
     import torch
     from codeformer_amd import ops
-    spec = importlib.util.spec_from_file_location('f43_check', os.path.join(ROOT, 'tools', 'f43_check.py'))
-    fc = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(fc)
+    fc = load_script('tools/f43_check.py')
     for c in fc.SMALL:
         assert fc.case(fp32=True, **c), c
     g = torch.Generator().manual_seed(4)
@@ -508,14 +489,14 @@ def test_winograd_f43_fp32_upsampling_gather(sc):
     precision 'fp32'; GroupNorm partials of the output; batch invariance; refusals."""
     import pytest
     import torch
-    import torch.nn.functional as F
     from codeformer_amd import ops
+    reference = load_script('tools/conv_case.py').reference
     g = torch.Generator().manual_seed(17)
     for (B, H, W, cin, cout) in ((2, 32, 32, 128, 128), (1, 64, 48, 256, 256), (3, 16, 32, 64, 128)):
         x = torch.randn(B, H, W, cin, generator=g)
         w = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
         b = torch.randn(cout, generator=g) * 0.1
-        ref = F.conv2d(F.interpolate(x.double().permute(0, 3, 1, 2), scale_factor=2.0, mode='nearest'), w.double(), b.double(), padding=1).permute(0, 2, 3, 1)
+        ref = reference(x, w, b, prologue=ops.PRO_NONE, epilogue=ops.EPI_NONE, upsample=True)
         pw = ops.pack_weight(w.cuda(), b.cuda(), bf16=ops.WF43F)
         y = ops.conv2d(x.cuda(), pw, upsample=True, emit_stats=True)
         folded = ops.conv2d(x.cuda(), ops.pack_weight(w.cuda(), b.cuda(), up2x=True), upsample=True, emit_stats=True)
@@ -543,16 +524,15 @@ def test_winograd_f43_with_512_input_channels(sc):
     are summed, so the bound is sqrt(2) x the 4e-5 (fp32 operands) / 2e-5 (split halves) of the <= 256-channel cases; the 8-wave form still refuses."""
     import pytest
     import torch
-    import torch.nn.functional as F
     from codeformer_amd import ops
+    reference = load_script('tools/conv_case.py').reference
     g = torch.Generator().manual_seed(3)
     for (B, H, cin, cout, cs) in ((2, 64, 512, 256, 256), (1, 32, 512, 128, 256)):
         x = torch.randn(B, H, H, cin, generator=g)
         w = torch.randn(cout, cin, 3, 3, generator=g) * (2 / (9 * cin)) ** 0.5
         b = torch.randn(cout, generator=g) * 0.1
         sc_, sh_ = torch.rand(B, cin, generator=g) + 0.5, torch.randn(B, cin, generator=g) * 0.1
-        xd = x.double() * sc_.double()[:, None, None, :] + sh_.double()[:, None, None, :]
-        ref = F.conv2d((xd * torch.sigmoid(xd)).permute(0, 3, 1, 2), w.double(), b.double(), padding=1).permute(0, 2, 3, 1)
+        ref = reference(x, w, b, prologue=ops.PRO_AFFINE_SWISH, epilogue=ops.EPI_NONE, sc=sc_, sh=sh_)
         scale = max(float(ref.abs().max()) / 4.0, 1.0)
         for code, bound in ((ops.WF43F, 4e-5), (ops.WF43, 2e-5)):
             pw = ops.pack_weight(w.cuda(), b.cuda(), bf16=code)

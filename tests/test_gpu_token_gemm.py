@@ -30,12 +30,10 @@ each (not committed), tests of this file that fail | of the four token-GEMM test
   (f) gemm_split_kernel without its lo hi MFMA (every nsplit)          9: permutation, mixed_cols / mixed_rows gates of h_sk, bitwise, batch, counters | 2
 With chunk weights of EQUAL size (+S, -S, ..) edit (d) passed cancel_chunks: every chunk addition was exact; the weights are unequal for that reason.
 """
-import importlib.util
-import os
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _tools import load_script
+
 pytestmark = pytest.mark.gpu
 
 KERNELS = ('f32_sk', 'f32_tile', 'h_sk', 'h_tile', 'h_wg')
@@ -50,9 +48,7 @@ def gc():
     assert torch.cuda.is_available(), 'gpu tests need an MI355X'
     from codeformer_amd import lib
     lib.load()
-    spec = importlib.util.spec_from_file_location('gemm_check', os.path.join(ROOT, 'tools', 'gemm_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
+    m = load_script('tools/gemm_check.py')
     assert m.KERNELS == KERNELS
     return m
 

@@ -6,6 +6,8 @@ import sys
 
 import numpy as np
 
+from _tools import load_script
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -254,11 +256,8 @@ def test_bench_line_stays_under_two_kilobytes():
     """The driver keeps a 2 KB tail of bench.py's stdout and truncates long strings (round-5 review: the fp32 figure was cut out of its record).
     The line is assembled from `compact_roofline` + flat scalars; with every field filled by values of realistic width it must stay below 2000
     characters, every string below 128, and the committed line of the round must carry the contract's fields with the IEEE-fp32 headline."""
-    import importlib.util
     import json
-    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
+    bench = load_script('bench.py')
     full = {'kind': 'conv3x3_wino43', 'kernel': 'x' * 300, 'bound': 'mfma', 'achieved': 123.45, 'peak': 157.3, 'unit': 'TFLOP/s', 'frac': 0.5351, 'traffic': 1186352743,
             'traffic_recorded': 1186352743, 'traffic_source': 'profiles/r06_pmc_bench_fp32.json', 'traffic_per_alg_bytes': 1.214, 'avg_launch_ms': 0.6357, 'launches_per_step': 54,
             'ms_per_step': 34.33, 'alg_bytes_per_launch': 977596568, 'frac_hbm_peak_alg_bytes': 0.1922, 'effective_tflops': 336.68, 'frac_algorithmic': 2.1404,
@@ -288,10 +287,7 @@ def test_bench_line_stays_under_two_kilobytes():
 def test_no_timing_or_ablation_scaffolds_in_the_product_sources():
     """Round 6 moved every timing / ablation scaffold out of codeformer_amd/csrc (tools/experiments/*.patch restore them for an experiment build):
     the macro names must not come back, and the stripping tool must find nothing to do."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('strip_mod', os.path.join(ROOT, 'tools', 'strip_experiment_macros.py'))
-    st = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(st)
+    st = load_script('tools/strip_experiment_macros.py')
     csrc = os.path.join(ROOT, 'codeformer_amd', 'csrc')
     for f in sorted(os.listdir(csrc)):
         src = open(os.path.join(csrc, f)).read()

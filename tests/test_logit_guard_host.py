@@ -1,13 +1,14 @@
 """Logit guard (CodeFormer.logit_guard), the parts that need no GPU: the gap rule restated in numpy against diagnostics.top2_gap on the
 reference's logits, the C ABI declaration / binding of cf_argmax_rows_gap, the --logit_guard flag of the three entry points and the
 function that resolves it, and the host path's `last_min_gap` / `guard_stats`."""
-import importlib.util
 import os
 import re
 
 import numpy as np
 import pytest
 import torch
+
+from _tools import load_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
@@ -87,10 +88,7 @@ def test_entry_point_validates_before_any_launch():
 
 
 def _script(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, name + '.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_script(name + '.py')
 
 
 def test_flag_parses_in_inference_codeformer():

@@ -10,21 +10,15 @@ outlier on a normal convolution part of sigma sqrt(2)) and every channels-per-gr
   * the rows whose bound on the relative rstd error stays inside ENVELOPE at the largest n_t are exactly the STRICT list, asserted
     literally: the GPU test cannot reclassify a row.
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _tools import load_script
 
 
 @pytest.fixture(scope='module')
 def m():
-    spec = importlib.util.spec_from_file_location('norm_conditioning', os.path.join(ROOT, 'tests', 'test_gpu_norm_conditioning.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    return load_script('tests/test_gpu_norm_conditioning.py')
 
 
 NPIX = 1024

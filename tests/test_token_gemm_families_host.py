@@ -12,22 +12,16 @@ For the input families of tools/gemm_check.py at the largest shapes the GPU test
   * gelu_edges: the fp64 pre-activations are the targets exactly, and the emulation of both schemes reproduces them bitwise;
   * routes(): every kernel is reached by at least one of the shapes, the refusals have no route.
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _tools import load_script
 
 
 @pytest.fixture(scope='module')
 def gc():
-    spec = importlib.util.spec_from_file_location('gemm_check', os.path.join(ROOT, 'tools', 'gemm_check.py'))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_script('tools/gemm_check.py')
 
 
 LARGEST = (384, 1152, 64)      # the larger of gemm_check.GATE_SHAPES (rows x K), and K = 1152 is the largest K any test uses

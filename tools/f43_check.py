@@ -6,70 +6,22 @@ import os
 import sys
 
 import torch
-import torch.nn.functional as F
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), HERE]
 from codeformer_amd import ops  # noqa: E402
-
-
-def t_ms(fn, n=10):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
+from conv_case import draw, launch_args, reference, stats_rel_err, t_ms  # noqa: E402
 
 
 def make(B, H, W, cin, cout, c_split=None, prologue=ops.PRO_NONE, epilogue=ops.EPI_NONE, stats=False, seed=0, wscale=1.0, xscale=1.0,
          ref=True):
-    dev = 'cpu' if ref else 'cuda'   # (timing-only cases draw their data on the device: no fp64 reference needed)
-    g = torch.Generator(device=dev).manual_seed(seed)
-    x = torch.randn(B, H, W, cin, generator=g, device=dev) * xscale
-    w = torch.randn(cout, cin, 3, 3, generator=g, device=dev) * (2.0 / (9 * cin)) ** 0.5 * wscale
-    b = torch.randn(cout, generator=g, device=dev) * 0.1
-    sc = torch.rand(B, cin, generator=g, device=dev) + 0.5
-    sh = torch.randn(B, cin, generator=g, device=dev) * 0.1
-    res = torch.randn(B, H, W, cout, generator=g, device=dev)
-    ss = torch.randn(B, H, W, cout, generator=g, device=dev) * 0.3
-    want = None
-    if ref:
-        xd = x.double()
-        if prologue in (ops.PRO_AFFINE, ops.PRO_AFFINE_SWISH):
-            xd = xd * sc.double()[:, None, None, :] + sh.double()[:, None, None, :]
-            if prologue == ops.PRO_AFFINE_SWISH:
-                xd = xd * torch.sigmoid(xd)
-        elif prologue == ops.PRO_LEAKY:
-            xd = F.leaky_relu(xd, 0.2)
-        want = F.conv2d(xd.permute(0, 3, 1, 2), w.double(), b.double(), padding=1).permute(0, 2, 3, 1)
-        if epilogue == ops.EPI_RESIDUAL:
-            want = want + res.double()
-        elif epilogue == ops.EPI_SFT:
-            want = res.double() + 0.7 * (res.double() * ss.double() + want)
-    kw = dict(prologue=prologue, epilogue=epilogue, emit_stats=stats)
-    if prologue in (ops.PRO_AFFINE, ops.PRO_AFFINE_SWISH):
-        kw.update(scale=sc.cuda(), shift=sh.cuda())
-    if epilogue != ops.EPI_NONE:
-        kw.update(res=res.cuda())
-    if epilogue == ops.EPI_SFT:
-        kw.update(sft_scale=ss.cuda(), sft_w=0.7)
-    xc = x.cuda()
-    x1, x2 = (xc, None) if c_split is None else (xc[..., :c_split].contiguous(), xc[..., c_split:].contiguous())
+    # (timing-only cases draw their data on the device: no fp64 reference needed)
+    x, w, b, sc, sh, res, ss = draw(B, H, W, cin, cout, seed=seed, wscale=wscale, xscale=xscale, device='cpu' if ref else 'cuda')
+    want = reference(x, w, b, prologue=prologue, epilogue=epilogue, sc=sc, sh=sh, res=res, ss=ss) if ref else None
+    x1, x2, kw = launch_args(x, sc, sh, res, ss, prologue=prologue, epilogue=epilogue, stats=stats, c_split=c_split)
     if prologue in (ops.PRO_NONE, ops.PRO_LEAKY):   # un-normalised input: the per-image range scale, as the arch modules pass it
         kw['act'] = ops.act_scale(x1, x2)
     return x1, x2, w.cuda(), b.cuda(), kw, want
-
-
-def stats_err(y, B, H, W):
-    st = y._cf_stats
-    got = st.part.view(B, 32, st.parts, 2).sum(2)
-    r = y.double().view(B, H * W, 32, st.cpg)
-    want = torch.stack([r.sum((1, 3)), (r * r).sum((1, 3))], -1)
-    return float(((got - want).abs() / want.abs().clamp_min(1e-6)).max())
 
 
 def case(B, H, W, cin, cout, timing=False, check=True, fp32=False, **kwargs):
@@ -87,7 +39,7 @@ def case(B, H, W, cin, cout, timing=False, check=True, fp32=False, **kwargs):
         # (fp32 operands: measured 1.1-2.8e-5 -- products rounded to 24 bits where the split-half sum of three carries ~32 -- bound 4e-5)
         ok = float(d4.max()) <= (4e-5 if fp32 else 2e-5) * max(scale / 4.0, 1.0) and bool(torch.isfinite(y4).all())
         if kw['emit_stats']:
-            e4 = stats_err(y4, B, H, W)
+            e4 = stats_rel_err(y4)
             msg += f' stats {e4:.1e}'
             ok = ok and e4 < 2e-6   # (fp32 over four values, then fp64: the shipped kernels' scheme)
         y4b = ops.conv2d(x1, pw4, x2=x2, **kw)

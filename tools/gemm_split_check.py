@@ -6,21 +6,10 @@ import sys
 import torch
 import torch.nn.functional as F
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), HERE]
 from codeformer_amd import ops  # noqa: E402
-
-
-def t_ms(fn, n=20):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
+from conv_case import t_ms  # noqa: E402
 
 
 def case(M, K, N, epilogue=ops.EPI_NONE, bias=True, seed=0, timing=False, wscale=1.0):
@@ -54,13 +43,13 @@ def case(M, K, N, epilogue=ops.EPI_NONE, bias=True, seed=0, timing=False, wscale
             same = same and bool(torch.equal(y, ys))
     msg = f'M{M} K{K} N{N} epi{epilogue}: split max {es:.2e} | fp32 max {ef:.2e} (ref max {float(ref.abs().max()):.2f}) | split counts bitwise equal: {same}'
     if timing:
-        ts_, tf_ = t_ms(lambda: ops.linear(xc, pw_s, **kw)), t_ms(lambda: ops.linear(xc, pw_f, **kw))
+        ts_, tf_ = t_ms(lambda: ops.linear(xc, pw_s, **kw), n=20), t_ms(lambda: ops.linear(xc, pw_f, **kw), n=20)
         fl = 2.0 * M * N * K
         msg += f' | split {ts_ * 1e3:.1f} us ({fl / ts_ / 1e9:.0f} TF-equiv) fp32 {tf_ * 1e3:.1f} us ({fl / tf_ / 1e9:.0f}) x{tf_ / ts_:.2f}'
         per = {}
         for ns in (-1, 1, 2, 4):
             if (ns == -1 and K <= 1024) or (ns > 0 and (K // 128) % ns == 0):
-                per[ns] = t_ms(lambda: ops.conv2d(x4, pw_s, epilogue=epilogue, res=r4, split_k=ns)) * 1e3
+                per[ns] = t_ms(lambda: ops.conv2d(x4, pw_s, epilogue=epilogue, res=r4, split_k=ns), n=20) * 1e3
         msg += ' | us by split_k: ' + ' '.join(f'{k}:{v:.1f}' for k, v in per.items())
     print(msg, flush=True)
     return es, ef, float(ref.abs().max()), same

@@ -1,66 +1,24 @@
 """Split-half conv kernels (cf_split.hip direct form, cf_winograd.hip / cf_wsplit.hip Winograd form; CF_OPERAND_F16X2) vs an fp64
 reference, next to the exact-fp32 kernels (accuracy + time).
 GPU box only.  usage: python tools/split_check.py [quick]"""
+import math
 import os
 import sys
 
-import torch
-import torch.nn.functional as F
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), HERE]
 from codeformer_amd import ops  # noqa: E402
-
-
-def t_ms(fn, n=10):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
+from conv_case import draw, launch_args, reference, stats_rel_err, t_ms  # noqa: E402
 
 
 def case(B, H, W, cin, cout, *, upsample=False, c_split=None, prologue=ops.PRO_NONE, epilogue=ops.EPI_NONE, stats=False, seed=0,
          timing=True, wscale=1.0, xscale=1.0, others=True):
     """Returns (err_split, err_best_fp32_kernel, stats_rel_err, ref_absmax, mean_abs_err_split, err_wsplit, stats_rel_err_wsplit);
     the last two are NaN / 0 for shapes the Winograd form does not cover."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, H, W, cin, generator=g) * xscale
-    w = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5 * wscale
-    b = torch.randn(cout, generator=g) * 0.1
-    sc = torch.rand(B, cin, generator=g) + 0.5
-    sh = torch.randn(B, cin, generator=g) * 0.1
-    Ho, Wo = (2 * H, 2 * W) if upsample else (H, W)
-    res = torch.randn(B, Ho, Wo, cout, generator=g)
-    ss = torch.randn(B, Ho, Wo, cout, generator=g) * 0.3
-    xd = x.double()
-    if prologue in (ops.PRO_AFFINE, ops.PRO_AFFINE_SWISH):
-        xd = xd * sc.double()[:, None, None, :] + sh.double()[:, None, None, :]
-        if prologue == ops.PRO_AFFINE_SWISH:
-            xd = xd * torch.sigmoid(xd)
-    elif prologue == ops.PRO_LEAKY:
-        xd = F.leaky_relu(xd, 0.2)
-    xn = xd.permute(0, 3, 1, 2)
-    if upsample:
-        xn = F.interpolate(xn, scale_factor=2.0, mode='nearest')
-    ref = F.conv2d(xn, w.double(), b.double(), padding=1).permute(0, 2, 3, 1)
-    if epilogue == ops.EPI_RESIDUAL:
-        ref = ref + res.double()
-    elif epilogue == ops.EPI_SFT:
-        ref = res.double() + 0.7 * (res.double() * ss.double() + ref)
-    kw = dict(prologue=prologue, epilogue=epilogue, emit_stats=stats, upsample=upsample)
-    if prologue in (ops.PRO_AFFINE, ops.PRO_AFFINE_SWISH):
-        kw.update(scale=sc.cuda(), shift=sh.cuda())
-    if epilogue != ops.EPI_NONE:
-        kw.update(res=res.cuda())
-    if epilogue == ops.EPI_SFT:
-        kw.update(sft_scale=ss.cuda(), sft_w=0.7)
-    xc = x.cuda()
-    x1, x2 = (xc, None) if c_split is None else (xc[..., :c_split].contiguous(), xc[..., c_split:].contiguous())
+    x, w, b, sc, sh, res, ss = draw(B, H, W, cin, cout, upsample=upsample, seed=seed, wscale=wscale, xscale=xscale)
+    ref = reference(x, w, b, prologue=prologue, epilogue=epilogue, sc=sc, sh=sh, res=res, ss=ss, upsample=upsample)
+    x1, x2, kw = launch_args(x, sc, sh, res, ss, prologue=prologue, epilogue=epilogue, stats=stats, upsample=upsample, c_split=c_split)
+    Ho, Wo = ref.shape[1:3]
     pw_s = ops.pack_weight(w.cuda(), b.cuda(), bf16=ops.SPLIT, up2x=upsample)
     ys = ops.conv2d(x1, pw_s, x2=x2, **kw)
     d = (ys.cpu().double() - ref).abs()
@@ -76,11 +34,7 @@ def case(B, H, W, cin, cout, *, upsample=False, c_split=None, prologue=ops.PRO_N
         ew = float(dw.max())
         msg += f' | wsplit max {ew:.2e} mean {float(dw.mean()):.2e}'
         if stats:
-            sw = yw._cf_stats
-            tw = sw.part.view(B, 32, sw.parts, 2).sum(2)
-            r = yw.double().view(B, Ho * Wo, 32, sw.cpg)
-            want = torch.stack([r.sum((1, 3)), (r * r).sum((1, 3))], -1)
-            estw = float(((tw - want).abs() / want.abs().clamp_min(1e-6)).max())
+            estw = stats_rel_err(yw)
             msg += f' (stats {estw:.1e})'
     ef = float('nan')
     pw_f = None
@@ -91,14 +45,10 @@ def case(B, H, W, cin, cout, *, upsample=False, c_split=None, prologue=ops.PRO_N
         df = (yf.cpu().double() - ref).abs()
         ef = float(df.max())
         msg += f' | fp32 {"winograd" if code else "direct"} max {ef:.2e} mean {float(df.mean()):.2e}'
-    msg += f' (ref max {float(ref.abs().max()):.2f}, weight scale 2^{pw_s.scale and __import__("math").frexp(pw_s.scale)[1] - 1})'
+    msg += f' (ref max {float(ref.abs().max()):.2f}, weight scale 2^{pw_s.scale and math.frexp(pw_s.scale)[1] - 1})'
     est = 0.0
     if stats:   # the epilogue's GroupNorm partials must describe exactly the tensor that was written
-        sw = ys._cf_stats
-        tw = sw.part.view(B, 32, sw.parts, 2).sum(2)
-        r = ys.double().view(B, Ho * Wo, 32, sw.cpg)
-        want = torch.stack([r.sum((1, 3)), (r * r).sum((1, 3))], -1)
-        est = float(((tw - want).abs() / want.abs().clamp_min(1e-6)).max())
+        est = stats_rel_err(ys)
         msg += f' | stats rel err {est:.1e}'
     if timing:
         ts_ = t_ms(lambda: ops.conv2d(x1, pw_s, x2=x2, **kw))

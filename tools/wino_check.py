@@ -2,57 +2,17 @@
 import os
 import sys
 
-import torch
-import torch.nn.functional as F
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), HERE]
 from codeformer_amd import ops  # noqa: E402
-
-
-def t_ms(fn, n=10):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
+from conv_case import draw, launch_args, reference, stats_rel_err, t_ms  # noqa: E402
 
 
 def case(B, H, W, cin, cout, *, c_split=None, prologue=ops.PRO_NONE, epilogue=ops.EPI_NONE, stats=False, seed=0, timing=True,
          direct=True):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, H, W, cin, generator=g)
-    w = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
-    b = torch.randn(cout, generator=g) * 0.1
-    sc = torch.rand(B, cin, generator=g) + 0.5
-    sh = torch.randn(B, cin, generator=g) * 0.1
-    res = torch.randn(B, H, W, cout, generator=g)
-    ss = torch.randn(B, H, W, cout, generator=g) * 0.3
-    xd = x.double()
-    if prologue in (ops.PRO_AFFINE, ops.PRO_AFFINE_SWISH):
-        xd = xd * sc.double()[:, None, None, :] + sh.double()[:, None, None, :]
-        if prologue == ops.PRO_AFFINE_SWISH:
-            xd = xd * torch.sigmoid(xd)
-    elif prologue == ops.PRO_LEAKY:
-        xd = F.leaky_relu(xd, 0.2)
-    ref = F.conv2d(xd.permute(0, 3, 1, 2), w.double(), b.double(), padding=1).permute(0, 2, 3, 1)
-    if epilogue == ops.EPI_RESIDUAL:
-        ref = ref + res.double()
-    elif epilogue == ops.EPI_SFT:
-        ref = res.double() + 0.7 * (res.double() * ss.double() + ref)
-    kw = dict(prologue=prologue, epilogue=epilogue, emit_stats=stats)
-    if prologue in (ops.PRO_AFFINE, ops.PRO_AFFINE_SWISH):
-        kw.update(scale=sc.cuda(), shift=sh.cuda())
-    if epilogue != ops.EPI_NONE:
-        kw.update(res=res.cuda())
-    if epilogue == ops.EPI_SFT:
-        kw.update(sft_scale=ss.cuda(), sft_w=0.7)
-    xc = x.cuda()
-    x1, x2 = (xc, None) if c_split is None else (xc[..., :c_split].contiguous(), xc[..., c_split:].contiguous())
+    x, w, b, sc, sh, res, ss = draw(B, H, W, cin, cout, seed=seed)
+    ref = reference(x, w, b, prologue=prologue, epilogue=epilogue, sc=sc, sh=sh, res=res, ss=ss)
+    x1, x2, kw = launch_args(x, sc, sh, res, ss, prologue=prologue, epilogue=epilogue, stats=stats, c_split=c_split)
     pw_d = ops.pack_weight(w.cuda(), b.cuda())
     pw_w = ops.pack_weight(w.cuda(), b.cuda(), bf16=ops.WINOGRAD)
     yw = ops.conv2d(x1, pw_w, x2=x2, **kw)
@@ -62,11 +22,7 @@ def case(B, H, W, cin, cout, *, c_split=None, prologue=ops.PRO_NONE, epilogue=op
     msg = f'B{B} {H}x{W} {cin}->{cout} pro{prologue} epi{epilogue}{" cat" if c_split else ""}: direct {ed:.2e} winograd {ew:.2e} (ref max {float(ref.abs().max()):.2f})'
     es = 0.0
     if stats:   # the epilogue's GroupNorm partials must describe exactly the tensor that was written
-        sw = yw._cf_stats
-        tw = sw.part.view(B, 32, sw.parts, 2).sum(2)
-        r = yw.double().view(B, H * W, 32, sw.cpg)
-        want = torch.stack([r.sum((1, 3)), (r * r).sum((1, 3))], -1)
-        es = float(((tw - want).abs() / want.abs().clamp_min(1e-6)).max())
+        es = stats_rel_err(yw)
         msg += f' | stats rel err {es:.1e}'
     if timing:
         td_, tw_ = t_ms(lambda: ops.conv2d(x1, pw_d, x2=x2, **kw)), t_ms(lambda: ops.conv2d(x1, pw_w, x2=x2, **kw))
