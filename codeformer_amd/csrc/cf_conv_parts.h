@@ -28,7 +28,7 @@ bool cf_wsplit_covers(const cf_conv_desc* d);                                   
 int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);   // called by cf_winograd_launch for what it covers
 int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);      // cf_wf43.hip: F(4,3)
 int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);     // cf_split.hip: direct, split-half operands
-int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream);                  // cf_gemm_split.hip: split-half token GEMM
+int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);  // cf_gemm_split.hip: split-half token GEMM
 int cf_gemm_f32_tile_try(const cf_conv_desc* d, hipStream_t stream);                  // cf_gemm_split.hip: fp32 token tiles (CF_OK: launched, 1: not its shape)
 // split-K geometry: output tiles of the launch and accumulator bytes one (tile, split) parks in the workspace
 int cf_gemm_split_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_part);

@@ -14,6 +14,17 @@
 //     fp32 split-K GEMM): the bits do not depend on how many workgroups (1, 2, 4, 8) share a tile, so the host picks the split
 //     count from the tiles in flight and results stay bitwise batch-invariant;
 //   * epilogue: bias, exact-erf GELU or residual, 128-byte row segments per store instruction.
+//
+// The four kernels (and the fp32 split-K instantiation of cf_igemm.hip) agree BITWISE.  What they share is written once where the compiled
+// function stayed instruction-identical to the one with the text written out (tools/strip_experiment_macros.py --verify; the rule of
+// cf_conv_parts.h): gs_finish / gs_bias (the epilogue), gs_args and the two shape predicates (host).  Own text, and what a shared form did:
+//   gs_finish  gemm_split_chunk_kernel (one of its four unrolled GELU tests became a scalar compare: other opcodes)
+//   the ring   the two tile kernels each keep load_stage, stage and the R0..R3 schedule: as ONE template, over an operand policy or over
+//              the kernels' own lambdas, both got other address arithmetic (6 to 11 opcode counts) and the split-half one 240 for 236
+//              VGPRs.  The chunk fold is a vector add in the fp32 kernel and element loops in the others; each in the other's wording
+//              changes its v_pk_add_f32 count.  Keep the two copies in step by hand.
+//   the 8-channel split of gemm_split_kernel / gemm_split_chunk_kernel: as a helper the latter got other register numbers throughout;
+//   the accumulator reset: as a helper gemm_split_kernel got 34 for 40 SGPRs, and the loop is one line.
 #include <cstdlib>
 #include <type_traits>
 
@@ -40,6 +51,19 @@ struct GsArgs {
   int n_alt;
 };
 __device__ __forceinline__ const float* gs_rows(const GsArgs& g, int n0) { return (g.a_alt && n0 >= g.n_alt) ? g.a_alt : g.a; }
+
+// ---- what the four kernels share (this file only) --------------------------------------------------------------------------------------
+// The epilogue expression, once: v = tot * acc_scale + bias (SCALED = false, the fp32 operands: tot + bias, no multiply), exact-erf GELU or
+// + residual, store.  The caller loads the bias once per column.  The expression shape is part of the result (contracted into FMAs as written).
+__device__ __forceinline__ float gs_bias(const GsArgs& g, int n) { return g.bias ? g.bias[n] : 0.f; }
+template <bool SCALED>
+__device__ __forceinline__ void gs_finish(const GsArgs& g, float tot, int row, int n, float bias) {
+  const size_t o = (size_t)row * g.N + n;
+  float v = SCALED ? tot * g.acc_scale + bias : tot + bias;
+  if (g.epilogue == CF_EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+  if (g.epilogue == CF_EPI_RESIDUAL) v += g.res[o];
+  g.out[o] = v;
+}
 
 constexpr int GS_GROUP = 4;  // k steps (of 16) per prefetch group; a virtual chunk of 128 values = two groups
 
@@ -130,15 +154,9 @@ __global__ __launch_bounds__(256) void gemm_split_kernel(const GsArgs g) {
 
   // ---- epilogue: lane holds column n0 + l31 of rows cf_acc_row(r, lane) ----
   const int n = n0 + l31;
-  const float bias = g.bias ? g.bias[n] : 0.f;
+  const float bias = gs_bias(g, n);
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const size_t o = (size_t)(m0 + cf_acc_row(r, lane)) * g.N + n;
-    float v = tot[r] * g.acc_scale + bias;
-    if (g.epilogue == CF_EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-    if (g.epilogue == CF_EPI_RESIDUAL) v += g.res[o];
-    g.out[o] = v;
-  }
+  for (int r = 0; r < 16; ++r) gs_finish<true>(g, tot[r], m0 + cf_acc_row(r, lane), n, bias);
 }
 
 // ---- the same GEMM with the token tile staged through LDS (round 4): 128 tokens x BN = 64 NI columns (NI = 1) per workgroup -----
@@ -284,17 +302,11 @@ __global__ __launch_bounds__(256) void gemm_split_tile_kernel(const GsArgs g) {
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) {
     const int n = n0 + ni * 32 + l31;
-    const float bias = g.bias ? g.bias[n] : 0.f;
+    const float bias = gs_bias(g, n);
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const size_t o = (size_t)(m0 + wm * 64 + mi * 32 + cf_acc_row(r, lane)) * g.N + n;
-        float v = tot[mi][ni][r] * g.acc_scale + bias;
-        if (g.epilogue == CF_EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-        if (g.epilogue == CF_EPI_RESIDUAL) v += g.res[o];
-        g.out[o] = v;
-      }
+      for (int r = 0; r < 16; ++r) gs_finish<true>(g, tot[mi][ni][r], m0 + wm * 64 + mi * 32 + cf_acc_row(r, lane), n, bias);
   }
 }
 
@@ -379,7 +391,7 @@ __global__ __launch_bounds__(256, MI * NI == 1 ? 1 : 2) void gemm_split_chunk_ke
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) {
     const int n = n0 + ni * 32 + l31;
-    const float bias = g.bias ? g.bias[n] : 0.f;
+    const float bias = gs_bias(g, n);
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -521,17 +533,11 @@ __global__ __launch_bounds__(256) void gemm_f32_tile_kernel(const GsArgs g) {
   // ---- epilogue: the expression of cf_igemm.hip's vector epilogue per element (+ bias, then GELU / + residual); lane holds column n of rows
   //      cf_acc_row(r, lane) of each of its tiles.  A wave's 32 lanes of a half store 128 contiguous bytes per row. ----
   const int n = n0 + l31;
-  const float bias = g.bias ? g.bias[n] : 0.f;
+  const float bias = gs_bias(g, n);
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const size_t o = (size_t)(m0 + wm * 64 + mi * 32 + cf_acc_row(r, lane)) * g.N + n;
-      float v = tot[mi][r] + bias;
-      if (g.epilogue == CF_EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-      if (g.epilogue == CF_EPI_RESIDUAL) v += g.res[o];
-      g.out[o] = v;
-    }
+    for (int r = 0; r < 16; ++r) gs_finish<false>(g, tot[mi][r], m0 + wm * 64 + mi * 32 + cf_acc_row(r, lane), n, bias);
 }
 
 // W' = scale * W as hi = f16(W'), lo = f16(W' - hi) in MFMA-operand order [K/16][N/32][hi, lo][lane 64][4 words]:
@@ -554,6 +560,35 @@ __global__ void pack_linear_f16x2_kernel(const float* __restrict__ w, int N, int
     out |= (unsigned)__builtin_bit_cast(unsigned short, hv) << (16 * h);
   }
   packed[i] = out;
+}
+
+// What the launches of this file accept: a dense single-input token GEMM (no channel stride, NCHW end, prologue or statistics) ...
+bool gs_plain_token_gemm(const cf_conv_desc* d) {
+  return d->stride == 1 && !d->in_nchw && !d->out_nchw && d->c1 == 0 && d->prologue == CF_PRO_NONE && !d->stats_out &&
+         (d->ld_in0 == 0 || d->ld_in0 == d->c0) && (d->ld_out == 0 || d->ld_out == d->cout);
+}
+// ... with one of the epilogues gs_finish knows
+bool gs_epi_known(const cf_conv_desc* d) { return d->epilogue == CF_EPI_NONE || d->epilogue == CF_EPI_GELU || d->epilogue == CF_EPI_RESIDUAL; }
+
+// The kernel arguments of an m-row launch of the descriptor's GEMM (a_alt: the second token matrix, split-half operands only).
+GsArgs gs_args(const cf_conv_desc* d, long m, int nsplit, float* ws, unsigned* counters, const float* a_alt) {
+  GsArgs g;
+  g.a = d->in0;
+  g.w = d->weight;
+  g.bias = d->bias;
+  g.res = d->res;
+  g.out = d->out;
+  g.M = (int)m;
+  g.N = d->cout;
+  g.K = d->c0;
+  g.epilogue = d->epilogue;
+  g.acc_scale = d->acc_scale;  // (the fp32 kernel does not read it)
+  g.ws = ws;
+  g.counters = counters;
+  g.nsplit = nsplit;
+  g.a_alt = a_alt;
+  g.n_alt = a_alt ? d->alt_cout0 : 0;
+  return g;
 }
 
 }  // namespace
@@ -588,40 +623,27 @@ int cf_gemm_split_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_pa
   return CF_OK;
 }
 
-int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream) {
+// parts_query (cf_conv2d_stats_parts): every check below, then 0 partials -- these kernels write no statistics -- and no launch.
+int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {
   int tiles = 0;
   long per = 0;
   const int rc = cf_gemm_split_geometry(d, &tiles, &per);
   if (rc != CF_OK) return rc;
-  CF_REQUIRE(d->stride == 1 && !d->in_nchw && !d->out_nchw && d->c1 == 0 && d->prologue == CF_PRO_NONE && !d->stats_out &&
-                 (d->ld_in0 == 0 || d->ld_in0 == d->c0) && (d->ld_out == 0 || d->ld_out == d->cout),
-             "cf_conv2d(1x1, f16x2): dense single-input token GEMMs without prologue / statistics only");
-  CF_REQUIRE(d->epilogue == CF_EPI_NONE || d->epilogue == CF_EPI_GELU || d->epilogue == CF_EPI_RESIDUAL,
-             "cf_conv2d(1x1, f16x2): epilogues are none / GELU / residual");
+  CF_REQUIRE(gs_plain_token_gemm(d), "cf_conv2d(1x1, f16x2): dense single-input token GEMMs without prologue / statistics only");
+  CF_REQUIRE(gs_epi_known(d), "cf_conv2d(1x1, f16x2): epilogues are none / GELU / residual");
   CF_REQUIRE(d->acc_scale > 0.f, "cf_conv2d(1x1, f16x2): acc_scale must be the inverse of the pack-time weight scale (got %g)", (double)d->acc_scale);
   CF_REQUIRE(!d->in0_alt || (d->alt_cout0 > 0 && d->alt_cout0 < d->cout && d->alt_cout0 % 128 == 0),
              "cf_conv2d(1x1, f16x2): in0_alt needs 0 < alt_cout0 < cout, a multiple of 128 (got %d of %d)", d->alt_cout0, d->cout);
+  const long m = (long)d->batch * d->hout * d->wout;
   const int V = d->c0 / 128;
   if (d->split_k == CF_SPLITK_IN_WORKGROUP) {   // the chunks of a tile shared by the waves of one workgroup (same bits)
-    const long m = (long)d->batch * d->hout * d->wout;
     CF_REQUIRE(V >= 1 && V <= GS_CHUNK_MAXV && m % 32 == 0,
                "cf_conv2d(1x1, f16x2, in-workgroup split): K %d must be a multiple of 128 up to %d, M a multiple of 32 (N %% 64 == 0: the packing)", d->c0, GS_CHUNK_MAXV * 128);
-    GsArgs g;
-    g.a_alt = d->in0_alt;
-    g.n_alt = d->alt_cout0;
-    g.a = d->in0;
-    g.w = d->weight;
-    g.bias = d->bias;
-    g.res = d->res;
-    g.out = d->out;
-    g.M = (int)m;
-    g.N = d->cout;
-    g.K = d->c0;
-    g.epilogue = d->epilogue;
-    g.acc_scale = d->acc_scale;
-    g.ws = nullptr;
-    g.counters = nullptr;
-    g.nsplit = 1;
+    if (parts_query) {
+      *parts_query = 0;
+      return CF_OK;
+    }
+    const GsArgs g = gs_args(d, m, 1, nullptr, nullptr, d->in0_alt);
     // (a 64 x 64-tile instantiation <2, 2> of the same kernel -- operands of half a chunk in flight -- was measured from 2048 rows up: 17.3 vs 15.2 us
     //  at 2048 x 512 x 512, 23.4 vs the token-tile kernel's 23.5 us at 4096 rows: no gain, not instantiated; the host sends large launches to the tile kernel)
     CF_LDS_ATTR((gemm_split_chunk_kernel<1, 1>), GS_CHUNK_MAXV * 4096);
@@ -632,22 +654,11 @@ int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream) {
   const int nsplit = d->split_k >= 1 ? d->split_k : 1;
   CF_REQUIRE(V % nsplit == 0, "cf_conv2d(1x1, f16x2): split_k %d must divide K/128 = %d", nsplit, V);
   CF_REQUIRE(nsplit == 1 || (d->workspace && d->counters), "cf_conv2d(1x1, f16x2): split_k > 1 needs workspace and counters");
-  GsArgs g;
-  g.a_alt = d->in0_alt;
-  g.n_alt = d->alt_cout0;
-  g.a = d->in0;
-  g.w = d->weight;
-  g.bias = d->bias;
-  g.res = d->res;
-  g.out = d->out;
-  g.M = (int)((long)d->batch * d->hout * d->wout);
-  g.N = d->cout;
-  g.K = d->c0;
-  g.epilogue = d->epilogue;
-  g.acc_scale = d->acc_scale;
-  g.ws = d->workspace;
-  g.counters = d->counters;
-  g.nsplit = nsplit;
+  if (parts_query) {
+    *parts_query = 0;
+    return CF_OK;
+  }
+  const GsArgs g = gs_args(d, m, nsplit, d->workspace, d->counters, d->in0_alt);
   // token tiles of 128 rows staged through LDS where the shape allows and K is not split (bitwise the same result: see the kernel);
   // the narrow 128 x 64 form: its 256+ workgroups for N = 512 keep more loads in flight than 128 x 128 tiles (measured inside the
   // step: 26.9 vs 29.6 us on 4096 x 512 x 1024)
@@ -667,31 +678,14 @@ int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream) {
 int cf_gemm_f32_tile_try(const cf_conv_desc* d, hipStream_t stream) {
   const long m = (long)d->batch * d->hout * d->wout;
   const int k = d->c0;
-  if (d->taps != 1 || d->bf16_mfma != CF_OPERAND_F32 || d->split_k != 1 || d->c1 != 0 || d->stride != 1 || d->in_nchw || d->out_nchw ||
-      d->prologue != CF_PRO_NONE || d->stats_out || d->stats_cpg || m % 128 || k % 128 || d->cout % 64 || d->cout_pad != d->cout ||
-      (d->ld_in0 != 0 && d->ld_in0 != d->c0) || (d->ld_out != 0 && d->ld_out != d->cout) || d->pad_mode != CF_PAD_ZERO ||
-      !(d->epilogue == CF_EPI_NONE || d->epilogue == CF_EPI_GELU || d->epilogue == CF_EPI_RESIDUAL))
+  if (d->taps != 1 || d->bf16_mfma != CF_OPERAND_F32 || d->split_k != 1 || !gs_plain_token_gemm(d) || !gs_epi_known(d) || d->stats_cpg ||
+      m % 128 || k % 128 || d->cout % 64 || d->cout_pad != d->cout || d->pad_mode != CF_PAD_ZERO)
     return 1;
   // 512 -> 512 (v / out projections) stays on the 64 x 64 instantiation: 29.4 us against 33.6 here at 4096 tokens (its 512 workgroups
   // against 256 one-wave-per-SIMD ones); every other Linear shape of the Transformer gains (profiles/r06_gemm_f32_tile_probe.txt:
   // 256 -> 512 19.0 -> 16.4 us, 512 -> 1024 52.7 -> 45.8, 1024 -> 512 54.7 -> 51.0).  A per-shape choice between bitwise-equal kernels.
   if (k == 512 && d->cout == 512) return 1;
-  GsArgs g;
-  g.a_alt = nullptr;   // (fp32 operands: one token matrix per launch)
-  g.n_alt = 0;
-  g.a = d->in0;
-  g.w = d->weight;
-  g.bias = d->bias;
-  g.res = d->res;
-  g.out = d->out;
-  g.M = (int)m;
-  g.N = d->cout;
-  g.K = k;
-  g.epilogue = d->epilogue;
-  g.acc_scale = 1.f;
-  g.ws = nullptr;
-  g.counters = nullptr;
-  g.nsplit = 1;
+  const GsArgs g = gs_args(d, m, 1, nullptr, nullptr, nullptr);   // (fp32 operands: one token matrix per launch)
   hipLaunchKernelGGL(gemm_f32_tile_kernel, dim3((unsigned)((g.M / 128) * (g.N / 64))), dim3(256), 0, stream, g);
   CF_CHECK_LAUNCH("cf_conv2d(1x1, fp32 token tiles)");
   return CF_OK;

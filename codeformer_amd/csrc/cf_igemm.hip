@@ -1360,7 +1360,8 @@ static int conv_validate(const cf_conv_desc* d, const int* pq, ConvFacts& f) {
                "cf_conv2d: act_scale is applied by the Winograd / split-half convolution kernels only (operand %d, winograd %d, taps %d)",
                d->bf16_mfma, d->winograd, d->taps);
   }
-  if (d->taps == 1 && d->bf16_mfma == CF_OPERAND_F16X2) CF_REQUIRE(!pq, "cf_conv2d(1x1, f16x2): no statistics epilogue");
+  if (d->taps == 1 && d->bf16_mfma == CF_OPERAND_F16X2)  // (a query without statistics, stats_cpg 0, goes on through the token GEMM's checks)
+    CF_REQUIRE(!pq || (!d->stats_cpg && (long)d->hout * d->wout <= CF_TOKEN_IMAGE_MAX), "cf_conv2d(1x1, f16x2): no statistics epilogue");
   else CF_REQUIRE(d->winograd >= 0 && d->winograd <= 2, "cf_conv2d: winograd must be 0, 1 (F(2x2,3x3)) or 2 (F(4x4,3x3)), got %d", d->winograd);
   const bool direct = !d->winograd && d->bf16_mfma != CF_OPERAND_F16X2;  // the kernels of this file (ext implies it)
   const int cp = d->cout_pad;
@@ -1504,7 +1505,7 @@ static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
     // images of more than CF_TOKEN_IMAGE_MAX pixels: the streaming 1x1 form of the split-half convolution kernel (weight: form 3 of
     // cf_pack_conv_weight_f16x2); token matrices (the Transformer's 16x16 "images"): the token GEMM (cf_pack_linear_weight_f16x2)
     if ((long)d->hout * d->wout > CF_TOKEN_IMAGE_MAX) return cf_split_launch(d, stream, pq);
-    return cf_gemm_split_launch(d, stream);
+    return cf_gemm_split_launch(d, stream, pq);
   }
   if (d->winograd == 2) return cf_wf43_launch(d, stream, pq);  // F(4x4,3x3), split-half operands (cf_wf43.hip)
   if (d->winograd) return cf_winograd_launch(d, stream, pq);   // F(2x2,3x3), fp32 or split-half operands
