@@ -345,14 +345,19 @@ class CodeFormer(VQAutoEncoder):
             self.fuse_convs_dict[f_size] = Fuse_sft_block(ch, ch)
 
     # ------------------------------------------------------------------ GPU (HIP) path
-    def _forward_hip(self, x, w, code_only, adain, f43_encoder=None, guard=False):
+    def _forward_hip(self, x, w, code_only, adain, f43_encoder=None, guard=False, u8=False, out_u8=None):
         """f43_encoder: the encoder's F(4x4,3x3) choice of THIS call (None: self.winograd_f43_encoder; the logit guard's second pass
         hands False down instead of flipping the attribute -- two threads may share a network).  guard: take the argmax on
-        cf_argmax_rows_gap and leave the per-face minimum top-2 gap in `last_min_gap` (with code_only too)."""
-        B, _, Himg, Wimg = x.shape
-        if (Himg, Wimg) != (512, 512):
-            raise ValueError(f'CodeFormer expects aligned 512x512 faces, got {Himg}x{Wimg}')
-        x = x.float().contiguous()
+        cf_argmax_rows_gap and leave the per-face minimum top-2 gap in `last_min_gap` (with code_only too).
+        u8 (restore_u8, which checked the tensors): x is the uint8 (B,512,512,3) BGR batch, read by the first conv, and the first returned
+        tensor is the uint8 (B,512,512,3) image the last conv wrote -- into out_u8 when given."""
+        if u8:
+            B = x.shape[0]
+        else:
+            B, _, Himg, Wimg = x.shape
+            if (Himg, Wimg) != (512, 512):
+                raise ValueError(f'CodeFormer expects aligned 512x512 faces, got {Himg}x{Wimg}')
+            x = x.float().contiguous()
         enc_feat = {}
         enc_taps = {self.fuse_encoder_block[f]: (lambda t: enc_feat.__setitem__(str(t.shape[2]), t))
                     for f in self.connect_list}
@@ -361,7 +366,7 @@ class CodeFormer(VQAutoEncoder):
         enc_code = ops.SPLIT if self.encoder_precision == 'f16x2' or (self.encoder_precision == 'auto' and self.precision != 'fp32') else ops.WINOGRAD
         if self.winograd_f43_encoder if f43_encoder is None else f43_encoder:
             enc_code = {ops.SPLIT: ops.SPLIT_F43, ops.WINOGRAD: ops.WINOGRAD_F43}[enc_code]
-        lq = self.encoder.forward_nhwc(x, enc_taps, bf16=enc_code)        # (B,16,16,256) channels-last
+        lq = self.encoder.forward_nhwc(x, enc_taps, bf16=enc_code, img_u8=u8)        # (B,16,16,256) channels-last
         T = lq.shape[1] * lq.shape[2]
         tokens = lq.view(B * T, lq.shape[3])
 
@@ -404,7 +409,10 @@ class CodeFormer(VQAutoEncoder):
                     enc = ops.to_bf16(enc)
                 return self.fuse_convs_dict[f].forward_nhwc(enc, t, w, bf16=bf16)
             gen_taps = {self.fuse_generator_block[f]: fuse for f in self.connect_list}
-        out = self.generator.forward_nhwc(quant, gen_taps, bf16=bf16, storage_bf16=bool(self.bf16_storage) and bf16 == 1)      # (B,3,512,512) NCHW
+        if u8 and out_u8 is None:
+            out_u8 = torch.empty((B, 512, 512, 3), dtype=torch.uint8, device=x.device)
+        out = self.generator.forward_nhwc(quant, gen_taps, bf16=bf16, storage_bf16=bool(self.bf16_storage) and bf16 == 1,
+                                          img_out=out_u8 if u8 else None)      # (B,3,512,512) NCHW, or the uint8 (B,512,512,3) image
         self.last_indices = idx.view(B, T)
         return out, logits, lq_feat
 
@@ -442,17 +450,19 @@ class CodeFormer(VQAutoEncoder):
                 x = self.fuse_convs_dict[f](enc_feat[f].detach(), x, w)
         return x, logits, lq_feat
 
-    def _forward_graphed(self, x, w, code_only, adain, guard=False):
+    def _forward_graphed(self, x, w, code_only, adain, guard=False, u8=False, out_u8=None):
         """Capture-once / replay-many execution of _forward_hip on the current stream.  Outputs are copies, so callers may
-        keep them across calls.  A graph is re-captured when any packed weight was rebuilt since its capture."""
+        keep them across calls.  A graph is re-captured when any packed weight was rebuilt since its capture.
+        u8: the uint8 form of _forward_hip -- the static input is the uint8 batch, the boundary form is part of the key, and the image
+        is copied into out_u8 when given."""
         with _GRAPH_LOCK:   # static buffers per shape: two threads replaying one graph would race on them
-            key = (tuple(x.shape), float(w), bool(code_only), bool(adain), self.precision, bool(self.bf16_storage), self.encoder_precision, self.gemm_precision, bool(self.winograd_f43_encoder), str(x.device), ops.switches(), bool(guard))
+            key = (tuple(x.shape), float(w), bool(code_only), bool(adain), self.precision, bool(self.bf16_storage), self.encoder_precision, self.gemm_precision, bool(self.winograd_f43_encoder), str(x.device), ops.switches(), bool(guard), bool(u8))
             ent = self._graphs.get(key)
             sig = self._param_signature()
             if ent is None or ent['epoch'] != PACK_EPOCH[0] or ent['sig'] != sig:
-                static_x = x.float().contiguous().clone()
+                static_x = x.clone() if u8 else x.float().contiguous().clone()
                 for _ in range(2):                      # warm-up: packs weights, sets kernel attributes, primes the allocator
-                    self._forward_hip(static_x, w, code_only, adain, guard=guard)
+                    self._forward_hip(static_x, w, code_only, adain, guard=guard, u8=u8)
                 torch.cuda.synchronize(x.device)
                 graph = torch.cuda.CUDAGraph()
                 # The zero-initialised scratch words of the range-scale / split-K kernels are kept per (device, stream).  Created inside the
@@ -470,7 +480,7 @@ class CodeFormer(VQAutoEncoder):
                 gc.disable()
                 try:
                     with torch.cuda.graph(graph, stream=cap):
-                        outs = self._forward_hip(static_x, w, code_only, adain, guard=guard)
+                        outs = self._forward_hip(static_x, w, code_only, adain, guard=guard, u8=u8)
                 finally:
                     if gc_on:
                         gc.enable()
@@ -486,6 +496,8 @@ class CodeFormer(VQAutoEncoder):
                 self.last_indices = ent['idx'].clone()   # (a fresh tensor per call, as the eager path returns: the next replay overwrites the graph's own)
             if ent['gap'] is not None:
                 self.last_min_gap = ent['gap'].clone()   # (the same ownership rule)
+            if out_u8 is not None:
+                return (out_u8.copy_(ent['outs'][0]),) + tuple(o.clone() for o in ent['outs'][1:])
             return tuple(o.clone() for o in ent['outs'])
 
     def _param_signature(self):
@@ -576,9 +588,9 @@ class CodeFormer(VQAutoEncoder):
             st['min_gap'] = _min_nan(st['min_gap'], float(gmin))
             pend.clear()
 
-    def _forward_guarded(self, x, w, code_only, adain, graphed):
+    def _forward_guarded(self, x, w, code_only, adain, graphed, u8=False, out_u8=None):
         guard = self.logit_guard
-        outs = (self._forward_graphed if graphed else self._forward_hip)(x, w, code_only, adain, guard=True)
+        outs = (self._forward_graphed if graphed else self._forward_hip)(x, w, code_only, adain, guard=True, u8=u8, out_u8=out_u8)
         gmin = self.last_min_gap
         if guard == 'report':
             st = self._guard_totals
@@ -594,7 +606,7 @@ class CodeFormer(VQAutoEncoder):
         sel = flag.nonzero().flatten().to(x.device)
         idx = self.last_indices
         # second pass: the flagged faces as one batch, eagerly (it neither captures a graph nor evicts one)
-        outs2 = self._forward_hip(x.index_select(0, sel), w, code_only, adain, f43_encoder=False, guard=True)
+        outs2 = self._forward_hip(x.index_select(0, sel), w, code_only, adain, f43_encoder=False, guard=True, u8=u8)
         st = self._guard_totals
         st['rerun_faces'] += int(sel.numel())
         st['index_changes'] += int((idx.index_select(0, sel) != self.last_indices).sum())
@@ -604,17 +616,47 @@ class CodeFormer(VQAutoEncoder):
         self.last_min_gap = gmin.index_copy_(0, sel, self.last_min_gap)
         return outs
 
+    def _forward_cuda(self, x, w, code_only, adain, **u8):
+        """The dispatch forward and restore_u8 share: graph replay by the use_hip_graphs / graph_max_batch rule, the logit guard, else eager."""
+        ops.L.ensure_device(x.device)   # kernel attributes on the tensor's device, before (never inside) a capture
+        with torch.no_grad(), torch.cuda.device(x.device):
+            graphed = self.use_hip_graphs is True or (self.use_hip_graphs == 'auto' and x.shape[0] <= self.graph_max_batch)
+            graphed = graphed and ops.PROFILE is None and not torch.cuda.is_current_stream_capturing()
+            if self.logit_guard != 'off':
+                return self._forward_guarded(x, w, code_only, adain, graphed, **u8)
+            if graphed:
+                return self._forward_graphed(x, w, code_only, adain, **u8)
+            return self._forward_hip(x, w, code_only, adain, **u8)
+
     def forward(self, x, w=0, detach_16=True, code_only=False, adain=False):
         if self.logit_guard not in ('off', 'report', 'rerun'):
             raise ValueError(f"logit_guard must be 'off', 'report' or 'rerun', got {self.logit_guard!r}")
         if x.is_cuda:
-            ops.L.ensure_device(x.device)   # kernel attributes on the tensor's device, before (never inside) a capture
-            with torch.no_grad(), torch.cuda.device(x.device):
-                graphed = self.use_hip_graphs is True or (self.use_hip_graphs == 'auto' and x.shape[0] <= self.graph_max_batch)
-                graphed = graphed and ops.PROFILE is None and not torch.cuda.is_current_stream_capturing()
-                if self.logit_guard != 'off':
-                    return self._forward_guarded(x, w, code_only, adain, graphed)
-                if graphed:
-                    return self._forward_graphed(x, w, code_only, adain)
-                return self._forward_hip(x, w, code_only, adain)
+            return self._forward_cuda(x, w, code_only, adain)
         return self._forward_host(x, w, detach_16, code_only, adain)
+
+    def restore_u8(self, faces, w=0.5, adain=True, out=None):
+        """uint8 (B,512,512,3) BGR aligned faces -> the restored faces in the same form: the bytes of
+        ops.tensor_to_img_u8(self(ops.img_u8_to_tensor(faces), w=w, adain=adain)[0]), with the conversions folded into the first and the
+        last conv (cf_conv2d_u8) -- no fp32 image tensor exists at either end.  Dispatch (graph replay, logit guard: 'rerun' replaces the
+        flagged faces' rows), `last_indices` and `last_min_gap` are those of forward.
+        out: a contiguous uint8 (B,512,512,3) destination on faces' device (e.g. a `[:m]` slice of a larger buffer); it is returned.
+        CPU tensors take the host path with the converters of utils/img_util.py."""
+        if self.logit_guard not in ('off', 'report', 'rerun'):
+            raise ValueError(f"logit_guard must be 'off', 'report' or 'rerun', got {self.logit_guard!r}")
+        for t, what in ((faces, 'faces'), (out, 'out')):
+            if t is None and what == 'out':
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 4 or tuple(t.shape[1:]) != (512, 512, 3) or not t.is_contiguous():
+                raise ValueError(f'restore_u8: {what} must be a contiguous uint8 (B,512,512,3) BGR tensor, got '
+                                 f'{(t.dtype, tuple(t.shape), t.stride()) if torch.is_tensor(t) else type(t)}')
+        if out is not None and (out.shape[0] != faces.shape[0] or out.device != faces.device):
+            raise ValueError(f'restore_u8: out is {tuple(out.shape)} on {out.device}, faces {tuple(faces.shape)} on {faces.device}')
+        if faces.is_cuda:
+            return self._forward_cuda(faces, w, False, adain, u8=True, out_u8=out)[0]
+        from ..utils.img_util import img2tensor, normalize_, tensor2img
+        with torch.no_grad():
+            x = torch.stack([normalize_(img2tensor(f / 255., bgr2rgb=True, float32=True), (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)) for f in faces.numpy()])
+            y = self._forward_host(x, w, True, False, adain)[0]
+            res = torch.stack([torch.from_numpy(tensor2img(y[i], rgb2bgr=True, min_max=(-1, 1))) for i in range(y.shape[0])])
+        return res if out is None else out.copy_(res)

@@ -269,7 +269,10 @@ class _Conv3x3(HipModule):
     def forward_nhwc(self, x, bf16=False, **kw):
         plain = not kw.get('out_nchw') and not kw.get('in_nchw')
         # operand code: 0 fp32 / 1 bf16 / 2 f16 / ops.WINOGRAD / ops.SPLIT, reduced to what this layer's shape supports
-        h, w = (x.shape[2], x.shape[3]) if kw.get('in_nchw') else (x.shape[1], x.shape[2])
+        if kw.get('img_in') is not None:    # the uint8 (B,H,W,3) image stands for the NCHW input (x is None)
+            h, w = kw['img_in'].shape[1], kw['img_in'].shape[2]
+        else:
+            h, w = (x.shape[2], x.shape[3]) if kw.get('in_nchw') else (x.shape[1], x.shape[2])
         unnormalised = plain and kw.get('prologue', ops.PRO_NONE) in (ops.PRO_NONE, ops.PRO_LEAKY)
         if unnormalised and int(bf16) == 2:
             bf16 = ops.SPLIT   # (single IEEE halves on the direct kernel have no range scaling; the split kernels do)
@@ -296,7 +299,7 @@ class _GroupNorm(nn.GroupNorm):
         return super().forward(x)
 
 
-def _run_blocks_nhwc(blocks, x, taps=None, first_nchw=False, last_nchw=False, bf16=False, storage_bf16=False):
+def _run_blocks_nhwc(blocks, x, taps=None, first_nchw=False, last_nchw=False, bf16=False, storage_bf16=False, img_in=False, img_out=None):
     """Execute a block list on channels-last activations, folding GroupNorm entries into the following conv.
 
     taps: optional {block index: callable(x)} invoked after that block (encoder feature taps / generator fusions;
@@ -305,6 +308,9 @@ def _run_blocks_nhwc(blocks, x, taps=None, first_nchw=False, last_nchw=False, bf
     ops.TOKEN_IMAGE_MAX pixels per image lives in HBM as bf16 (cf_conv_desc.io_bf16).  The switch happens in front of the first Upsample
     whose output is that large: its fp32 input (32x32) is copied to bf16 once (ops.to_bf16) and from there every kernel reads and writes
     bf16 -- the storage type of a launch is the dtype of its input tensor; the final 64 -> 3 conv writes the fp32 NCHW image.
+    img_in (with first_nchw): x is the uint8 (B,H,W,3) BGR image, read by the first conv as ops.img_u8_to_tensor(x) would present it.
+    img_out (with last_nchw): a uint8 (B,H,W,3) destination the last conv fills with what ops.tensor_to_img_u8 makes of its NCHW output;
+    it is returned (ops.conv2d: img_in / img_out).
     """
     pending = None
     n = len(blocks)
@@ -323,8 +329,12 @@ def _run_blocks_nhwc(blocks, x, taps=None, first_nchw=False, last_nchw=False, bf
                 pending = None
             if i == 0 and first_nchw:
                 kw['in_nchw'] = True
+                if img_in:
+                    x, kw['img_in'] = None, x
             if i == n - 1 and last_nchw:
                 kw['out_nchw'] = True
+                if img_out is not None:
+                    kw['img_out'] = img_out
             kw['emit_stats'] = i != n - 1      # every inner conv feeds a GroupNorm of the next block
             x = blk.forward_nhwc(x, bf16=code, **kw)
         else:
@@ -372,11 +382,12 @@ class Encoder(HipModule):
         with torch.no_grad():
             return ops.to_nchw(self.forward_nhwc(x.float().contiguous()))
 
-    def forward_nhwc(self, x_nchw, taps=None, bf16=False):
+    def forward_nhwc(self, x_nchw, taps=None, bf16=False, img_u8=False):
         """x_nchw: the (B,3,H,W) network input (read directly by the first conv); returns NHWC.
         bf16: operand code for the 3x3 convs (only 0 = direct fp32 or ops.WINOGRAD = fp32 Winograd make sense here: the code
-        indices depend on the encoder)."""
-        return _run_blocks_nhwc(self.blocks, x_nchw, taps, first_nchw=True, bf16=bf16)
+        indices depend on the encoder).
+        img_u8: x_nchw is the uint8 (B,H,W,3) BGR image instead -- the same activations, bitwise, as on ops.img_u8_to_tensor of it."""
+        return _run_blocks_nhwc(self.blocks, x_nchw, taps, first_nchw=True, bf16=bf16, img_in=img_u8)
 
     def forward_host(self, x):
         for blk in self.blocks:
@@ -419,10 +430,11 @@ class Generator(HipModule):
         with torch.no_grad():
             return self.forward_nhwc(ops.to_nhwc(x.float()))
 
-    def forward_nhwc(self, x, taps=None, bf16=False, storage_bf16=False):
+    def forward_nhwc(self, x, taps=None, bf16=False, storage_bf16=False, img_out=None):
         """x: (B,16,16,C) NHWC latent; returns the (B,3,H,W) NCHW image (written directly by the last conv).
-        bf16=True: every 3x3 conv except the final 64->3 one uses bf16 MFMA operands; storage_bf16: see _run_blocks_nhwc."""
-        return _run_blocks_nhwc(self.blocks, x, taps, last_nchw=True, bf16=bf16, storage_bf16=storage_bf16)
+        bf16=True: every 3x3 conv except the final 64->3 one uses bf16 MFMA operands; storage_bf16: see _run_blocks_nhwc.
+        img_out: a uint8 (B,H,W,3) destination -- the last conv writes the BGR bytes of ops.tensor_to_img_u8(image) there; returns it."""
+        return _run_blocks_nhwc(self.blocks, x, taps, last_nchw=True, bf16=bf16, storage_bf16=storage_bf16, img_out=img_out)
 
     def forward_host(self, x):
         for blk in self.blocks:

@@ -37,6 +37,16 @@ def tensor_to_faces(t):
     return [tensor2img(t[i], rgb2bgr=True, min_max=(-1, 1)) for i in range(t.shape[0])]
 
 
+def restore_faces(net, faces, device, w, adain):
+    """List of uint8 512x512x3 BGR faces -> list of restored uint8 faces: tensor_to_faces(net(faces_to_tensor(faces), w, adain)[0]), through
+    net.restore_u8 (bytes in, bytes out) when the network has it."""
+    if hasattr(net, 'restore_u8'):
+        with torch.no_grad():
+            return list(net.restore_u8(torch.from_numpy(np.stack(faces)).to(device, non_blocking=True), w=w, adain=adain).cpu().numpy())
+    with torch.no_grad():
+        return tensor_to_faces(net(faces_to_tensor(faces, device), w=w, adain=adain)[0])
+
+
 def inpaint_composite(x, y):
     """(1-mask)*x + mask*y with mask = pure-white input pixels (inference_inpainting.py:68-74)."""
     if x.is_cuda:

@@ -98,6 +98,20 @@ __device__ __forceinline__ void cf_store16(float* p, f32x4 v, bool nt) {
   else *reinterpret_cast<f32x4*>(p) = v;
 }
 
+// ---- the uint8 image boundary (cf_misc.hip: cf_img_u8_to_tensor / cf_tensor_to_img_u8; cf_igemm.hip: cf_conv2d_u8) ------------------------
+// byte k of a BGR image -> the network's input value: (float)((double)k / 255.) then (v - 0.5f) / 0.5f, the arithmetic of
+// img2tensor(img / 255.) + normalize (inference_codeformer.py:199-201).  Only 256 inputs exist: callers evaluate them once into an LDS table.
+__device__ __forceinline__ float cf_from_u8(int k) {
+  const float v = (float)((double)k / 255.0);
+  return (v - 0.5f) / 0.5f;
+}
+// network output value -> byte == tensor2img(min_max=(-1,1)): clamp, (v + 1) / 2, * 255, round half to even (img_util.py:66-90)
+__device__ __forceinline__ uint32_t cf_to_u8(float v) {
+  v = fminf(fmaxf(v, -1.0f), 1.0f);
+  v = (v - (-1.0f)) / (1.0f - (-1.0f));
+  return (uint32_t)(uint8_t)rintf(v * 255.0f);
+}
+
 // ---- bf16 STORAGE of activations (cf_conv_desc.io_bf16, ABI v22; precision 'bf16' of the network: BASELINE configs 3 / 5) ------------
 // A tensor element is the upper half of its fp32 value, rounded to nearest even ONCE, in the producing epilogue, after the GroupNorm
 // partials were taken from the fp32 values; consumers widen on load (a shift: exact).  Four channels = 8 bytes, eight = 16.

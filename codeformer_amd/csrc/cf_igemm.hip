@@ -15,6 +15,7 @@
 // is then reused by all 9 taps; the per-tap weight slab is double-buffered in LDS and prefetched
 // through registers while the MFMAs of the previous tap run.  Each wave accumulates a
 // (MI*32) x (NI*32) sub-tile in MI*NI*16 accumulator registers.
+#include <string.h>
 #include <type_traits>
 
 #include "cf_conv_parts.h"
@@ -873,8 +874,16 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
 // halo patch + prologue as the MFMA kernel, weights fetched through the scalar cache (wave-uniform addresses), coalesced
 // per-plane NCHW stores.  Accumulation order: slab, tap, channel (a plain fp32 FMA chain).
 // NCO = output channels evaluated per pixel (3 for the RGB head: the zero padding row of the packed weight is not multiplied through)
-template <int NCO, bool BIO = false>   // BIO: the input is a bf16 tensor (cf_conv_desc.io_bf16; the NCHW image stays fp32)
-__global__ __launch_bounds__(256) void conv3x3_few_cout_kernel(const ConvArgsExt a) {
+// U8 (cf_conv2d_u8, NCO = 3): the output is the uint8 HWC BGR image -- byte 2 - co of a pixel is cf_to_u8(acc[co] + bias[co]), what
+// cf_tensor_to_img_u8 makes of the NCHW planes.  A thread owns one pixel = three bytes: the tile's bytes go through `As` (free after the
+// K loop's last barrier; no LDS is added -- `As` sets the six resident workgroups per CU) as one 24-bit word per pixel, and 192 threads
+// write the sixteen 48-byte row segments as dwords.  `a.out` carries the image's address (the descriptor keeps float* fields).
+template <int NCO, bool BIO = false, bool U8 = false>   // BIO: the input is a bf16 tensor (cf_conv_desc.io_bf16; the NCHW image stays fp32)
+// (waves per SIMD: with the U8 epilogue the fp32-tensor instantiation needs 97 registers, one more than five waves allow; asked for five it
+// keeps 96 and holds two values in scratch around the K loop -- one store before it, one load after.  DESIGN.md section 7 has both builds'
+// timings.  1 is the default request: the instantiations without U8 are instruction for instruction what they were without the attribute.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(U8 ? 5 : 1))) void conv3x3_few_cout_kernel(const ConvArgsExt a) {
+  static_assert(!U8 || NCO == 3, "the uint8 image has three channels");
   constexpr int TH = 16, TW = 16, HWD = TW + 2, NPIX = (TH + 2) * HWD, APT = (NPIX * 4 + 255) / 256;
   __shared__ __attribute__((aligned(16))) float As[NPIX * CF_LDK];
   const int tid = threadIdx.x;
@@ -963,11 +972,35 @@ __global__ __launch_bounds__(256) void conv3x3_few_cout_kernel(const ConvArgsExt
       __syncthreads();
     }
   }
-  const int oy = y0 + py, ox = x0 + px;
+  if constexpr (U8) {
+    uint32_t* words = reinterpret_cast<uint32_t*>(As);   // [16 x 16 pixels]: B | G << 8 | R << 16
+    uint32_t w = 0;
 #pragma unroll
-  for (int co = 0; co < 4; ++co)
-    if (co < a.cout && oy < a.hout && ox < a.wout)
-      a.out[(((size_t)b * a.cout + co) * a.hout + oy) * a.wout + ox] = acc[co] + (a.bias ? a.bias[co] : 0.f);
+    for (int co = 0; co < 3; ++co) w |= cf_to_u8(acc[co] + (a.bias ? a.bias[co] : 0.f)) << (8 * (2 - co));
+    words[tid] = w;
+    __syncthreads();
+    if (tid < 16 * 12) {   // dword d of tile row `row`: bytes 4 d .. 4 d + 3 of its 48, from the pixels (4 d) / 3 and the next one
+      const int row = tid / 12, d = tid - row * 12, p = (4 * d) / 3, off = 4 * d - 3 * p;
+      const int nb = (a.wout - x0 < TW ? a.wout - x0 : TW) * 3 - 4 * d;   // bytes of this dword inside the image row
+      if (y0 + row < a.hout && nb > 0) {
+        const uint32_t v = (words[row * TW + p] >> (8 * off)) | (words[row * TW + p + 1] << (24 - 8 * off));   // (d = 11: p + 1 = 15)
+        uint8_t* g = reinterpret_cast<uint8_t*>(a.out) + (((size_t)b * a.hout + (y0 + row)) * a.wout + x0) * 3 + 4 * d;
+        // a row starts on the 4-byte grid only where (image base + row * wout * 3) % 4 == 0: elsewhere, and on a dword the image's right
+        // edge cuts, byte stores (as cf_tensor_to_img_u8 does for h * w % 4 != 0)
+        if (nb >= 4 && (reinterpret_cast<uintptr_t>(g) & 3) == 0) {
+          *reinterpret_cast<uint32_t*>(g) = v;
+        } else {
+          for (int k = 0; k < 4 && k < nb; ++k) g[k] = (uint8_t)(v >> (8 * k));
+        }
+      }
+    }
+  } else {
+    const int oy = y0 + py, ox = x0 + px;
+#pragma unroll
+    for (int co = 0; co < 4; ++co)
+      if (co < a.cout && oy < a.hout && ox < a.wout)
+        a.out[(((size_t)b * a.cout + co) * a.hout + oy) * a.wout + ox] = acc[co] + (a.bias ? a.bias[co] : 0.f);
+  }
 }
 
 // ---- 3x3 convolution of an NCHW input with <= 4 channels into 64 NHWC channels (the network's first conv, vqgan_arch.py:243) --------
@@ -980,8 +1013,13 @@ __global__ __launch_bounds__(256) void conv3x3_few_cout_kernel(const ConvArgsExt
 // the thread keeps the 27 float4 weight rows of ITS channel quad in registers for all sixteen pixels it computes: the LDS-resident
 // weights cost one ds_read_b128 per tap and pixel, 3456 LDS wave-instructions per tile = 0.31 of the kernel's 0.39 ms per 16 faces.
 // The FMA chain (channel-major, then taps) and with it every bit of the output is unchanged.
-template <int C0, bool NT = false>   // NT: non-temporal output stores (cf_common.h: cf_store16; a compile-time choice here -- sixteen stores per thread)
+// U8 (cf_conv2d_u8, C0 = 3): the input is the uint8 HWC BGR image, `a.in0` carries its address.  Only the fill of s_in differs: channel c
+// (0 = R) of a pixel is cf_from_u8 of its byte 2 - c, through a 256-entry LDS table as in cf_img_u8_to_tensor -- the values that kernel
+// would have written as fp32 NCHW, so output and statistics partials are bitwise those of the two launches.  Halo pixels outside the
+// image are 0.f, not cf_from_u8(0).
+template <int C0, bool NT = false, bool U8 = false>   // NT: non-temporal output stores (cf_common.h: cf_store16; a compile-time choice here -- sixteen stores per thread)
 __global__ __launch_bounds__(256) void conv3x3_few_cin_kernel(const ConvArgsExt a) {
+  static_assert(!U8 || C0 == 3, "the uint8 image has three channels");
   __shared__ float s_in[4][18 * 18];
   __shared__ __attribute__((aligned(16))) float s_w[36][64];  // [tap * 4 + c][n]
   const int tid = threadIdx.x;
@@ -995,13 +1033,27 @@ __global__ __launch_bounds__(256) void conv3x3_few_cin_kernel(const ConvArgsExt 
     const int nn = i & 63, tc = i >> 6, tap = tc >> 2, c = tc & 3;
     (&s_w[0][0])[i] = (c < a.c0 && nn < a.cout) ? a.weight[((size_t)tap * a.cout_pad + nn) * CF_BK + c] : 0.f;  // [tap][1 slab][cout_pad][16]
   }
-  const size_t plane = (size_t)a.hin * a.win;
-  for (int i = tid; i < 4 * 18 * 18; i += 256) {
-    const int c = i / (18 * 18), p = i - c * (18 * 18), hy = p / 18, hx = p - hy * 18;
-    const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
-    float v = 0.f;
-    if (c < a.c0 && iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win) v = a.in0[((size_t)b * a.c0 + c) * plane + (size_t)iy * a.win + ix];
-    s_in[c][p] = v;
+  if constexpr (U8) {
+    __shared__ float lut[256];
+    lut[tid] = cf_from_u8(tid);
+    __syncthreads();
+    const uint8_t* img = reinterpret_cast<const uint8_t*>(a.in0);
+    for (int i = tid; i < 18 * 18 * 3; i += 256) {   // the patch's bytes in image order: 18 row segments of 54 contiguous bytes
+      const int hy = i / 54, j = i - hy * 54, hx = j / 3, k = j - hx * 3;
+      const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
+      float v = 0.f;
+      if (iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win) v = lut[img[(((size_t)b * a.hin + iy) * a.win + ix) * 3 + k]];
+      s_in[2 - k][hy * 18 + hx] = v;   // (s_in[3] is never read with C0 = 3)
+    }
+  } else {
+    const size_t plane = (size_t)a.hin * a.win;
+    for (int i = tid; i < 4 * 18 * 18; i += 256) {
+      const int c = i / (18 * 18), p = i - c * (18 * 18), hy = p / 18, hx = p - hy * 18;
+      const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
+      float v = 0.f;
+      if (c < a.c0 && iy >= 0 && iy < a.hin && ix >= 0 && ix < a.win) v = a.in0[((size_t)b * a.c0 + c) * plane + (size_t)iy * a.win + ix];
+      s_in[c][p] = v;
+    }
   }
   __syncthreads();
   f32x4 wreg[C0 > 0 ? C0 * 9 : 1];
@@ -1412,7 +1464,7 @@ static int launch_ladder(const ConvArgsExt& a, bool narrow, bool exact64, hipStr
 }
 
 // The vector-ALU first conv (write-bound layer): 16x16 pixel tiles, four statistics partials per tile.
-static int launch_few_cin(ConvArgsExt& a, const cf_conv_desc* d, hipStream_t stream, int* pq) {
+static int launch_few_cin(ConvArgsExt& a, const cf_conv_desc* d, hipStream_t stream, int* pq, bool u8 = false) {
   a.tiles_x = d->wout / 16;
   a.tiles_per_img = a.tiles_x * (d->hout / 16);
   a.nparts = a.tiles_per_img * 4;
@@ -1420,20 +1472,22 @@ static int launch_few_cin(ConvArgsExt& a, const cf_conv_desc* d, hipStream_t str
     *pq = a.nparts;
     return CF_OK;
   }
-  const auto kern = d->c0 != 3 ? conv3x3_few_cin_kernel<0> : a.nt_out ? conv3x3_few_cin_kernel<3, true> : conv3x3_few_cin_kernel<3>;
+  auto kern = d->c0 != 3 ? conv3x3_few_cin_kernel<0> : a.nt_out ? conv3x3_few_cin_kernel<3, true> : conv3x3_few_cin_kernel<3>;
+  if (u8) kern = a.nt_out ? conv3x3_few_cin_kernel<3, true, true> : conv3x3_few_cin_kernel<3, false, true>;   // (c0 = 3: checked by cf_conv2d_u8)
   hipLaunchKernelGGL(kern, dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
-  CF_CHECK_LAUNCH("cf_conv2d");
+  CF_CHECK_LAUNCH(u8 ? "cf_conv2d_u8" : "cf_conv2d");
   return CF_OK;
 }
 
 // The vector-ALU NCHW <=4-channel output conv, any image size (edge tiles are masked).  No statistics: a parts query goes on to the next rung.
-static int launch_few_cout(ConvArgsExt& a, const cf_conv_desc* d, hipStream_t stream, int* pq) {
+static int launch_few_cout(ConvArgsExt& a, const cf_conv_desc* d, hipStream_t stream, int* pq, bool u8 = false) {
   if (pq) return CF_NOT_MINE;
   a.tiles_x = (d->wout + 15) / 16;
   a.tiles_per_img = a.tiles_x * ((d->hout + 15) / 16);
-  const auto kern = d->cout != 3 ? conv3x3_few_cout_kernel<4> : d->io_bf16 ? conv3x3_few_cout_kernel<3, true> : conv3x3_few_cout_kernel<3>;
+  auto kern = d->cout != 3 ? conv3x3_few_cout_kernel<4> : d->io_bf16 ? conv3x3_few_cout_kernel<3, true> : conv3x3_few_cout_kernel<3>;
+  if (u8) kern = d->io_bf16 ? conv3x3_few_cout_kernel<3, true, true> : conv3x3_few_cout_kernel<3, false, true>;   // (cout = 3: checked by cf_conv2d_u8)
   hipLaunchKernelGGL(kern, dim3(a.tiles_per_img * d->batch), dim3(256), 0, stream, a);
-  CF_CHECK_LAUNCH("cf_conv2d");
+  CF_CHECK_LAUNCH(u8 ? "cf_conv2d_u8" : "cf_conv2d");
   return CF_OK;
 }
 
@@ -1516,6 +1570,56 @@ static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
 }
 
 extern "C" int cf_conv2d(const cf_conv_desc* d, cf_stream_t stream) { return conv_dispatch(d, (hipStream_t)stream, nullptr); }
+
+// cf_conv2d with the uint8 HWC BGR image at one end: the two vector-ALU boundary kernels in their U8 forms, nothing else.  The image
+// pointer takes the place of d->in0 / d->out in a copy of the descriptor; the copy then passes every check of cf_conv2d, and the rules
+// by which launch_direct would have sent it to the same kernel are REQUIRED here, so the fp32 launch it stands for exists.
+// conv_validate for cf_conv2d_u8: the same checks, and a refusal of theirs names the export that was called.
+static int conv_validate_u8(const cf_conv_desc* u, ConvFacts& f) {
+  const int rc = conv_validate(u, nullptr, f);
+  if (rc != CF_OK) {
+    char msg[512];
+    snprintf(msg, sizeof(msg), "%s", cf_last_error());
+    if (!strncmp(msg, "cf_conv2d:", 10)) cf_set_error("cf_conv2d_u8:%s", msg + 10);
+  }
+  return rc;
+}
+extern "C" int cf_conv2d_u8(const cf_conv_desc* d, const uint8_t* img_in, uint8_t* img_out, cf_stream_t stream) {
+  CF_REQUIRE(d, "cf_conv2d_u8: null descriptor");
+  CF_REQUIRE(img_in || img_out, "cf_conv2d_u8: img_in and img_out are both NULL (exactly one of them is the image)");
+  CF_REQUIRE(!(img_in && img_out), "cf_conv2d_u8: img_in and img_out are both set (exactly one of them is the image)");
+  CF_REQUIRE(d->taps == 9 && d->stride == 1 && !d->upsample && d->bf16_mfma == CF_OPERAND_F32 && !d->winograd && d->c1 == 0 && d->split_k < 1,
+             "cf_conv2d_u8: needs a plain 3x3 stride-1 conv with fp32 operands (taps %d stride %d upsample %d operand %d winograd %d c1 %d split_k %d)",
+             d->taps, d->stride, d->upsample, d->bf16_mfma, d->winograd, d->c1, d->split_k);
+  CF_REQUIRE(d->epilogue == CF_EPI_NONE, "cf_conv2d_u8: no epilogue op at the image boundary (got %d)", d->epilogue);
+  cf_conv_desc u = *d;
+  ConvFacts f;
+  ConvArgsExt a;
+  if (img_in) {
+    CF_REQUIRE(d->in_nchw == 1 && !d->out_nchw, "cf_conv2d_u8: img_in stands for the NCHW input of an NHWC conv: needs in_nchw = 1 (got %d), out_nchw = 0 (got %d)",
+               d->in_nchw, d->out_nchw);
+    CF_REQUIRE(d->c0 == 3, "cf_conv2d_u8: img_in is a 3-channel BGR image: needs c0 = 3 (got %d)", d->c0);
+    CF_REQUIRE(d->cout == 64 && d->cout_pad == 64, "cf_conv2d_u8: img_in needs cout = cout_pad = 64 (got %d / %d)", d->cout, d->cout_pad);
+    CF_REQUIRE(d->hout % 16 == 0 && d->wout % 16 == 0, "cf_conv2d_u8: img_in needs hout, wout multiples of 16 (got %dx%d)", d->hout, d->wout);
+    CF_REQUIRE(d->prologue == CF_PRO_NONE && !d->io_bf16 && d->pad_mode == CF_PAD_ZERO && (!d->stats_cpg || d->stats_cpg == 2),
+               "cf_conv2d_u8: img_in takes no prologue, fp32 tensors, zero padding, stats_cpg 0 or 2 (prologue %d io_bf16 %d pad_mode %d stats_cpg %d)",
+               d->prologue, d->io_bf16, d->pad_mode, d->stats_cpg);
+    u.in0 = reinterpret_cast<const float*>(img_in);
+    if (const int rc = conv_validate_u8(&u, f); rc != CF_OK) return rc;
+    CF_REQUIRE(!f.ext, "cf_conv2d_u8: img_in needs a dense output (ld_out %d)", d->ld_out);
+    conv_fill_args(a, &u, f);
+    return launch_few_cin(a, &u, (hipStream_t)stream, nullptr, true);
+  }
+  CF_REQUIRE(d->out_nchw == 1 && !d->in_nchw, "cf_conv2d_u8: img_out stands for the NCHW output of an NHWC conv: needs out_nchw = 1 (got %d), in_nchw = 0 (got %d)",
+             d->out_nchw, d->in_nchw);
+  CF_REQUIRE(d->cout == 3 && d->cout_pad == 32, "cf_conv2d_u8: img_out is a 3-channel BGR image: needs cout = 3, cout_pad = 32 (got %d / %d)", d->cout, d->cout_pad);
+  CF_REQUIRE((d->io_bf16 == 0 || d->io_bf16 == 1) && !d->stats_out, "cf_conv2d_u8: img_out needs io_bf16 0 or 1 (got %d) and no statistics", d->io_bf16);
+  u.out = reinterpret_cast<float*>(img_out);
+  if (const int rc = conv_validate_u8(&u, f); rc != CF_OK) return rc;
+  CF_REQUIRE(f.few_cout && !f.ext, "cf_conv2d_u8: img_out needs a dense input (ld_in0 %d, c0 %d)", d->ld_in0, d->c0);
+  conv_fill_args(a, &u, f);
+  return launch_few_cout(a, &u, (hipStream_t)stream, nullptr, true);
+}
 
 // split-K geometry: output tiles of the launch and accumulator bytes one (tile, split) parks in the workspace
 static int splitk_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_part) {

@@ -279,10 +279,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void img_u8_to_tensor_kernel(const uint8_t* __restrict__ img, int hw, float* __restrict__ out,
                                                                long nquads, int batch) {
   __shared__ float lut[256];
-  {
-    const float v = (float)((double)threadIdx.x / 255.0);
-    lut[threadIdx.x] = (v - 0.5f) / 0.5f;
-  }
+  lut[threadIdx.x] = cf_from_u8(threadIdx.x);   // (cf_common.h: the one definition, shared with the first conv's uint8 form)
   __syncthreads();
   const int qpi = (hw + 3) >> 2;  // quads per image (the last one may be partial)
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nquads; i += (long)gridDim.x * blockDim.x) {
@@ -308,12 +305,7 @@ __global__ __launch_bounds__(256) void img_u8_to_tensor_kernel(const uint8_t* __
 }
 
 // fp32 NCHW RGB -> u8 HWC BGR == tensor2img(min_max=(-1,1)): clamp, (v + 1) / 2, * 255, round half to even (img_util.py:66-90);
-// four pixels per thread: one 16-byte load per colour plane, three 4-byte stores of the interleaved bytes.
-__device__ __forceinline__ uint32_t cf_to_u8(float v) {
-  v = fminf(fmaxf(v, -1.0f), 1.0f);
-  v = (v - (-1.0f)) / (1.0f - (-1.0f));
-  return (uint32_t)(uint8_t)rintf(v * 255.0f);
-}
+// (cf_to_u8, cf_common.h); four pixels per thread: one 16-byte load per colour plane, three 4-byte stores of the interleaved bytes.
 __global__ __launch_bounds__(256) void tensor_to_img_u8_kernel(const float* __restrict__ t, int hw, uint8_t* __restrict__ img,
                                                                long nquads) {
   const int qpi = (hw + 3) >> 2;

@@ -536,7 +536,8 @@ def _roofline_kind(pw, io, stride, upsample, c0, in_nchw, out_nchw, out_pixels, 
 
 def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale=None, shift=None,
            epilogue=EPI_NONE, res=None, sft_scale=None, sft_w=0.0, in_nchw=False, out_nchw=False, emit_stats=False,
-           out=None, pad_mode=PAD_ZERO, pad_lo=0, split_k=None, act=None, x_alt=None, alt_from=0, stats_into=None):
+           out=None, pad_mode=PAD_ZERO, pad_lo=0, split_k=None, act=None, x_alt=None, alt_from=0, stats_into=None,
+           img_in=None, img_out=None):
     """Implicit-GEMM conv (3x3 / 1x1).  x: (B,H,W,C0) [x2: (B,H,W,C1) concatenated after x]; returns (B,Ho,Wo,cout)
     (or (B,cout,Ho,Wo) when out_nchw).  With in_nchw, x is (B,C<=4,H,W).
     emit_stats: also write the GroupNorm(32) partial statistics of the output in the epilogue and attach them to the
@@ -550,21 +551,37 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     stats_into: a StatsPair -- the statistics partials of this launch go into its shared buffer (two sibling convolutions whose range-scale
     tables are then ONE launch: act_scale_pair).
     x_alt / alt_from (split-half token GEMMs only): output columns >= alt_from read their rows from x_alt (same shape as x) -- two Linear
-    layers on two token matrices in one launch (q|k on LN(x) + pos, v on LN(x))."""
+    layers on two token matrices in one launch (q|k on LN(x) + pos, v on LN(x)).
+    img_in / img_out (cf_conv2d_u8): the uint8 (B,H,W,3) BGR image at one end of the network.  img_in stands for x (pass x=None): the
+    launch is the in_nchw one on img_u8_to_tensor(img_in), bitwise, statistics included.  img_out is the destination and is returned:
+    the bytes tensor_to_img_u8 makes of the out_nchw launch's planes.  Both are contiguous CUDA tensors; any other dtype is refused."""
     lib = L.load()
-    io = _act_dtype(x, 'x')            # float32, or bfloat16 = bf16 storage of every activation of the launch (io_bf16)
-    if in_nchw:
+    u8_in = u8_out = None
+    if img_in is not None and img_out is not None:
+        raise ValueError('conv2d: img_in and img_out belong to two different layers (the first and the last conv)')
+    for t, what in ((img_in, 'img_in'), (img_out, 'img_out')):
+        if t is not None and (t.dim() != 4 or t.shape[3] != 3):
+            raise ValueError(f'{what}: expected a uint8 (B,H,W,3) BGR image, got shape {tuple(t.shape)}')
+    if img_in is not None:
+        if x is not None or not in_nchw:
+            raise ValueError('img_in stands for the NCHW input: pass x=None and in_nchw=True')
+        u8_in = L.ptr(img_in, dtype=torch.uint8)
+        B, H, W, c0 = img_in.shape
+        io, ld0, dev = torch.float32, 0, img_in.device
+    elif in_nchw:
+        io, dev = _act_dtype(x, 'x'), x.device
         _f32(x)
         B, c0, H, W = x.shape
         ld0 = 0
         if not x.is_contiguous():
             raise ValueError('in_nchw input must be contiguous')
     else:
+        io, dev = _act_dtype(x, 'x'), x.device            # float32, or bfloat16 = bf16 storage of every activation of the launch (io_bf16)
         B, H, W, c0 = x.shape
         ld0 = _nhwc_ld(x, 'x')
     c1 = ld1 = 0
     if x2 is not None:
-        if x2.shape[:3] != x.shape[:3]:
+        if img_in is not None or x2.shape[:3] != x.shape[:3]:
             raise ValueError('x2 spatial shape mismatch')
         c1 = x2.shape[3]
         if x2.dtype != io:
@@ -587,11 +604,16 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     shape = (B, pw.cout, Ho, Wo) if out_nchw else (B, Ho, Wo, pw.cout)
     ldo = 0
     odt = torch.float32 if out_nchw else io      # (the NCHW network output stays fp32)
-    if out is None:
-        out = torch.empty(shape, dtype=odt, device=x.device)
+    if img_out is not None:
+        if not out_nchw or out is not None or tuple(img_out.shape) != (B, Ho, Wo, pw.cout) or img_out.device != dev:
+            raise ValueError(f'img_out stands for the NCHW output: pass out_nchw=True, no out, and a uint8 {(B, Ho, Wo, 3)} image on {dev}')
+        u8_out = L.ptr(img_out, dtype=torch.uint8)
+        out = img_out
+    elif out is None:
+        out = torch.empty(shape, dtype=odt, device=dev)
     else:
-        if tuple(out.shape) != shape or out.dtype != odt or out.device != x.device:
-            raise ValueError(f'out: expected {odt} {shape} on {x.device}')
+        if tuple(out.shape) != shape or out.dtype != odt or out.device != dev:
+            raise ValueError(f'out: expected {odt} {shape} on {dev}')
         if out_nchw:
             if not out.is_contiguous():
                 raise ValueError('out_nchw destination must be contiguous')
@@ -608,11 +630,11 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
         if t is not None and tuple(t.shape) != (B, c0 + c1):
             raise ValueError(f'prologue table shape {tuple(t.shape)} != {(B, c0 + c1)}')
     d = L.ConvDesc(
-        in0=L.ptr(x, not in_nchw, dtype=io), in1=L.ptr(x2, True, dtype=io), c0=c0, c1=c1, batch=B, hin=H, win=W, hout=Ho, wout=Wo, cout=pw.cout,
+        in0=None if img_in is not None else L.ptr(x, not in_nchw, dtype=io), in1=L.ptr(x2, True, dtype=io), c0=c0, c1=c1, batch=B, hin=H, win=W, hout=Ho, wout=Wo, cout=pw.cout,
         cout_pad=pw.cout_pad, taps=pw.taps, stride=stride, upsample=int(bool(upsample)), in_nchw=int(bool(in_nchw)),
         out_nchw=int(bool(out_nchw)), prologue=prologue, epilogue=epilogue, pro_scale=L.ptr(scale),
         pro_shift=L.ptr(shift), weight=L.ptr(pw.w, dtype=None), bias=L.ptr(pw.bias), res=L.ptr(res, True, dtype=io),
-        sft_scale=L.ptr(sft_scale, True, dtype=io), sft_w=float(sft_w), out=L.ptr(out, not out_nchw, dtype=odt), bf16_mfma=int(pw.bf16),
+        sft_scale=L.ptr(sft_scale, True, dtype=io), sft_w=float(sft_w), out=None if img_out is not None else L.ptr(out, not out_nchw, dtype=odt), bf16_mfma=int(pw.bf16),
         ld_in0=ld0, ld_in1=ld1, ld_out=ldo, pad_mode=int(pad_mode), pad_lo=int(pad_lo), winograd=int(pw.wino),
         acc_scale=1.0 / pw.scale, io_bf16=int(io == torch.bfloat16))
     if x_alt is not None:
@@ -632,24 +654,31 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
             nbytes, tiles = lib.cf_conv2d_workspace_bytes(ctypes.byref(d)), lib.cf_conv2d_tiles(ctypes.byref(d))
             if nbytes < 0 or tiles <= 0:
                 raise RuntimeError(f'cf_conv2d_workspace_bytes failed: {L.last_error()}')
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-            d.workspace, d.counters = L.ptr(ws), L.ptr(_counters(x.device, tiles), dtype=torch.int32)
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+            d.workspace, d.counters = L.ptr(ws), L.ptr(_counters(dev, tiles), dtype=torch.int32)
     if emit_stats and not out_nchw and pw.cout % GN_GROUPS == 0 and pw.cout // GN_GROUPS >= 2:
         d.stats_cpg = pw.cout // GN_GROUPS
         parts = lib.cf_conv2d_stats_parts(ctypes.byref(d))
         if parts <= 0:
             raise RuntimeError(f'cf_conv2d_stats_parts failed ({parts}): {L.last_error()}')
         n_part = B * GN_GROUPS * parts * 2
-        part = torch.empty(n_part, dtype=torch.float64, device=x.device) if stats_into is None else stats_into.take(n_part, x.device)
+        part = torch.empty(n_part, dtype=torch.float64, device=dev) if stats_into is None else stats_into.take(n_part, dev)
         d.stats_out = L.ptr(part, dtype=torch.float64)
         out._cf_stats = GNStats(part, parts, d.stats_cpg)
+
+    def launch():
+        if u8_in is None and u8_out is None:
+            L.check(lib.cf_conv2d(ctypes.byref(d), L.stream_ptr()), 'cf_conv2d')
+        else:      # the same descriptor; the image pointer takes the place of in0 / out
+            L.check(lib.cf_conv2d_u8(ctypes.byref(d), u8_in, u8_out, L.stream_ptr()), 'cf_conv2d_u8')
     if PROFILE is None:
-        L.check(lib.cf_conv2d(ctypes.byref(d), L.stream_ptr()), 'cf_conv2d')
+        launch()
         return out
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    L.check(lib.cf_conv2d(ctypes.byref(d), L.stream_ptr()), 'cf_conv2d')
+    launch()
     e1.record()
+    x = img_in if img_in is not None else x
     cin = c0 + c1
     flops = 2.0 * B * Ho * Wo * pw.cout * cin * (4 if (upsample and not pw.wino) else pw.taps)   # executed MACs (folded taps for up2x); Winograd
     # launches are booked at the direct convolution's 9 taps (the algorithmic work), not at their 4 MFMA multiplies per output

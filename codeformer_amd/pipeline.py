@@ -2,8 +2,9 @@
 
 The reference restores one face per forward and pays, per face, two host passes over the pixels (img2tensor + normalize,
 tensor2img), a blocking device->host copy and `torch.cuda.empty_cache()` (inference_codeformer.py:197-206).  Here a batch moves as
-    decode (worker pool) -> pinned uint8 staging -> H2D on a copy stream -> cf_img_u8_to_tensor -> CodeFormer.forward ->
-    cf_tensor_to_img_u8 -> D2H on a second copy stream into pinned uint8 staging -> encode + write (worker pool)
+    decode (worker pool) -> pinned uint8 staging -> H2D on a copy stream -> CodeFormer.restore_u8 (uint8 faces in, uint8 faces out,
+    written into the slot; a network without it: cf_img_u8_to_tensor -> forward -> cf_tensor_to_img_u8) -> D2H on a second copy stream
+    into pinned uint8 staging -> encode + write (worker pool)
 with a ring of staging slots, so that while batch k is on the GPU the pool already decodes batch k+1.. and still encodes batch k-1.
 Only uint8 crosses PCIe (0.79 MB per face each way instead of 3.1 MB of fp32) and the compute stream never waits for the host.
 
@@ -100,16 +101,18 @@ class AlignedFacePipeline:
                     slot.ev_in.record(self.h2d)
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(slot.ev_in)
-                x = ops.img_u8_to_tensor(slot.dev_in[:m])
                 try:
-                    out = self.net(x, w=w, adain=adain)[0]
+                    if hasattr(self.net, 'restore_u8'):      # bytes in, bytes out: the first / last conv read / write the uint8 faces,
+                        self.net.restore_u8(slot.dev_in[:m], w=w, adain=adain, out=slot.dev_out[:m])   # straight into the slot
+                    else:                                    # (a network with the call signature only)
+                        out = self.net(ops.img_u8_to_tensor(slot.dev_in[:m]), w=w, adain=adain)[0]
+                        slot.dev_out[:m].copy_(ops.tensor_to_img_u8(out))
                 except Exception as error:  # noqa: BLE001 -- the reference prints the error and returns the input face
                     if strict:
                         raise
                     print(f'\tFailed inference for CodeFormer: {error}')
                     stats['failures'] += m
-                    out = x
-                slot.dev_out[:m].copy_(ops.tensor_to_img_u8(out))
+                    slot.dev_out[:m].copy_(ops.tensor_to_img_u8(ops.img_u8_to_tensor(slot.dev_in[:m])))
                 slot.ev_done.record(cur)
                 with torch.cuda.stream(self.d2h):
                     self.d2h.wait_event(slot.ev_done)

@@ -88,8 +88,11 @@ class VideoRestorer:
 
         def run(items):
             nonlocal calls, faces, up_calls
-            x = ops.img_u8_to_tensor(torch.stack([c for _, _, c in items]))
-            y = ops.tensor_to_img_u8(self.net(x, w=w, adain=adain)[0])
+            crops = torch.stack([c for _, _, c in items])
+            if hasattr(self.net, 'restore_u8'):          # bytes in, bytes out (a network with the call signature only: the converters)
+                y = self.net.restore_u8(crops, w=w, adain=adain)
+            else:
+                y = ops.tensor_to_img_u8(self.net(ops.img_u8_to_tensor(crops), w=w, adain=adain)[0])
             calls += 1
             faces += len(items)
             yu = None

@@ -207,6 +207,14 @@ typedef struct cf_conv_desc {
 } cf_conv_desc;
 
 int cf_conv2d(const cf_conv_desc* d, cf_stream_t stream);
+/* cf_conv2d with a uint8 HWC BGR image at either end of the network: the image is read by the first conv / written by the last one,
+   bitwise what cf_img_u8_to_tensor + cf_conv2d / cf_conv2d + cf_tensor_to_img_u8 give (output tensor, statistics partials, bytes).
+   img_in  != NULL: replaces d->in0; needs in_nchw = 1, c0 = 3, taps 9, stride 1, fp32 operands, cout = cout_pad = 64,
+                    hout, wout multiples of 16, no prologue / epilogue (the shapes conv3x3_few_cin takes today).
+   img_out != NULL: replaces d->out; needs out_nchw = 1, cout = 3 (cout_pad 32), taps 9, stride 1, fp32 operands, no epilogue,
+                    a dense input (io_bf16 0 or 1).
+   Exactly one of the two is non-NULL.  Anything else: CF_ERR_ARG, nothing launched. */
+int cf_conv2d_u8(const cf_conv_desc* d, const uint8_t* img_in, uint8_t* img_out, cf_stream_t stream);
 /* number of statistics partials per (image, group) the launch described by d will write (>0), or <0 on error */
 int cf_conv2d_stats_parts(const cf_conv_desc* d);
 /* split-K launches: bytes of workspace / number of output tiles (= counters) the launch described by d needs (0 when split_k <= 1) */

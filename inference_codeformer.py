@@ -28,7 +28,7 @@ from basicsr.utils.download_util import load_file_from_url  # noqa: E402
 from basicsr.utils.img_util import imread_bgr, resize_bilinear  # noqa: E402
 from basicsr.utils.misc import get_device  # noqa: E402
 from basicsr.utils.registry import ARCH_REGISTRY  # noqa: E402
-from codeformer_amd.cli import add_logit_guard_arg, apply_logit_guard, faces_to_tensor, guard_summary, tensor_to_faces  # noqa: E402
+from codeformer_amd.cli import add_logit_guard_arg, apply_logit_guard, faces_to_tensor, guard_summary, restore_faces, tensor_to_faces  # noqa: E402
 from codeformer_amd.utils.face_misc import AlignedFaceHelper, is_gray  # noqa: E402
 
 pretrain_model_url = {
@@ -344,16 +344,14 @@ def main(argv=None):
                 print('Grayscale input: True')
             faces.append(img)
             grays.append(g)
-        x = faces_to_tensor(faces, device)
         try:
-            with torch.no_grad():
-                restored = tensor_to_faces(net(x, w=w, adain=True)[0])
+            restored = restore_faces(net, faces, device, w, True)
         except Exception as error:  # the reference swallows the error and returns the input face (F7)
             if args.strict:
                 raise
             print(f'\tFailed inference for CodeFormer: {error}')
             failures += len(faces)
-            restored = tensor_to_faces(x)
+            restored = tensor_to_faces(faces_to_tensor(faces, device))
         for img_path, face, out, g in zip(chunk, faces, restored, grays):
             imwrite(finish_face(face, out, g), out_name(img_path))
     if guard_summary(net):

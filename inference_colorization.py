@@ -39,13 +39,12 @@ def main(argv=None):
         chunk = paths[s:s + bs]
         for j, q in enumerate(chunk):
             print(f'[{s + j + 1}/{len(paths)}] Processing: {os.path.basename(q)}')
-        x = cli.faces_to_tensor(cli.load_faces(chunk, size=(512, 512)), device)
+        crops = cli.load_faces(chunk, size=(512, 512))
         try:
-            with torch.no_grad():
-                faces = cli.tensor_to_faces(net(x, w=0, adain=True)[0])
+            faces = cli.restore_faces(net, crops, device, 0, True)
         except Exception as error:
             print(f'\tFailed inference for CodeFormer: {error}')
-            faces = cli.tensor_to_faces(x)
+            faces = cli.tensor_to_faces(cli.faces_to_tensor(crops, device))
         for q, face in zip(chunk, faces):
             base = os.path.splitext(os.path.basename(q))[0]
             if args.suffix is not None:
