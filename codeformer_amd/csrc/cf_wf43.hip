@@ -2,6 +2,7 @@
 //   <PRO, EPI, 8, 16>   64 output channels per eight-wave workgroup, TWO workgroups per CU (the text below describes this form)
 //   <PRO, EPI, 16, 32>  128 output channels per sixteen-wave workgroup on 32-channel slabs (see "The 16-wave form" at the end)
 //   <PRO, EPI, 16, 16>  the same on 16-channel slabs (cin % 32 != 0)
+// and, on the stages of <NONE, NONE, 16, 32> with fp32 operands, the Upsample blocks as four F(4x4,2x2) sub-pixel phases (see "UP" at the kernel)
 //
 // Serves 3x3 stride-1 convolutions of generator and fusion (CFT) blocks (vqgan_arch.py:141-164,296-323, codeformer_arch.py:136-157) and,
 // since round 5, the encoder's covered layers (vqgan_arch.py:243-262) -- the encoder decides the code indices, so that use sits behind a
@@ -155,13 +156,32 @@ __device__ __forceinline__ unsigned f4_vu(unsigned lq, unsigned p, unsigned t) {
 // weight stream of slab s: bitwise the two-interval <., ., 16, 16> form, 4-13 % fewer cycles per patch and the same launch time at the
 // power cap, split-half operands in round 5 and fp32 operands in round 6 (profiles/r05_f43_ovl_stage_timing.txt, r06_f43_fp32_stage_timing.txt).
 // It is not part of the library; commit beb776c holds its source.)
-// UP (round 6; fp32 operands, no prologue / epilogue operand: the Upsample blocks of precision 'fp32', vqgan_arch.py:129-138): the convolution reads
-// the NEAREST-x2 UPSAMPLED image without it ever existing -- halo pixel (iy, ix) of the (h x w) grid is source pixel (iy >> 1, ix >> 1) of the
-// (h/2 x w/2) tensor; zero padding, patch layout, transforms and everything behind the gather are those of the plain form.  2.25 products per
-// output and input channel instead of the 4 of the folded sub-pixel form (cf_igemm.hip TAPS = 4), which the fp32 pipe executes one by one.
-template <int PRO, int EPI, int NW, int KS, bool F32, bool UP = false>
+// UPF = 1, GUP (round 6; fp32 operands, no prologue / epilogue operand): the convolution reads the NEAREST-x2 UPSAMPLED image without it ever existing
+// -- halo pixel (iy, ix) of the (h x w) grid is source pixel (iy >> 1, ix >> 1) of the (h/2 x w/2) tensor; zero padding, patch layout, transforms and
+// everything behind the gather are those of the plain form: 2.25 products per output.  Kept for a plain F(4,3) packing given to an upsampling launch
+// (cf_conv_desc.upsample == 1): its tile geometry is what tests/test_gpu_conv_families.py pins for that packing.  The network runs UPF = 2.
+// UPF = 2, UP (fp32 operands on 32-channel slabs, no prologue / epilogue operand: the Upsample blocks of precision 'fp32', vqgan_arch.py:129-138): nearest-x2
+// + 3x3 is four 2x2 convolutions of the LOW-RESOLUTION image, one per output parity (pa, pb) -- along an axis the taps g0 g1 g2 fold to
+// [g0, g1 + g2] on rows i - 1, i (parity 0) or [g0 + g1, g2] on rows i, i + 1 (parity 1) -- and a 2x2 kernel has the Winograd form F(4x4,2x2):
+//   Y = A42^T [ (G42 g_p G42^T) (.) (B42^T d B42) ] A42      d: 5x5 window, Y: 4x4 outputs of one phase, points (0, -1, 1/2, 2, inf)
+//   B42^T = [ 1 -1.5 -1.5 1 0 ;  0 1 -2.5 1 0 ;  0 -2 -1 1 0 ;  0 -.5 .5 1 0 ;  0 1 -1.5 -1.5 1 ]
+//   G42   = [ 1 0 ; -2/9 2/9 ; -8/9 -4/9 ; 1/9 2/9 ; 0 1 ]          A42^T = [ 1 1 1 1 0 ;  0 -1 .5 2 0 ;  0 1 .25 4 0 ;  0 -1 .125 8 1 ]
+// (the set with the smallest error among those tools/winograd_f42_numerics.py compares; every entry of B42^T and A42^T is exact in fp32):
+// 25 positions xi * 5 + nu per 16 outputs = 1.5625 products per output and input channel instead of the 2.25 of F(4,3) on the upsampled image.
+// A workgroup owns ONE phase of a 16x16 block of low-resolution positions (a.h x a.w is the low-resolution image): 256 outputs at (2 i + pa,
+// 2 j + pb).  Within an image the workgroups are ordered phase-major (rt = phase * blocks + block), so neighbours stream the same weights; an
+// image has 4 x blocks workgroups = the 16x16 patches of its output, one GroupNorm partial each.  The halo patch starts at (y0 - 1 + pa,
+// x0 - 1 + pb): tile (ty, tx) then transforms rows / columns 4 t .. 4 t + 4 of the patch with the addressing of the plain form (row and column
+// 17 of the patch are loaded and not read), and zero padding of the low-resolution image is the padding of the upsampled one.  Waves 0..3
+// transform xi 0..2, waves 4..7 xi 3, 4; the M interval splits the positions 13 / 12 over the two position halves of the waves.
+template <int PRO, int EPI, int NW, int KS, bool F32, int UPF = 0>
 __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
-  static_assert(!UP || (F32 && PRO == CF_PRO_NONE && EPI == CF_EPI_NONE), "the upsampling gather: fp32 operands, no prologue, no epilogue operand");
+  constexpr bool UP = UPF == 2;                  // the sub-pixel F(4,2) form
+  constexpr bool GUP = UPF == 1;                 // the upsampling gather of F(4,3)
+  static_assert(UPF == 0 || (F32 && NW == 16 && KS == 32 && PRO == CF_PRO_NONE && EPI == CF_EPI_NONE), "the upsampling forms: fp32 operands on 32-channel slabs, no prologue, no epilogue operand");
+  constexpr int NPW = UP ? 13 : 18;              // transform-domain positions of a wave (UP: 13 of the lower half, 12 of the upper)
+  constexpr int NXI = UP ? 5 : 6;                // positions per xi
+  constexpr int OS = UP ? 2 : 1;                 // output pixels between the outputs of a workgroup
   static_assert(KS == 16 || (KS == 32 && NW == 16), "32-channel slabs need the LDS of the 16-wave form");
   constexpr int F4_THREADS = NW * 64;
   constexpr int F4_BN = NW * 8;                  // output channels per workgroup
@@ -189,9 +209,13 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   const int n0 = ntile * F4_BN;
   const int b = mt / a.tiles_per_img;
   const int rt = mt - b * a.tiles_per_img;
-  const int tyw = rt / a.tiles_x;
+  const int blocks = a.tiles_per_img >> 2;                  // UP: 16x16 blocks of the low-resolution image
+  const int phase = UP ? rt / blocks : 0;
+  const int pa = phase >> 1, pb = phase & 1;                // UP: output parity of this workgroup
+  const int blk = UP ? rt - phase * blocks : rt;
+  const int tyw = blk / a.tiles_x;
   const int y0 = tyw * F4_TH;
-  const int x0 = (rt - tyw * a.tiles_x) * F4_TW;
+  const int x0 = (blk - tyw * a.tiles_x) * F4_TW;
   const int n = a.cin / KS;   // slabs
 
   constexpr bool affine = PRO == CF_PRO_AFFINE || PRO == CF_PRO_AFFINE_SWISH;
@@ -211,14 +235,15 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   // p < 324: pixel (hy, hx) = (p / 18, p % 18); padding items (p >= 324, item 5 of most threads) and pixels outside the image are loaded
   // from the patch's centre pixel and stored as zeros (padding items: not stored).  The LDS slot of item j is that of item 0 plus 64 j
   // (the swizzle repeats every 16 slots): one address + immediates.
-  const int pix_origin = (y0 - 1) * a.w + (x0 - 1);  // (wave-uniform; negative on the top / left border: only invalid items would use it there)
+  const int py0 = y0 - 1 + pa, px0 = x0 - 1 + pb;     // halo origin (UP: moved by the phase, see above)
+  const int pix_origin = py0 * a.w + px0;            // (wave-uniform; negative on the top / left border: only invalid items would use it there)
   auto item = [&](unsigned u, int j, unsigned& rel, bool& valid) __attribute__((always_inline)) {
     const unsigned p = u + (unsigned)(PSTEP * j);
     const unsigned hy = (p * 3641u) >> 16;  // p / 18 for p < 1024
     const unsigned hx = p - 18u * hy;
-    const int iy = y0 - 1 + (int)hy, ix = x0 - 1 + (int)hx;
+    const int iy = py0 + (int)hy, ix = px0 + (int)hx;
     valid = (int)(p < (unsigned)F4_NPIX) & (int)((unsigned)iy < (unsigned)a.h) & (int)((unsigned)ix < (unsigned)a.w);  // (no short circuit: no branches)
-    if constexpr (UP) {   // `rel` = the SOURCE pixel's index in its (h/2 x w/2) image (the patch's centre pixel for padding items)
+    if constexpr (GUP) {   // `rel` = the SOURCE pixel's index in its (h/2 x w/2) image (the patch's centre pixel for padding items)
       const unsigned sy = valid ? (unsigned)iy : (unsigned)(y0 + 8), sx = valid ? (unsigned)ix : (unsigned)(x0 + 8);
       rel = (sy >> 1) * ((unsigned)a.w >> 1) + (sx >> 1);
     } else {
@@ -227,9 +252,9 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   };
   const size_t img0 = (size_t)b * a.h * a.w;
   const unsigned img_px = (unsigned)(a.h * a.w);
-  const size_t img0_in = UP ? img0 / 4 : img0;          // (the source of the upsampling form has a quarter of the pixels)
-  const unsigned img_px_in = UP ? img_px / 4 : img_px;
   // one descriptor per concatenated input, based at this image (the launch checks that an image stays below 2^31 bytes)
+  const size_t img0_in = GUP ? img0 / 4 : img0;          // (the source of the upsampling gather has a quarter of the pixels)
+  const unsigned img_px_in = GUP ? img_px / 4 : img_px;
   const __amdgpu_buffer_rsrc_t rs_in0 = f4_rsrc(a.in0 + img0_in * a.c0, img_px_in * (unsigned)a.c0 * 4u);
   const __amdgpu_buffer_rsrc_t rs_in1 = f4_rsrc(a.c1 ? a.in1 + img0_in * a.c1 : a.in0, img_px_in * (unsigned)a.c1 * 4u);
   constexpr bool HALVES = F4_APT >= 6;                   // six items per gather thread: a slab's items are requested and stored in two halves
@@ -251,7 +276,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
       unsigned rel;
       bool valid;
       item(tl / (unsigned)QPP, j, rel, valid);
-      const unsigned voff = (__umul24(UP ? rel : (unsigned)(pix_origin + (int)rel), cs) + k4x) * 4u;
+      const unsigned voff = (__umul24(GUP ? rel : (unsigned)(pix_origin + (int)rel), cs) + k4x) * 4u;
       (HALVES && j >= RAN ? rb[j % RAN] : ra[j % RAN]) = first ? f4_ld128(rs_in0, voff, soff) : f4_ld128(rs_in1, voff, soff);
     }
   };
@@ -315,6 +340,28 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
       }
     }
   };
+  // UP: the rows of B42^T on five values (xi of the column pass, nu of the row pass)
+  auto bt42 = [](auto xi, f4_f32x2 d0, f4_f32x2 d1, f4_f32x2 d2, f4_f32x2 d3, f4_f32x2 d4) __attribute__((always_inline)) {
+    constexpr int XI = decltype(xi)::value;
+    if constexpr (XI == 0) return (d0 + d3) - (d1 + d2) * 1.5f;
+    else if constexpr (XI == 1) return (d1 + d3) - d2 * 2.5f;
+    else if constexpr (XI == 2) return (d3 - d2) - d1 * 2.f;
+    else if constexpr (XI == 3) return (d2 - d1) * 0.5f + d3;
+    else return (d1 + d4) - (d2 + d3) * 1.5f;
+  };
+  auto row_pass42 = [&](const f4_f32x2 (&zz)[5], int pos) __attribute__((always_inline)) {
+    f4_f32x2 v[5];
+    v[0] = bt42(std::integral_constant<int, 0>{}, zz[0], zz[1], zz[2], zz[3], zz[4]);
+    v[1] = bt42(std::integral_constant<int, 1>{}, zz[0], zz[1], zz[2], zz[3], zz[4]);
+    v[2] = bt42(std::integral_constant<int, 2>{}, zz[0], zz[1], zz[2], zz[3], zz[4]);
+    v[3] = bt42(std::integral_constant<int, 3>{}, zz[0], zz[1], zz[2], zz[3], zz[4]);
+    v[4] = bt42(std::integral_constant<int, 4>{}, zz[0], zz[1], zz[2], zz[3], zz[4]);
+#pragma unroll
+    for (int nu = 0; nu < 5; ++nu) {
+      t_hi[(pos + nu) * PSK] = v[nu][0];
+      t_lo[(pos + nu) * PSK] = v[nu][1];
+    }
+  };
   // Two parts keep the live set small: first the single row of the half (xi 0 from tile rows 0, 2, 4 / xi 5 from rows 1, 3, 5), then
   // the even / odd pair (xi 1, 2 or 3, 4: tile rows 1..4).  `mid` runs between the two row passes of the second part (the slab's first
   // weight fragments are requested there: the first pass's column sums are dead, the live set is at its smallest).
@@ -323,6 +370,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
     unsigned ln = (unsigned)lane;
     asm volatile("" : "+v"(ln));  // opaque per slab (see above)
     // 16-channel slabs: wave = (xi half, tile half), lane = (tile, 8 channel pairs); 32-channel slabs: wave = (xi half, tile row), lane = (tile column, 16 pairs)
+    constexpr int TG0 = UP ? 15 : 18;   // first position of the upper xi half
     const unsigned t_tile = KS == 32 ? 4u * (unsigned)(wave & 3) + (ln >> 4) : 8u * (unsigned)(wave & 1) + (ln >> 3);
     const unsigned t_cp = KS == 32 ? ln & 15u : ln & 7u;
     const unsigned t_ty = t_tile >> 2, t_tx = t_tile & 3u;
@@ -338,25 +386,51 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
       // unit p = j >> 1 of quad lq (f4_vu), word j & 1
       const unsigned lq0 = (2u * t_cp) & 3u, j = t_cp >> 1;
       if (KS == 32) {
-        t_hi = V + (tg * 18) * PSK + t_tile * 32 + f4_vu(lq0, j >> 1, t_tile) * 2u + (j & 1u);
-        t_lo = V + (tg * 18) * PSK + t_tile * 32 + f4_vu(lq0 + 1u, j >> 1, t_tile) * 2u + (j & 1u);
+        t_hi = V + (tg * TG0) * PSK + t_tile * 32 + f4_vu(lq0, j >> 1, t_tile) * 2u + (j & 1u);
+        t_lo = V + (tg * TG0) * PSK + t_tile * 32 + f4_vu(lq0 + 1u, j >> 1, t_tile) * 2u + (j & 1u);
       } else {
-        t_hi = V + (tg * 18) * PSK + t_tile * CF_BK + ((lq0 ^ (unsigned)f4_vs((int)t_ty)) << 2) + j;
-        t_lo = V + (tg * 18) * PSK + t_tile * CF_BK + (((lq0 + 1u) ^ (unsigned)f4_vs((int)t_ty)) << 2) + j;
+        t_hi = V + (tg * TG0) * PSK + t_tile * CF_BK + ((lq0 ^ (unsigned)f4_vs((int)t_ty)) << 2) + j;
+        t_lo = V + (tg * TG0) * PSK + t_tile * CF_BK + (((lq0 + 1u) ^ (unsigned)f4_vs((int)t_ty)) << 2) + j;
       }
     } else if (KS == 32) {
       const unsigned lq = t_cp >> 2, e = t_cp & 3u;
-      t_hi = V + (tg * 18) * PSK + t_tile * 32 + f4_vu(lq, e >> 1, t_tile) * 2u + (e & 1u);
-      t_lo = V + (tg * 18) * PSK + t_tile * 32 + f4_vu(lq, 2u + (e >> 1), t_tile) * 2u + (e & 1u);
+      t_hi = V + (tg * TG0) * PSK + t_tile * 32 + f4_vu(lq, e >> 1, t_tile) * 2u + (e & 1u);
+      t_lo = V + (tg * TG0) * PSK + t_tile * 32 + f4_vu(lq, 2u + (e >> 1), t_tile) * 2u + (e & 1u);
     } else {
-      t_hi = V + (tg * 18) * PSK + t_tile * CF_BK + (((t_cp >> 1) ^ (unsigned)f4_vs((int)t_ty)) << 2) + (t_cp & 1u);
+      t_hi = V + (tg * TG0) * PSK + t_tile * CF_BK + (((t_cp >> 1) ^ (unsigned)f4_vs((int)t_ty)) << 2) + (t_cp & 1u);
       t_lo = t_hi + 2;
     }
     auto px = [&](int r, int j) __attribute__((always_inline)) {  // (r, j compile-time after unrolling)
       const int q = 2 * r + j;
       return *reinterpret_cast<const f4_f32x2*>(pb + (4 << SH) * (4 * r + (q >> 2)) + (tk[q >> 2] ^ (((unsigned)q & 3u) << SH)));
     };
-    if (tg == 0) {
+    if constexpr (UP) {
+      // one xi at a time (five column values live); tile rows 0..4 and columns 0..4 of the six the plain form reads
+      auto xi_pass = [&](auto xi) __attribute__((always_inline)) {
+        constexpr int XI = decltype(xi)::value;
+        f4_f32x2 z[5];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+          const f4_f32x2 zero = {0.f, 0.f};
+          z[j] = bt42(xi, XI == 0 ? px(0, j) : zero, px(1, j), px(2, j), px(3, j), XI == 4 ? px(4, j) : zero);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        row_pass42(z, (XI >= 3 ? XI - 3 : XI) * 5);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      if (tg == 0) {
+        xi_pass(std::integral_constant<int, 0>{});
+        xi_pass(std::integral_constant<int, 1>{});
+        mid();
+        __builtin_amdgcn_sched_barrier(0);
+        xi_pass(std::integral_constant<int, 2>{});
+      } else {
+        xi_pass(std::integral_constant<int, 3>{});
+        mid();
+        __builtin_amdgcn_sched_barrier(0);
+        xi_pass(std::integral_constant<int, 4>{});
+      }
+    } else if (tg == 0) {
       {  // xi = 0: .25 (d0 + d4) - 1.0625 d2
         f4_f32x2 z[6];
 #pragma unroll
@@ -413,11 +487,11 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
 
   // ---- MFMA interval: wave = (xi half m_g, 16-channel block m_nb) owns positions 18 m_g + i, i = 0..17 ----
   const int m_g = wave / (NW / 2), m_nb = wave % (NW / 2);
-  f32x4 acc[18];
+  f32x4 acc[NPW];
 #pragma unroll
-  for (int i = 0; i < 18; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < NPW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   // weight fragments: descriptor over the packed tensor, lane offset 16 lane bytes, everything else in the scalar offset
-  const __amdgpu_buffer_rsrc_t rs_w = f4_rsrc(a.weight, 36u * (unsigned)a.cin * (unsigned)a.cout * 4u);
+  const __amdgpu_buffer_rsrc_t rs_w = f4_rsrc(a.weight, (UP ? 100u : 36u) * (unsigned)a.cin * (unsigned)a.cout * 4u);   // (UP: 4 phases x 25 positions)
   const unsigned w_pos = (unsigned)a.cin * (unsigned)a.cout * 4u;                                        // bytes between positions
   const unsigned w_chunk = (unsigned)(a.cout * KS) * 4u;                                                 // ... between slabs
   const unsigned w_s0 = (unsigned)(18 * m_g) * w_pos + (unsigned)(n0 / 16 + m_nb) * (unsigned)(64 * KS); // (wave-uniform; a fragment: 64 lanes x KS bytes)
@@ -495,9 +569,10 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   f32x4 xb[3][2], xa[1][2];
   // (round 5 also measured a form in which a wave owns 9 positions x 2 channel blocks -- half the A-fragment LDS reads, bitwise the same, flat on
   //  every shape: profiles/r05_f43_pair_ab.txt; the switch lives in tools/experiments/ablation_and_timing_macros.patch)
-  const int p_g = 18 * m_g;                     // first position of this wave
+  const int p_g = NPW * m_g;                    // first position of this wave
   const int p_nb = m_nb;                        // its 16-channel block
-  const unsigned w_s32 = (unsigned)p_g * w_pos + (unsigned)(n0 / 16 + p_nb) * (unsigned)(64 * KS);
+  const bool p_last = !UP || m_g == 0;          // UP: the upper half has 12 positions: its 13th fragments are neither requested nor multiplied (wave-uniform)
+  const unsigned w_s32 = (unsigned)(p_g + 25 * phase) * w_pos + (unsigned)(n0 / 16 + p_nb) * (unsigned)(64 * KS);
   auto load_B32 = [&](int chunk, int i) __attribute__((always_inline)) {
     const unsigned so = w_s32 + (unsigned)i * w_pos + (unsigned)chunk * w_chunk;
     xb[i % 3][0] = f4_ld128(rs_w, lane16, so);
@@ -525,12 +600,14 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
     };
     read_A(0);
 #pragma unroll
-    for (int i = 0; i < 18; ++i) {
+    for (int i = 0; i < NPW; ++i) {
       __builtin_amdgcn_sched_barrier(0);
       if (F32) {  // eight k groups: xa / xb [0] = j 0..3, [1] = j 4..7
+        if (i + 1 < NPW || p_last) {   // (wave-uniform)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[0][j >> 2][j & 3], xb[i % 3][j >> 2][j & 3], acc[i], 0, 0, 0);
+          for (int j = 0; j < 8; ++j) {
+            acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[0][j >> 2][j & 3], xb[i % 3][j >> 2][j & 3], acc[i], 0, 0, 0);
+          }
         }
       } else {
         mf(xa[0][1], xb[i % 3][0], acc[i]);
@@ -538,8 +615,8 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
         mf(xa[0][0], xb[i % 3][0], acc[i]);
       }
       // (one register set: the next fragment is read once this position's MFMAs are issued -- 128 registers)
-      if (i + 1 < 18) read_A(i + 1);
-      if (i + 3 < 18) load_B32(chunk, i + 3);
+      if (i + 1 < NPW && (p_last || i + 1 < NPW - 1)) read_A(i + 1);
+      if (i + 3 < NPW && (p_last || i + 3 < NPW - 1)) load_B32(chunk, i + 3);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -690,15 +767,17 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   const int nn = n0 + 2 * e_cp;
   f4_f32x2 bias2 = {0.f, 0.f};
   if (a.bias) bias2 = *reinterpret_cast<const f4_f32x2*>(a.bias + nn);
-  const unsigned e_rowc = (unsigned)a.w * (unsigned)a.cout * 4u;   // bytes between image rows
-  const unsigned e_px = (unsigned)a.cout * 4u;                       // ... between pixels
-  const unsigned e_img = img_px * (unsigned)a.cout * 4u;
-  const __amdgpu_buffer_rsrc_t rs_out = f4_rsrc(a.out + img0 * a.cout, e_img);
+  // UP: the output image is (2 h x 2 w); this workgroup's outputs are every second pixel of every second row, from (2 y0 + pa, 2 x0 + pb)
+  const unsigned e_rowc = (unsigned)(OS * OS * a.w) * (unsigned)a.cout * 4u;   // bytes between the workgroup's output rows
+  const unsigned e_px = (unsigned)(OS * a.cout) * 4u;                          // ... between its pixels
+  const unsigned e_img = (unsigned)(OS * OS) * img_px * (unsigned)a.cout * 4u;
+  const __amdgpu_buffer_rsrc_t rs_out = f4_rsrc(a.out + (size_t)(OS * OS) * img0 * a.cout, e_img);
   const __amdgpu_buffer_rsrc_t rs_res = f4_rsrc(EPI == CF_EPI_NONE ? a.out : a.res + img0 * a.cout, e_img);
   const __amdgpu_buffer_rsrc_t rs_sft = f4_rsrc(EPI == CF_EPI_SFT ? a.sft_scale + img0 * a.cout : a.out, e_img);
   const bool rh1 = e_rh != 0;
   // xi contraction of this lane's two output rows: rows 0, 1 (e_rh = 0): tA = (s1 + s2) + m0, tB = .5 d1 + 2 d2;
   //                                                 rows 2, 3 (e_rh = 1): tA = .25 s1 + 4 s2,  tB = (.125 d1 + 8 d2) + m5
+  // UP (A42^T): rows 0, 1: tA = (m1 + m2 + m3) + m0, tB = (.5 m2 + 2 m3) - m1;  rows 2, 3: tA = m1 + .25 m2 + 4 m3, tB = ((.125 m2 + 8 m3) - m1) + m4
   const float ca1 = rh1 ? 0.25f : 1.f, ca2 = rh1 ? 4.f : 1.f, cb1 = rh1 ? 0.125f : 0.5f, cb2 = rh1 ? 8.f : 2.f;
   double psum = 0.0, psq = 0.0;  // this wave's GroupNorm partial over both passes
 #pragma unroll
@@ -707,7 +786,8 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
     asm volatile("" : "+v"(e_zero));  // opaque 0 placed here: keeps hipcc from hoisting this pass's residual / SFT loads above the slab loop / the previous pass
     // lane part: the output-row half and the channel pair; scalar part: the tile of this wave and pass
     const unsigned voff0 = (unsigned)(2 * e_rh) * e_rowc + (unsigned)(2 * e_cp) * 4u + e_zero;
-    const unsigned soff0 = (unsigned)(y0 + 4 * (e_tp >> 1)) * e_rowc + (unsigned)(x0 + 4 * (2 * th + (e_tp & 1))) * e_px + (unsigned)n0 * 4u;
+    const unsigned soff0 = (unsigned)(y0 + 4 * (e_tp >> 1)) * e_rowc + (unsigned)(x0 + 4 * (2 * th + (e_tp & 1))) * e_px + (unsigned)n0 * 4u +
+                           (UP ? (unsigned)(pa * 2 * a.w + pb) * (unsigned)a.cout * 4u : 0u);
     // residual / SFT operands of this pass first: their latency overlaps the staging
     f4_f32x2 r0[2][4], r1[2][4];
 #pragma unroll
@@ -720,8 +800,8 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
     __builtin_amdgcn_sched_barrier(0);
     if (th > 0) __syncthreads();  // the previous pass's reads are complete (first pass: the slab loop ended with a barrier)
 #pragma unroll
-    for (int i = 0; i < 18; ++i) {
-      float* mp = Mst + ((18 * m_g + i) * 8 + 2 * (lane >> 4)) * F4_BN + m_nb * 16 + (lane & 15);
+    for (int i = 0; i < NPW; ++i) {   // (UP: the upper half stages its idle 13th accumulator, zeros, as position 25, which nothing reads)
+      float* mp = Mst + ((NPW * m_g + i) * 8 + 2 * (lane >> 4)) * F4_BN + m_nb * 16 + (lane & 15);
       mp[0] = acc[i][2 * th];
       mp[F4_BN] = acc[i][2 * th + 1];
     }
@@ -734,7 +814,16 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
     __syncthreads();
     const float* mq = Mst + e_tp * F4_BN + 2 * e_cp;
     auto col = [&](int nu, f4_f32x2& tA, f4_f32x2& tB) __attribute__((always_inline)) {
-      auto m = [&](int xi) __attribute__((always_inline)) { return *reinterpret_cast<const f4_f32x2*>(mq + ((xi * 6 + nu) * 8) * F4_BN); };
+      auto m = [&](int xi) __attribute__((always_inline)) { return *reinterpret_cast<const f4_f32x2*>(mq + ((xi * NXI + nu) * 8) * F4_BN); };
+      if constexpr (UP) {
+        const f4_f32x2 m1 = m(1), m2 = m(2), m3 = m(3);
+        const f4_f32x2 me = *reinterpret_cast<const f4_f32x2*>(mq + (((rh1 ? 4 : 0) * NXI + nu) * 8) * F4_BN);
+        const f4_f32x2 x = m1 + m2 * ca1 + m3 * ca2, y = (m2 * cb1 + m3 * cb2) - m1;
+        const f4_f32x2 xm = x + me, ym = y + me;
+        tA = rh1 ? x : xm;
+        tB = rh1 ? ym : y;
+        return;
+      }
       const f4_f32x2 m1 = m(1), m2 = m(2), m3 = m(3), m4 = m(4);
       const f4_f32x2 me = *reinterpret_cast<const f4_f32x2*>(mq + (((rh1 ? 5 : 0) * 6 + nu) * 8) * F4_BN);
       const f4_f32x2 s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
@@ -744,7 +833,18 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
       tB = rh1 ? ym : y;
     };
     f4_f32x2 o[2][4];
-    {
+    if constexpr (UP) {   // nu contraction with A42^T: t0 + t1 + t2 + t3,  -t1 + .5 t2 + 2 t3,  t1 + .25 t2 + 4 t3,  -t1 + .125 t2 + 8 t3 + t4
+      f4_f32x2 t[5][2];
+#pragma unroll
+      for (int nu = 0; nu < 5; ++nu) col(nu, t[nu][0], t[nu][1]);
+#pragma unroll
+      for (int aa = 0; aa < 2; ++aa) {
+        o[aa][0] = (t[0][aa] + t[1][aa]) + (t[2][aa] + t[3][aa]);
+        o[aa][1] = (t[2][aa] * 0.5f + t[3][aa] * 2.f) - t[1][aa];
+        o[aa][2] = (t[2][aa] * 0.25f + t[3][aa] * 4.f) + t[1][aa];
+        o[aa][3] = ((t[2][aa] * 0.125f + t[3][aa] * 8.f) - t[1][aa]) + t[4][aa];
+      }
+    } else {
       f4_f32x2 t0[2], ta[2], tb[2];
       col(0, t0[0], t0[1]);
       col(1, ta[0], ta[1]);
@@ -916,6 +1016,36 @@ __global__ void pack_weight_wf43_kernel(const float* __restrict__ w, int cout, i
   packed[i] = out;
 }
 
+// The sub-pixel F(4x4,2x2) form (UP): U_p = G42 g_p G42^T per output parity p = 2 a + b, g_p = the 3x3 taps folded to the 2x2 the parity sees on the
+// low-resolution image (fp64 throughout, rounded once), in the fp32 fragment order of the 32-channel-slab form:
+// [phase][pos = xi*5 + nu][cin/32][cout/16][lane 64][8 words], word j = U_p[n = block*16 + (lane&15)][c = chunk*32 + 4 j + (lane>>4)].
+__global__ void pack_weight_wf42_up_kernel(const float* __restrict__ w, int cout, int cin, int nchunks, float* __restrict__ packed, long total) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int j = (int)(i & 7), ln = (int)((i >> 3) & 63);
+  long r = i >> 9;
+  const int ntiles = cout / 16;
+  const int nn = (int)(r % ntiles) * 16 + (ln & 15);
+  r /= ntiles;
+  const int chunk = (int)(r % nchunks);
+  r /= nchunks;
+  const int pos = (int)(r % 25), phase = (int)(r / 25);
+  const int c = chunk * 32 + 4 * j + (ln >> 4);
+  const int xi = pos / 5, nu = pos % 5, pa = phase >> 1, pb = phase & 1;
+  const double G[5][2] = {{1.0, 0.0}, {-2.0 / 9.0, 2.0 / 9.0}, {-8.0 / 9.0, -4.0 / 9.0}, {1.0 / 9.0, 2.0 / 9.0}, {0.0, 1.0}};
+  const float* g = w + ((long)nn * cin + c) * 9;
+  // fold: parity 0 sees [g0, g1 + g2], parity 1 [g0 + g1, g2]: tap t of the 3 belongs to folded tap (t + 1 - parity) >> 1
+  double f[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+#pragma unroll
+  for (int y = 0; y < 3; ++y)
+#pragma unroll
+    for (int x = 0; x < 3; ++x) f[(y + 1 - pa) >> 1][(x + 1 - pb) >> 1] += (double)g[y * 3 + x];
+  double u = 0.0;
+#pragma unroll
+  for (int y = 0; y < 2; ++y) u += G[xi][y] * (f[y][0] * G[nu][0] + f[y][1] * G[nu][1]);
+  packed[i] = (float)u;
+}
+
 }  // namespace
 
 // Form of the 16-wave (128-output-channel) workgroup; packing and launch agree through this one function:
@@ -962,17 +1092,33 @@ extern "C" int cf_pack_conv_weight_winograd43(const float* w, int cout, int cin,
   return CF_OK;
 }
 
+extern "C" int cf_pack_conv_weight_winograd42_up(const float* w, int cout, int cin, int cout_pad, int cin_pad, void* packed, cf_stream_t stream) {
+  CF_REQUIRE(w && packed, "cf_pack_conv_weight_winograd42_up: null pointer");
+  CF_REQUIRE(cin_pad == cin && cout_pad == cout && cin > 0 && cout > 0 && cin % 32 == 0 && cout % 128 == 0,
+             "cf_pack_conv_weight_winograd42_up: bad padding cin %d->%d cout %d->%d (cin %% 32 == 0, cout %% 128 == 0, no padding)", cin, cin_pad, cout, cout_pad);
+  CF_REQUIRE(f4_k32_enabled(), "cf_pack_conv_weight_winograd42_up: the sub-pixel form runs on 32-channel slabs (CF_F43_WIDE=k16 is set)");
+  const long total = 100L * cin * cout;  // fp32 words: 4 phases x 25 positions
+  hipLaunchKernelGGL(pack_weight_wf42_up_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin, cin / 32,
+                     reinterpret_cast<float*>(packed), total);
+  CF_CHECK_LAUNCH("cf_pack_conv_weight_winograd42_up");
+  return CF_OK;
+}
+
 // Called by cf_conv2d (cf_igemm.hip) for descriptors with winograd == 2; the common argument checks have run there.
 int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {
   CF_REQUIRE(d->taps == 9 && d->stride == 1 && !d->in_nchw && !d->out_nchw &&
                  (d->bf16_mfma == CF_OPERAND_F16X2 || d->bf16_mfma == CF_OPERAND_F32),
              "cf_conv2d(winograd 2): F(4x4,3x3) covers 3x3 stride-1 NHWC convolutions with split-half or fp32 operands");
   const bool f32 = d->bf16_mfma == CF_OPERAND_F32;
-  // nearest-x2 + 3x3 (cf_conv_desc.upsample) with fp32 operands: the upsampling gather of the 16-wave form on 32-channel slabs (weights: the
-  // plain cf_pack_conv_weight_winograd43 packing of the 3x3 kernel, not the folded one)
+  // nearest-x2 + 3x3 with fp32 operands on the 16-wave form with 32-channel slabs.  cf_conv_desc.upsample == 2: four F(4x4,2x2) sub-pixel phases
+  // (weights: cf_pack_conv_weight_winograd42_up; what the network runs).  upsample == 1: F(4,3) on the virtually upsampled image through the
+  // upsampling gather (weights: the plain cf_pack_conv_weight_winograd43 packing of the 3x3 kernel).
+  const bool sub = d->upsample == 2;
   CF_REQUIRE(!d->upsample || (f32 && d->prologue == CF_PRO_NONE && d->epilogue == CF_EPI_NONE && d->c1 == 0 && d->cout % 128 == 0 && d->c0 % 32 == 0 &&
                               f4_k32_enabled()),
              "cf_conv2d(winograd 2, upsample): fp32 operands, one input with c0 %% 32 == 0, cout %% 128 == 0, no prologue / epilogue operand");
+  CF_REQUIRE(!sub || (d->hin % F4_TH == 0 && d->win % F4_TW == 0 && d->hout == 2 * d->hin && d->wout == 2 * d->win),
+             "cf_conv2d(winograd 2, upsample 2): needs an input of %dx%d multiples (got %dx%d)", F4_TH, F4_TW, d->hin, d->win);
   if (!f32)
     if (const int e = cf_require_acc_scale(d, "cf_conv2d(winograd 2)")) return e;
   CF_REQUIRE(!f32 || !d->act_scale, "cf_conv2d(winograd 2): fp32 operands take no activation range scale");
@@ -1005,6 +1151,11 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
   CF_REQUIRE(!k32 || d->c0 % 32 == 0, "cf_conv2d(winograd 2): with cout %% 128 == 0 and cin %% 32 == 0 the concat boundary must be a multiple of 32 (c0 = %d)", d->c0);
   a.ntn = d->cout / (wide ? 128 : 64);
   a.nt_out = cf_nt_store((long)d->batch * d->hout * d->wout * d->cout * 4);
+  if (sub) {   // the kernel's image is the low-resolution one; 4 phases x its 16x16 blocks = the 16x16 patches of the output (nparts stays)
+    a.h = d->hin;
+    a.w = d->win;
+    a.tiles_x = d->win / F4_TW;
+  }
   if (parts_query) {
     *parts_query = a.nparts;
     return CF_OK;
@@ -1013,9 +1164,11 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
   const dim3 grid(a.tiles_per_img * d->batch * a.ntn), block(wide ? 1024 : 512);
   // (cf_device_init sets the dynamic-LDS attribute of every instantiation on each device)
   if (d->upsample) {
-    CF_LDS_ATTR((wf43_kernel<CF_PRO_NONE, CF_EPI_NONE, 16, 32, true, true>), F4_LDS_FLOATS_32 * sizeof(float));
-    hipLaunchKernelGGL((wf43_kernel<CF_PRO_NONE, CF_EPI_NONE, 16, 32, true, true>), grid, block, lds, stream, a);
-    CF_CHECK_LAUNCH("cf_conv2d(winograd F(4,3) fp32, upsampling gather)");
+    CF_LDS_ATTR((wf43_kernel<CF_PRO_NONE, CF_EPI_NONE, 16, 32, true, 1>), F4_LDS_FLOATS_32 * sizeof(float));
+    CF_LDS_ATTR((wf43_kernel<CF_PRO_NONE, CF_EPI_NONE, 16, 32, true, 2>), F4_LDS_FLOATS_32 * sizeof(float));
+    if (sub) hipLaunchKernelGGL((wf43_kernel<CF_PRO_NONE, CF_EPI_NONE, 16, 32, true, 2>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((wf43_kernel<CF_PRO_NONE, CF_EPI_NONE, 16, 32, true, 1>), grid, block, lds, stream, a);
+    CF_CHECK_LAUNCH("cf_conv2d(winograd F(4,3) / F(4,2) fp32, upsampling forms)");
     return CF_OK;
   }
   // one (PRO, EPI, operand) -> its three forms, of which the layer's shape picks one

@@ -70,6 +70,7 @@ SIGNATURES = {
     'cf_pack_conv_weight_winograd_bf16': (_I, [_P, _I, _I, _I, _I, _F, _P, _P]),
     'cf_pack_conv_weight_winograd43_f16x2': (_I, [_P, _I, _I, _I, _I, _F, _P, _P]),
     'cf_pack_conv_weight_winograd43': (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    'cf_pack_conv_weight_winograd42_up': (_I, [_P, _I, _I, _I, _I, _P, _P]),
     'cf_pack_linear_weight_f16x2': (_I, [_P, _I, _I, _F, _P, _P]),
     'cf_pack_conv_weight_up2x_bf16': (_I, [_P, _I, _I, _I, _I, _P, _P]),
     'cf_pack_conv_weight_up2x_f16': (_I, [_P, _I, _I, _I, _I, _P, _P]),

@@ -96,6 +96,7 @@ SPLIT_F43 = 10  # ... REQUEST: SPLIT, with Winograd F(4x4,3x3) where its kernel 
 WF43 = 11      # ... Winograd F(4x4,3x3) with split-half operands (cf_wf43.hip; cf_conv_desc.winograd = 2)
 WINOGRAD_F43 = 12   # ... REQUEST: WINOGRAD (exact fp32), with Winograd F(4x4,3x3) on fp32 operands where its kernel applies (generator / CFT only)
 WF43F = 13     # ... Winograd F(4x4,3x3) with IEEE-fp32 operands (cf_wf43.hip on v_mfma_f32_16x16x4_f32; winograd = 2, operand fp32)
+WF42U = 14     # ... nearest x2 + 3x3 as four Winograd F(4x4,2x2) sub-pixel phases with IEEE-fp32 operands (cf_wf43.hip; winograd = 2 + upsample)
 OPERAND_F16X2 = 3   # enum cf_operand value behind SPLIT / WSPLIT / GSPLIT / WF43
 SPLIT_CODES = (SPLIT, SPLIT_F43)   # requested codes that put un-normalised inputs / stride-2 / 1x1 layers on the split-half kernels
 
@@ -143,15 +144,15 @@ def f43_ok(cin, cout, hout, wout, fp32=False):
     return cin % 16 == 0 and cin <= cin_max and cout % 64 == 0 and hout % 16 == 0 and wout % 16 == 0
 
 
-# precision 'fp32': the Upsample blocks (nearest x2 + 3x3) on the fp32 F(4x4,3x3) kernel with an UPSAMPLING gather (round 6) instead of the folded
-# sub-pixel form on the direct fp32 kernel, which executes every one of its 4 products per output (0.82 of the fp32 MFMA peak: nothing left
-# to schedule) -- F(4,3) needs 2.25.
+# precision 'fp32': the Upsample blocks (nearest x2 + 3x3) as four Winograd F(4x4,2x2) sub-pixel phases on the fp32 F(4,3) kernel's stages
+# (cf_wf43.hip: 25 transform-domain products per 16 outputs = 1.5625 per output) instead of the folded sub-pixel form on the direct fp32
+# kernel, which executes every one of its 4 products per output (0.82 of the fp32 MFMA peak: nothing left to schedule).
 
 
 def f43_up_ok(cin, cout, hout, wout):
-    """Shapes the upsampling form of the fp32 F(4x4,3x3) kernel covers ((hout, wout) = the OUTPUT size): the 16-wave workgroup on
-    32-channel slabs, GroupNorm-table limit of 256 input channels, whole 16x16 output patches, from the size where the 16-wave form pays."""
-    return cin % 32 == 0 and cin <= 256 and cout % 128 == 0 and hout % 16 == 0 and wout % 16 == 0 and \
+    """Shapes the sub-pixel F(4x4,2x2) form of the fp32 Winograd kernel covers ((hout, wout) = the OUTPUT size): the 16-wave workgroup on
+    32-channel slabs, at most 256 input channels, whole 16x16 blocks of the INPUT grid, from the size where the 16-wave form pays."""
+    return cin % 32 == 0 and cin <= 256 and cout % 128 == 0 and hout % 32 == 0 and wout % 32 == 0 and \
         hout * wout >= F43_WIDE_MIN_PIXELS_FP32
 
 
@@ -355,6 +356,32 @@ def _f43_max(w):
     return float(torch.einsum('xa,kcab,yb->kcxy', Gm, w.double(), Gm).abs().max())
 
 
+# Winograd F(4,2) for the sub-pixel phases of nearest x2 + 3x3 (conv2d(upsample=True) in precision 'fp32'): output parity a along an axis is the
+# 2-tap correlation [g0, g1 + g2] of rows i - 1, i (a = 0) or [g0 + g1, g2] of rows i, i + 1 (a = 1) of the low-resolution image, and
+#   Y = A42^T [ (G42 g_p G42^T) (.) (B42^T d B42) ] A42      d: 5x5 window, g_p: the folded 2x2 kernel of phase p, Y: 4x4 outputs of that phase
+# with the interpolation points (0, -1, 1/2, 2, inf): of the twelve sets tools/winograd_f42_numerics.py compares (0, +-1 / +-1/2 / +-2 with a
+# fourth point, and the mixed sets) the one with the smallest fp64-measured error of the fp32 pipeline -- 128 channels, 16x16 -> 32x32, |out| <=
+# 6.65: max 1.90e-5, mean 7.7e-7 (its mirror (0, 1, -1/2, -2) measures the same), against max 2.69e-5, mean 1.25e-6 of F(4x4,3x3) on the
+# upsampled image and mean 1.2e-6 of the symmetric sets (0, +-1, x).  Every entry of B42^T and A42^T is exact in fp32, so no row scaling is needed.
+B42T = ((1.0, -1.5, -1.5, 1.0, 0.0), (0.0, 1.0, -2.5, 1.0, 0.0), (0.0, -2.0, -1.0, 1.0, 0.0), (0.0, -0.5, 0.5, 1.0, 0.0), (0.0, 1.0, -1.5, -1.5, 1.0))
+G42 = ((1.0, 0.0), (-2 / 9, 2 / 9), (-8 / 9, -4 / 9), (1 / 9, 2 / 9), (0.0, 1.0))
+A42T = ((1.0, 1.0, 1.0, 1.0, 0.0), (0.0, -1.0, 0.5, 2.0, 0.0), (0.0, 1.0, 0.25, 4.0, 0.0), (0.0, -1.0, 0.125, 8.0, 1.0))
+
+
+def fold_phase_taps(w, a, b):
+    """(.., 3, 3) -> (.., 2, 2): the taps output parity (a, b) of nearest x2 + 3x3 sees on the low-resolution image (in w's dtype; fp64 for packing)."""
+    def fold(t, p, dim):
+        g0, g1, g2 = t.unbind(dim)
+        return torch.stack((g0, g1 + g2) if p == 0 else (g0 + g1, g2), dim)
+    return fold(fold(w, a, -2), b, -1)
+
+
+def f42_weights(w):
+    """(cout, cin, 3, 3) -> (4 phases p = 2a + b, cout, cin, 5, 5) fp64: G42 g_p G42^T, what cf_pack_conv_weight_winograd42_up evaluates and rounds once."""
+    G = torch.tensor(G42, dtype=torch.float64, device=w.device)
+    return torch.stack([torch.einsum('xa,kcab,yb->kcxy', G, fold_phase_taps(w.double(), p >> 1, p & 1), G) for p in range(4)])
+
+
 def _require_3x3(w, cin_mult, cout_mult, what, up2x):
     """The shape rule of the 3x3 layouts: whole K slabs and channel tiles; up2x is refused (pass False for a layout with a folded form)."""
     if up2x or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[1] % cin_mult or w.shape[0] % cout_mult:
@@ -375,15 +402,17 @@ _WINO = {WINOGRAD: ('winograd', 'cf_pack_conv_weight_winograd', 16, None, False,
          WF16: ('winograd f16x2', 'cf_pack_conv_weight_winograd_f16x2', 16, _f23_max, 2, True),   # (reads the hi slot)
          WBF16: ('winograd f16x2', 'cf_pack_conv_weight_winograd_bf16', 16, _f23_max, 1, True),
          WF43F: ('winograd F(4,3)', 'cf_pack_conv_weight_winograd43', 36, None, False, 2),
+         WF42U: ('winograd F(4,2) sub-pixel', 'cf_pack_conv_weight_winograd42_up', 100, None, False, 2),   # (4 phases x 25 positions)
          WF43: ('winograd F(4,3) f16x2', 'cf_pack_conv_weight_winograd43_f16x2', 36, _f43_max, OPERAND_F16X2, 2)}
 
 
 def _pack_winograd(w, b, code, up2x, stride2):
     what, fn, npos, domain_max, operand, wino = _WINO[code]
-    _require_3x3(w, 16, 64, what, up2x)
+    up = code == WF42U
+    _require_3x3(w, 32 if up else 16, 128 if up else 64, what, up2x)
     cout, cin = w.shape[:2]
     scale = () if domain_max is None else (pack_scale(domain_max(w)),)
-    return PackedWeight(_packed(fn, npos * cin * cout, w, cout, cin, cout, cin, *scale), b, cout, cin, 9, cout, cin, bf16=operand, wino=wino, scale=(*scale, 1.0)[0])
+    return PackedWeight(_packed(fn, npos * cin * cout, w, cout, cin, cout, cin, *scale), b, cout, cin, 9, cout, cin, bf16=operand, up2x=up, wino=wino, scale=(*scale, 1.0)[0])
 
 
 def _pack_split(w, b, code, up2x, stride2):
@@ -589,9 +618,10 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
         ld1 = _nhwc_ld(x2, 'x2')
     if c0 + c1 != pw.cin and not (c1 == 0 and c0 == pw.cin_pad):
         raise ValueError(f'input channels {c0}+{c1} != weight cin {pw.cin}')
-    f43_up = bool(upsample) and pw.wino == 2 and not pw.bf16     # fp32 F(4,3) with the upsampling gather: the PLAIN 3x3 packing (WF43F), not the folded one
+    f43_up = bool(upsample) and pw.wino == 2 and not pw.bf16 and not pw.up2x   # a PLAIN fp32 F(4,3) packing (WF43F): F(4,3) on the upsampled image through the upsampling gather
+    f42_up = bool(upsample) and pw.wino == 2 and not pw.bf16 and bool(pw.up2x)  # the WF42U packing: four F(4,2) sub-pixel phases (what the network runs)
     if bool(upsample) != bool(pw.up2x) and not f43_up:
-        raise ValueError('conv2d(upsample=True) needs a weight packed with up2x=True, or the fp32 F(4,3) packing (and vice versa)')
+        raise ValueError('conv2d(upsample=True) needs a weight packed with up2x=True, or the fp32 F(4,3) / F(4,2) sub-pixel packing (and vice versa)')
     if pw.taps == 1 and int(pw.bf16) == OPERAND_F16X2 and bool(pw.conv1) != (H * W > TOKEN_IMAGE_MAX):
         raise ValueError(f'1x1 with f16x2 operands: images of more than {TOKEN_IMAGE_MAX} pixels take a weight packed with bf16=SPLIT, '
                          'token matrices one packed with bf16=GSPLIT')
@@ -631,7 +661,7 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
             raise ValueError(f'prologue table shape {tuple(t.shape)} != {(B, c0 + c1)}')
     d = L.ConvDesc(
         in0=None if img_in is not None else L.ptr(x, not in_nchw, dtype=io), in1=L.ptr(x2, True, dtype=io), c0=c0, c1=c1, batch=B, hin=H, win=W, hout=Ho, wout=Wo, cout=pw.cout,
-        cout_pad=pw.cout_pad, taps=pw.taps, stride=stride, upsample=int(bool(upsample)), in_nchw=int(bool(in_nchw)),
+        cout_pad=pw.cout_pad, taps=pw.taps, stride=stride, upsample=2 if f42_up else int(bool(upsample)), in_nchw=int(bool(in_nchw)),
         out_nchw=int(bool(out_nchw)), prologue=prologue, epilogue=epilogue, pro_scale=L.ptr(scale),
         pro_shift=L.ptr(shift), weight=L.ptr(pw.w, dtype=None), bias=L.ptr(pw.bias), res=L.ptr(res, True, dtype=io),
         sft_scale=L.ptr(sft_scale, True, dtype=io), sft_w=float(sft_w), out=None if img_out is not None else L.ptr(out, not out_nchw, dtype=odt), bf16_mfma=int(pw.bf16),

@@ -116,7 +116,8 @@ typedef struct cf_conv_desc {
   int32_t stride;         /* 1 or 2 (2: pad right/bottom only, vqgan_arch.py:123) */
   int32_t upsample;       /* 1: nearest x2 + 3x3 (vqgan_arch.py:134-138) computed as four 2x2 sub-pixel convolutions of the
                              SOURCE tensor (taps folded at pack time: 4 instead of 9 MACs per weight, mathematically
-                             identical); `weight` must come from cf_pack_conv_weight_up2x[_bf16] */
+                             identical); `weight` must come from cf_pack_conv_weight_up2x[_bf16].  With winograd == 2 and
+                             CF_OPERAND_F32 see there: 1 or 2 selects the form */
   int32_t in_nchw;        /* 1: in0 is NCHW with c0 <= 4 channels (network input) */
   int32_t out_nchw;       /* 1: write out as NCHW (network output) */
   int32_t prologue;       /* enum cf_prologue */
@@ -167,7 +168,12 @@ typedef struct cf_conv_desc {
                              1e-3 pixel gate; the host uses it for generator / CFT convolutions (vqgan_arch.py:296-323,
                              codeformer_arch.py:136-157) and -- behind a measured logit-margin gate, round 5 -- for the encoder's covered layers.
                              ABI v20: also with CF_OPERAND_F32 (`weight` from cf_pack_conv_weight_winograd43; acc_scale / act_scale
-                             unused, act_scale must be null): the same kernel with IEEE-fp32 operands on v_mfma_f32_16x16x4_f32 */
+                             unused, act_scale must be null): the same kernel with IEEE-fp32 operands on v_mfma_f32_16x16x4_f32.
+                             With CF_OPERAND_F32 and `upsample` (one input, c0 % 32 == 0, c0 <= 256, cout % 128 == 0, no prologue / epilogue
+                             operand).  upsample == 1 (`weight` from the plain cf_pack_conv_weight_winograd43): F(4x4,3x3) on the virtually upsampled
+                             image, the gather reading source pixel (y >> 1, x >> 1).  upsample == 2 (`weight` from cf_pack_conv_weight_winograd42_up;
+                             hin % 16 == 0, win % 16 == 0): nearest x2 + 3x3 as four F(4x4,2x2) sub-pixel phases, 25 transform-domain GEMMs per 4x4
+                             outputs = 1.5625 products per output and input channel instead of 2.25 */
   float acc_scale;        /* CF_OPERAND_F16X2 only (direct or winograd): the accumulator is multiplied by this before the bias is added -- the exact
                              inverse of the power-of-two scale given to cf_pack_conv_weight_f16x2 (> 0) */
   /* Deterministic split-K for layers with few output tiles (one face: 16x16 .. 64x64 pixels), where latency is the serial K loop of
@@ -243,6 +249,12 @@ int cf_pack_conv_weight_winograd43_f16x2(const float* w, int cout, int cin, int 
  * c = slab * KS + 4 j + (lane >> 4) of output channel block * 16 + (lane & 15) (the 16x16x4 fp32 MFMA's B operand); KS = 32 when
  * cout_pad % 128 == 0 and cin_pad % 32 == 0 (the form cf_conv2d runs for that shape), else 16.  36*cin_pad*cout_pad floats. */
 int cf_pack_conv_weight_winograd43(const float* w, int cout, int cin, int cout_pad, int cin_pad, void* packed, cf_stream_t stream);
+/* winograd == 2 + CF_OPERAND_F32 + upsample (entry point added, ABI version unchanged): nearest x2 + 3x3 as four Winograd F(4x4,2x2) sub-pixel
+ * phases.  Phase p = 2 a + b (output parity (a, b)) folds the 3x3 taps to 2x2 -- along an axis [g0, g1 + g2] for parity 0, [g0 + g1, g2] for
+ * parity 1 -- and U_p = G42 g_p G42^T, points (0, -1, 1/2, 2, inf), is evaluated in fp64 and rounded once: [4 phases][25 positions xi * 5 + nu]
+ * [cin_pad/32][cout_pad/16][64 lanes][8 k groups] fp32 in the fragment order of the 32-channel-slab form above = 100*cin_pad*cout_pad floats;
+ * cout_pad == cout, cout % 128 == 0, cin_pad == cin, cin % 32 == 0. */
+int cf_pack_conv_weight_winograd42_up(const float* w, int cout, int cin, int cout_pad, int cin_pad, void* packed, cf_stream_t stream);
 /* winograd + SINGLE 16-bit operands (cout % 128 == 0, at least 32x32 pixels per image: the eight-wave kernel of cf_wsplit.hip; the
  * network's 'fp16' / 'bf16' modes, BASELINE configs 3 and 5): one MFMA per transform-domain product.  CF_OPERAND_F16 reads the hi slot of
  * the split packing above as it is; CF_OPERAND_BF16 takes this buffer: bf16(scale * U) in the hi slot of the same layout, zeros in the
