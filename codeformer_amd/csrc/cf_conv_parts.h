@@ -3,7 +3,8 @@
 //   head   the XCD-contiguous workgroup order, the range scale of an un-normalised input, the gather prologue on a value or a quad, the
 //          runtime -> compile-time dispatch of the prologue and of the epilogue triple, the three-MFMA split-half product;
 //   tail   the swish of the GroupNorm prologue, the epilogue arithmetic on a quad of channels, the GroupNorm partials of the output;
-//   host   the descriptor fields every argument struct has, the checks the launchers repeat, the prototypes by which the files call each other.
+//   host   the descriptor fields every argument struct has, the checks the launchers repeat, the prototypes by which the files call each other
+//          (the weight packers of every family live in cf_pack.hip and take the F(4,3) slab-form rule from here).
 // Pieces, all forceinline: a kernel keeps its own loops, staging and store order and calls these for the arithmetic, so that the order of
 // every addition is written down once.
 //
@@ -27,6 +28,7 @@ int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_que
 bool cf_wsplit_covers(const cf_conv_desc* d);                                         // cf_wsplit.hip: the eight-wave, 128-channel F(2,3) form,
 int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);   // called by cf_winograd_launch for what it covers
 int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);      // cf_wf43.hip: F(4,3)
+bool cf_wf43_k32(int cout, int cin);                                                  // cf_wf43.hip: F(4,3) / F(4,2) on 32-channel slabs? (cf_wf43_launch and the packers of cf_pack.hip)
 int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);     // cf_split.hip: direct, split-half operands
 int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);  // cf_gemm_split.hip: split-half token GEMM
 int cf_gemm_f32_tile_try(const cf_conv_desc* d, hipStream_t stream);                  // cf_gemm_split.hip: fp32 token tiles (CF_OK: launched, 1: not its shape)

@@ -540,28 +540,6 @@ __global__ __launch_bounds__(256) void gemm_f32_tile_kernel(const GsArgs g) {
     for (int r = 0; r < 16; ++r) gs_finish<false>(g, tot[mi][r], m0 + wm * 64 + mi * 32 + cf_acc_row(r, lane), n, bias);
 }
 
-// W' = scale * W as hi = f16(W'), lo = f16(W' - hi) in MFMA-operand order [K/16][N/32][hi, lo][lane 64][4 words]:
-// a lane's 16 bytes are the 8 halves of W'[n = tile*32 + (lane&31)][k = kstep*16 + (lane>>5)*8 + 0..7]
-__global__ void pack_linear_f16x2_kernel(const float* __restrict__ w, int N, int K, float scale, unsigned* __restrict__ packed, long total) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int e = (int)(i & 3), ln = (int)((i >> 2) & 63), part = (int)((i >> 8) & 1);
-  long r = i >> 9;
-  const int ntiles = N / 32;
-  const int n = (int)(r % ntiles) * 32 + (ln & 31);
-  const int ks = (int)(r / ntiles);
-  unsigned out = 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = ks * 16 + (ln >> 5) * 8 + e * 2 + h;
-    const float v = w[(long)n * K + k] * scale;  // exact: power of two
-    const _Float16 hi = (_Float16)v;
-    const _Float16 hv = part ? (_Float16)(v - (float)hi) : hi;
-    out |= (unsigned)__builtin_bit_cast(unsigned short, hv) << (16 * h);
-  }
-  packed[i] = out;
-}
-
 // What the launches of this file accept: a dense single-input token GEMM (no channel stride, NCHW end, prologue or statistics) ...
 bool gs_plain_token_gemm(const cf_conv_desc* d) {
   return d->stride == 1 && !d->in_nchw && !d->out_nchw && d->c1 == 0 && d->prologue == CF_PRO_NONE && !d->stats_out &&
@@ -592,18 +570,6 @@ GsArgs gs_args(const cf_conv_desc* d, long m, int nsplit, float* ws, unsigned* c
 }
 
 }  // namespace
-
-extern "C" int cf_pack_linear_weight_f16x2(const float* w, int n, int k, float scale, void* packed, cf_stream_t stream) {
-  CF_REQUIRE(w && packed, "cf_pack_linear_weight_f16x2: null pointer");
-  CF_REQUIRE(n > 0 && k > 0 && n % 64 == 0 && k % 128 == 0, "cf_pack_linear_weight_f16x2: N %d must be a multiple of 64, K %d of 128", n, k);
-  int ex = 0;
-  CF_REQUIRE(scale > 0.f && frexpf(scale, &ex) == 0.5f, "cf_pack_linear_weight_f16x2: scale %g is not a power of two", (double)scale);
-  const long total = (long)n * k;  // 32-bit words: hi + lo half per weight
-  hipLaunchKernelGGL(pack_linear_f16x2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, n, k, scale,
-                     reinterpret_cast<unsigned*>(packed), total);
-  CF_CHECK_LAUNCH("cf_pack_linear_weight_f16x2");
-  return CF_OK;
-}
 
 // Called by cf_conv2d (cf_igemm.hip) for taps == 1 descriptors with bf16_mfma == CF_OPERAND_F16X2; the common argument checks have run.
 int cf_gemm_split_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_part) {

@@ -1186,129 +1186,7 @@ int launch_sk(const ConvArgsExt& a, float* ws, unsigned* counters, int nsplit, h
   return CF_OK;
 }
 
-// Value of packed slab entry (slab, n, c).  slab < 9 (or 1): the plain tap.  Folded nearest-x2 + 3x3 (fold != 0): slab =
-// class*4 + tap2 with class = (oy&1)*2 + (ox&1), tap2 = ty*2 + tx over the 2x2 source footprint; the entry is the SUM of the
-// 3x3 taps that land on that source pixel: parity 0 -> {k=0} , {k=1,2} ; parity 1 -> {k=0,1} , {k=2} (per axis), summed
-// ky-major in fp32 (one rounding per add, fixed order).
-__device__ __forceinline__ float packed_weight_value(const float* __restrict__ w, int cout, int cin, int taps, int fold,
-                                                     int slab, int n, int c) {
-  if (n >= cout || c >= cin) return 0.f;
-  const float* wk = w + ((long)n * cin + c) * taps;
-  if (!fold) return wk[slab];
-  const int cls = slab >> 2, t2 = slab & 3;
-  const int sy = cls >> 1, sx = cls & 1, ty = t2 >> 1, tx = t2 & 1;
-  const int ky0 = sy == 0 ? (ty == 0 ? 0 : 1) : (ty == 0 ? 0 : 2), ky1 = sy == 0 ? (ty == 0 ? 0 : 2) : (ty == 0 ? 1 : 2);
-  const int kx0 = sx == 0 ? (tx == 0 ? 0 : 1) : (tx == 0 ? 0 : 2), kx1 = sx == 0 ? (tx == 0 ? 0 : 2) : (tx == 0 ? 1 : 2);
-  float v = 0.f;
-  for (int ky = ky0; ky <= ky1; ++ky)
-    for (int kx = kx0; kx <= kx1; ++kx) v += wk[ky * 3 + kx];
-  return v;
-}
-
-__global__ void pack_weight_kernel(const float* __restrict__ w, int cout, int cin, int taps, int fold, int cout_pad,
-                                   int nchunks, float* __restrict__ packed, long total) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int k = (int)(i % CF_BK);
-  long r = i / CF_BK;
-  const int n = (int)(r % cout_pad);
-  r /= cout_pad;
-  const int chunk = (int)(r % nchunks);
-  const int slab = (int)(r / nchunks);
-  packed[i] = packed_weight_value(w, cout, cin, taps, fold, slab, n, chunk * CF_BK + k);
-}
-
-// 16-bit variants: [tap][cin_pad/32][cout_pad][32] bf16 or IEEE half (round-to-nearest-even), two values per 32-bit word.
-__global__ void pack_weight_bf16_kernel(const float* __restrict__ w, int cout, int cin, int taps, int fold, int cout_pad,
-                                        int nchunks, unsigned* __restrict__ packed, long total_words, int f16) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total_words) return;
-  const int k2 = (int)(i % 16);  // word index inside the 32-channel row
-  long r = i / 16;
-  const int n = (int)(r % cout_pad);
-  r /= cout_pad;
-  const int chunk = (int)(r % nchunks);
-  const int slab = (int)(r / nchunks);
-  unsigned out = 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float v = packed_weight_value(w, cout, cin, taps, fold, slab, n, chunk * 32 + k2 * 2 + h);
-    if (f16) {
-      const _Float16 hv = (_Float16)v;
-      out |= (unsigned)__builtin_bit_cast(unsigned short, hv) << (16 * h);
-      continue;
-    }
-    unsigned u = __builtin_bit_cast(unsigned, v);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    out |= (u >> 16) << (16 * h);
-  }
-  packed[i] = out;
-}
-
 }  // namespace
-
-static int pack_bf16(const float* w, int cout, int cin, int fold, int cout_pad, int cin_pad, void* packed, cf_stream_t stream,
-                     int f16 = 0) {
-  CF_REQUIRE(w && packed, "cf_pack_conv_weight_bf16/f16: null pointer");
-  CF_REQUIRE(cin_pad % 32 == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % (f16 ? 32 : 64) == 0,
-             "cf_pack_conv_weight_bf16/f16: bad padding cin %d->%d cout %d->%d", cin, cin_pad, cout, cout_pad);
-  const int slabs = fold ? 16 : 9;
-  const long words = (long)slabs * cin_pad * cout_pad / 2;
-  hipLaunchKernelGGL(pack_weight_bf16_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout,
-                     cin, 9, fold, cout_pad, cin_pad / 32, reinterpret_cast<unsigned*>(packed), words, f16);
-  CF_CHECK_LAUNCH("cf_pack_conv_weight_bf16");
-  return CF_OK;
-}
-
-extern "C" int cf_pack_conv_weight_bf16(const float* w, int cout, int cin, int taps, int cout_pad, int cin_pad, void* packed,
-                                        cf_stream_t stream) {
-  CF_REQUIRE(taps == 9, "cf_pack_conv_weight_bf16: the bf16 path covers 3x3 convolutions (taps=9)");
-  return pack_bf16(w, cout, cin, 0, cout_pad, cin_pad, packed, stream);
-}
-
-extern "C" int cf_pack_conv_weight_up2x_bf16(const float* w, int cout, int cin, int cout_pad, int cin_pad, void* packed,
-                                             cf_stream_t stream) {
-  return pack_bf16(w, cout, cin, 1, cout_pad, cin_pad, packed, stream);
-}
-
-extern "C" int cf_pack_conv_weight_f16(const float* w, int cout, int cin, int taps, int cout_pad, int cin_pad, void* packed,
-                                       cf_stream_t stream) {
-  CF_REQUIRE(taps == 9, "cf_pack_conv_weight_f16: 3x3 weights only (taps=%d)", taps);
-  return pack_bf16(w, cout, cin, 0, cout_pad, cin_pad, packed, stream, 1);
-}
-
-extern "C" int cf_pack_conv_weight_up2x_f16(const float* w, int cout, int cin, int cout_pad, int cin_pad, void* packed,
-                                            cf_stream_t stream) {
-  return pack_bf16(w, cout, cin, 1, cout_pad, cin_pad, packed, stream, 1);
-}
-
-// fp32 layout [slab][cin_pad/16][cout_pad][16]: the plain taps, or (fold) the 16 folded slabs of the nearest-x2 + 3x3 convolution
-static int pack_f32(const char* name, const float* w, int cout, int cin, int taps, int fold, int cout_pad, int cin_pad, float* packed,
-                    cf_stream_t stream) {
-  CF_REQUIRE(w && packed, "%s: null pointer", name);
-  CF_REQUIRE(taps == 1 || taps == 9, "%s: taps must be 1 or 9 (got %d)", name, taps);
-  CF_REQUIRE(cin_pad % CF_BK == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % 32 == 0,
-             "%s: bad padding cin %d->%d cout %d->%d", name, cin, cin_pad, cout, cout_pad);
-  const long total = (long)(fold ? 16 : taps) * cin_pad * cout_pad;
-  hipLaunchKernelGGL(pack_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
-                     taps, fold, cout_pad, cin_pad / CF_BK, packed, total);
-  CF_CHECK_LAUNCH(name);
-  return CF_OK;
-}
-
-extern "C" int cf_pack_conv_weight_up2x(const float* w, int cout, int cin, int cout_pad, int cin_pad, float* packed,
-                                        cf_stream_t stream) {
-  return pack_f32("cf_pack_conv_weight_up2x", w, cout, cin, 9, 1, cout_pad, cin_pad, packed, stream);
-}
-
-extern "C" int64_t cf_packed_weight_elems(int cin_pad, int taps, int cout_pad) {
-  return (int64_t)taps * cin_pad * cout_pad;
-}
-
-extern "C" int cf_pack_conv_weight(const float* w, int cout, int cin, int taps, int cout_pad, int cin_pad,
-                                   float* packed, cf_stream_t stream) {
-  return pack_f32("cf_pack_conv_weight", w, cout, cin, taps, 0, cout_pad, cin_pad, packed, stream);
-}
 
 // What conv_validate derives for the pieces below (ext: the general instantiations, narrow: 64-wide N tiles of a small-M layer).
 struct ConvFacts { int ld0, ld1, ldo; bool ext, few_cout, narrow; };

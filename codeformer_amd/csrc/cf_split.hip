@@ -632,61 +632,6 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
   }
 }
 
-// packed slab entry (cf_igemm.hip's rule): plain tap, or the pre-summed taps of the folded nearest-x2 + 3x3
-__device__ __forceinline__ float split_weight_value(const float* __restrict__ w, int cout, int cin, int fold, int slab, int n, int c) {
-  if (n >= cout || c >= cin) return 0.f;
-  const float* wk = w + ((long)n * cin + c) * 9;
-  if (fold == 3) return w[(long)n * cin + c];  // 1x1 weight [cout][cin]
-  if (!fold) return wk[slab];
-  if (fold == 2) return 0.f;  // (stride-2 form: handled by split_weight_value_s2)
-  const int cls = slab >> 2, t2 = slab & 3;
-  const int sy = cls >> 1, sx = cls & 1, ty = t2 >> 1, tx = t2 & 1;
-  const int ky0 = sy == 0 ? (ty == 0 ? 0 : 1) : (ty == 0 ? 0 : 2), ky1 = sy == 0 ? (ty == 0 ? 0 : 2) : (ty == 0 ? 1 : 2);
-  const int kx0 = sx == 0 ? (tx == 0 ? 0 : 1) : (tx == 0 ? 0 : 2), kx1 = sx == 0 ? (tx == 0 ? 0 : 2) : (tx == 0 ? 1 : 2);
-  float v = 0.f;
-  for (int ky = ky0; ky <= ky1; ++ky)
-    for (int kx = kx0; kx <= kx1; ++kx) v += wk[ky * 3 + kx];
-  return v;
-}
-
-// Stride-2 form (Downsample: zero row / column appended bottom / right, 3x3 stride 2 -- vqgan_arch.py:117-126): the input is read as the
-// space-to-depth tensor X[i][j][(p, q, c)] = x[2i + p][2j + q][c] (4C channels, no copy: see the row-pair addressing of the gather) and
-// the convolution becomes a 2x2 stride-1 one, out[i][j] = sum_{ty,tx} W'[ty][tx] . X[i + ty][j + tx], with
-// W'[ty][tx][(p, q, c)] = w[2ty + p][2tx + q][c] where that tap exists and 0 elsewhere (7 of the 16 blocks are zero).
-__device__ __forceinline__ float split_weight_value_s2(const float* __restrict__ w, int cout, int cin, int tap, int n, int c4) {
-  if (n >= cout || c4 >= 4 * cin) return 0.f;
-  const int p = c4 / (2 * cin), q = (c4 / cin) & 1, c = c4 % cin;
-  const int ky = 2 * (tap >> 1) + p, kx = 2 * (tap & 1) + q;
-  if (ky > 2 || kx > 2) return 0.f;
-  return w[((long)n * cin + c) * 9 + ky * 3 + kx];
-}
-
-// [class][cin/32][tap][cout_pad][32 words] (class = 1 plain / 4 folded / 1 stride-2 form with 4 cin channels): words 0..15 = hi halves of channels (2k, 2k+1), 16..31 = lo
-__global__ void pack_weight_f16x2_kernel(const float* __restrict__ w, int cout, int cin, int fold, int cout_pad, int nchunks,
-                                         float scale, unsigned* __restrict__ packed, long total_words) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total_words) return;
-  const int k2 = (int)(i & 15), part = (int)((i >> 4) & 1);
-  long r = i >> 5;
-  const int n = (int)(r % cout_pad);
-  r /= cout_pad;
-  const int taps = fold == 3 ? 1 : fold ? 4 : 9;
-  const int tap = (int)(r % taps);
-  r /= taps;
-  const int chunk = (int)(r % nchunks);
-  const int slab = (int)(r / nchunks) * 4 + tap;  // class * 4 + tap (class = 0 when not folded)
-  unsigned out = 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int c = chunk * 32 + k2 * 2 + h;
-    const float v = (fold == 2 ? split_weight_value_s2(w, cout, cin, tap, n, c) : split_weight_value(w, cout, cin, fold, slab, n, c)) * scale;  // exact: power of two
-    const _Float16 hi = (_Float16)v;
-    const _Float16 hv = part ? (_Float16)(v - (float)hi) : hi;
-    out |= (unsigned)__builtin_bit_cast(unsigned short, hv) << (16 * h);
-  }
-  packed[i] = out;
-}
-
 template <int TAPS, int NI, bool S2 = false, bool BIO = false>
 int split_launch(SplitArgs& k, int batch, hipStream_t stream) {
   using C = SplitCfg<TAPS, NI, SP_WM>;
@@ -700,22 +645,6 @@ int split_launch(SplitArgs& k, int batch, hipStream_t stream) {
 }
 
 }  // namespace
-
-extern "C" int cf_pack_conv_weight_f16x2(const float* w, int cout, int cin, int up2x, int cout_pad, int cin_pad, float scale,
-                                         void* packed, cf_stream_t stream) {
-  CF_REQUIRE(w && packed, "cf_pack_conv_weight_f16x2: null pointer");
-  CF_REQUIRE((up2x == 2 ? 4 * cin_pad : cin_pad) % 32 == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % 64 == 0,
-             "cf_pack_conv_weight_f16x2: bad padding cin %d->%d cout %d->%d", cin, cin_pad, cout, cout_pad);
-  int ex = 0;
-  CF_REQUIRE(scale > 0.f && frexpf(scale, &ex) == 0.5f, "cf_pack_conv_weight_f16x2: scale %g is not a power of two", (double)scale);
-  CF_REQUIRE(up2x >= 0 && up2x <= 3, "cf_pack_conv_weight_f16x2: form %d (0 plain 3x3, 1 nearest-x2 folded, 2 stride 2, 3 1x1)", up2x);
-  CF_REQUIRE(up2x != 2 || (cin_pad == cin && cin % 16 == 0), "cf_pack_conv_weight_f16x2: the stride-2 form needs cin %% 16 == 0, unpadded");
-  const long words = (long)(up2x == 3 ? 1 : up2x ? 16 : 9) * cin_pad * cout_pad;  // two halves per word, hi + lo per channel: one word per weight
-  hipLaunchKernelGGL(pack_weight_f16x2_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
-                     up2x, cout_pad, (up2x == 2 ? 4 * cin_pad : cin_pad) / 32, scale, reinterpret_cast<unsigned*>(packed), words);
-  CF_CHECK_LAUNCH("cf_pack_conv_weight_f16x2");
-  return CF_OK;
-}
 
 // Called by cf_conv2d (cf_igemm.hip) for descriptors with bf16_mfma == CF_OPERAND_F16X2; the common argument checks have run.
 int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {

@@ -944,164 +944,21 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   }
 }
 
-// U' = scale * G' g G'^T (fp64, rounded once to fp32) as hi = f16(U'), lo = f16(U' - hi), in MFMA-operand order
-// [pos = xi*6 + nu][cin_pad/16][cout_pad/16][lane 64][4 words: hi, hi, lo, lo]; a lane's 16 bytes are the hi and the lo halves of
-// U'[n = block*16 + (lane&15)][c = chunk*16 + (lane>>4)*4 + 0..3]  (v_mfma_f32_16x16x16_f16 B operand, hi | lo in one dwordx4).
-__global__ void pack_weight_wf43_kernel(const float* __restrict__ w, int cout, int cin, int cout_pad, int nchunks, float scale,
-                                        unsigned* __restrict__ packed, long total, int k32, int f32) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // one 32-bit word = two halves (or one fp32 value)
-  if (i >= total) return;
-  if (f32) {
-    // fp32 operands (v_mfma_f32_16x16x4_f32): word j of a lane's 16 (32) bytes = U'[n = block*16 + (lane&15)][c = chunk*KS + 4 j + (lane>>4)]
-    const int j = k32 ? (int)(i & 7) : (int)(i & 3), ln = k32 ? (int)((i >> 3) & 63) : (int)((i >> 2) & 63);
-    long r = k32 ? i >> 9 : i >> 8;
-    const int ntiles = cout_pad / 16;
-    const int nn = (int)(r % ntiles) * 16 + (ln & 15);
-    r /= ntiles;
-    const int chunk = (int)(r % nchunks), pos = (int)(r / nchunks);
-    const int c = chunk * (k32 ? 32 : CF_BK) + 4 * j + (ln >> 4);
-    const int xi = pos / 6, nu = pos % 6;
-    const double Gf[6][3] = {{4.0, 0.0, 0.0},           {-32.0 / 15.0, -16.0 / 15.0, -8.0 / 15.0}, {-32.0 / 15.0, 16.0 / 15.0, -8.0 / 15.0},
-                             {1.0 / 15.0, 2.0 / 15.0, 4.0 / 15.0}, {1.0 / 15.0, -2.0 / 15.0, 4.0 / 15.0},  {0.0, 0.0, 4.0}};
-    float val = 0.f;
-    if (nn < cout && c < cin) {
-      const float* g = w + ((long)nn * cin + c) * 9;
-      double u = 0.0;
-#pragma unroll
-      for (int y = 0; y < 3; ++y) {
-        double rowv = 0.0;
-#pragma unroll
-        for (int x = 0; x < 3; ++x) rowv += (double)g[y * 3 + x] * Gf[nu][x];
-        u += Gf[xi][y] * rowv;
-      }
-      val = (float)u;
-    }
-    packed[i] = __builtin_bit_cast(unsigned, val);
-    return;
-  }
-  // 16-channel slabs: a lane's 16 bytes = [hi k0..3 | lo k0..3]; 32-channel slabs (k32): a lane's 32 bytes = [hi k0..7 | lo k0..7]
-  const int e = k32 ? (int)(i & 3) : (int)(i & 1), part = k32 ? (int)((i >> 2) & 1) : (int)((i >> 1) & 1);
-  const int ln = k32 ? (int)((i >> 3) & 63) : (int)((i >> 2) & 63);
-  long r = k32 ? i >> 9 : i >> 8;
-  const int ntiles = cout_pad / 16;
-  const int nn = (int)(r % ntiles) * 16 + (ln & 15);
-  r /= ntiles;
-  const int chunk = (int)(r % nchunks);
-  const int pos = (int)(r / nchunks);
-  const int xi = pos / 6, nu = pos % 6;
-  // rows of G' = D^-1 G for the points (0, 1/2, -1/2, 2, -2, inf), D = diag(1/4, 1/4, 1/4, 1/2, 1/2, 1/4)
-  const double Gm[6][3] = {{4.0, 0.0, 0.0},           {-32.0 / 15.0, -16.0 / 15.0, -8.0 / 15.0}, {-32.0 / 15.0, 16.0 / 15.0, -8.0 / 15.0},
-                           {1.0 / 15.0, 2.0 / 15.0, 4.0 / 15.0}, {1.0 / 15.0, -2.0 / 15.0, 4.0 / 15.0},  {0.0, 0.0, 4.0}};
-  unsigned out = 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int c = k32 ? chunk * 32 + (ln >> 4) * 8 + e * 2 + h : chunk * CF_BK + (ln >> 4) * 4 + e * 2 + h;
-    float val = 0.f;
-    if (nn < cout && c < cin) {
-      const float* g = w + ((long)nn * cin + c) * 9;
-      double u = 0.0;
-#pragma unroll
-      for (int y = 0; y < 3; ++y) {
-        double rowv = 0.0;
-#pragma unroll
-        for (int x = 0; x < 3; ++x) rowv += (double)g[y * 3 + x] * Gm[nu][x];
-        u += Gm[xi][y] * rowv;
-      }
-      val = (float)(u * (double)scale);
-    }
-    const _Float16 hi = (_Float16)val;
-    const _Float16 hv = part ? (_Float16)(val - (float)hi) : hi;
-    out |= (unsigned)__builtin_bit_cast(unsigned short, hv) << (16 * h);
-  }
-  packed[i] = out;
-}
-
-// The sub-pixel F(4x4,2x2) form (UP): U_p = G42 g_p G42^T per output parity p = 2 a + b, g_p = the 3x3 taps folded to the 2x2 the parity sees on the
-// low-resolution image (fp64 throughout, rounded once), in the fp32 fragment order of the 32-channel-slab form:
-// [phase][pos = xi*5 + nu][cin/32][cout/16][lane 64][8 words], word j = U_p[n = block*16 + (lane&15)][c = chunk*32 + 4 j + (lane>>4)].
-__global__ void pack_weight_wf42_up_kernel(const float* __restrict__ w, int cout, int cin, int nchunks, float* __restrict__ packed, long total) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int j = (int)(i & 7), ln = (int)((i >> 3) & 63);
-  long r = i >> 9;
-  const int ntiles = cout / 16;
-  const int nn = (int)(r % ntiles) * 16 + (ln & 15);
-  r /= ntiles;
-  const int chunk = (int)(r % nchunks);
-  r /= nchunks;
-  const int pos = (int)(r % 25), phase = (int)(r / 25);
-  const int c = chunk * 32 + 4 * j + (ln >> 4);
-  const int xi = pos / 5, nu = pos % 5, pa = phase >> 1, pb = phase & 1;
-  const double G[5][2] = {{1.0, 0.0}, {-2.0 / 9.0, 2.0 / 9.0}, {-8.0 / 9.0, -4.0 / 9.0}, {1.0 / 9.0, 2.0 / 9.0}, {0.0, 1.0}};
-  const float* g = w + ((long)nn * cin + c) * 9;
-  // fold: parity 0 sees [g0, g1 + g2], parity 1 [g0 + g1, g2]: tap t of the 3 belongs to folded tap (t + 1 - parity) >> 1
-  double f[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-#pragma unroll
-  for (int y = 0; y < 3; ++y)
-#pragma unroll
-    for (int x = 0; x < 3; ++x) f[(y + 1 - pa) >> 1][(x + 1 - pb) >> 1] += (double)g[y * 3 + x];
-  double u = 0.0;
-#pragma unroll
-  for (int y = 0; y < 2; ++y) u += G[xi][y] * (f[y][0] * G[nu][0] + f[y][1] * G[nu][1]);
-  packed[i] = (float)u;
-}
-
 }  // namespace
 
-// Form of the 16-wave (128-output-channel) workgroup; packing and launch agree through this one function:
-//   1  32-channel slabs, two barrier intervals per slab (rounds 4: v_mfma_f32_16x16x32_f16)            CF_F43_WIDE=k32
-//   0  16-channel slabs, two intervals (A/B only; also what cin % 32 != 0 runs in mode 1)                CF_F43_WIDE=k16
-static int f4_wide_mode() {
-  static const int v = [] {
+// Whether a layer of (cout, cin) runs the 16-wave (128-output-channel) workgroup on 32-channel slabs (two barrier intervals per slab, rounds 4:
+// v_mfma_f32_16x16x32_f16): where both channel counts allow, unless CF_F43_WIDE=k16 asks for 16-channel slabs (A/B only; also what cin % 32 != 0
+// runs).  Packing (cf_pack.hip) and launch agree through this one function.
+bool cf_wf43_k32(int cout, int cin) {
+  static const bool enabled = [] {
     const char* w = getenv("CF_F43_WIDE");
-    if (!w || !strcmp(w, "k32")) return 1;
-    if (!strcmp(w, "k16")) return 0;
+    if (!w || !strcmp(w, "k32")) return true;
+    if (!strcmp(w, "k16")) return false;
     // (an A/B switch read once per process: a mistyped value must not silently measure another form)
     fprintf(stderr, "libcodeformer_hip: CF_F43_WIDE=%s is not a form of the 16-wave F(4,3) workgroup (k32 | k16): using k32\n", w);
-    return 1;
+    return true;
   }();
-  return v;
-}
-static bool f4_k32_enabled() { return f4_wide_mode() == 1; }
-
-extern "C" int cf_pack_conv_weight_winograd43_f16x2(const float* w, int cout, int cin, int cout_pad, int cin_pad, float scale, void* packed,
-                                                    cf_stream_t stream) {
-  CF_REQUIRE(w && packed, "cf_pack_conv_weight_winograd43_f16x2: null pointer");
-  CF_REQUIRE(cin_pad % CF_BK == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % 64 == 0,
-             "cf_pack_conv_weight_winograd43_f16x2: bad padding cin %d->%d cout %d->%d", cin, cin_pad, cout, cout_pad);
-  int ex = 0;
-  CF_REQUIRE(scale > 0.f && frexpf(scale, &ex) == 0.5f, "cf_pack_conv_weight_winograd43_f16x2: scale %g is not a power of two", (double)scale);
-  const long total = 36L * cin_pad * cout_pad;  // 32-bit words: hi + lo half per weight
-  // the layout follows the form cf_conv2d will run (cf_wf43_form below): 32-channel slabs for the 16-wave form where cin allows
-  const int k32 = cout_pad % 128 == 0 && cin_pad % 32 == 0 && f4_k32_enabled();
-  hipLaunchKernelGGL(pack_weight_wf43_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
-                     cout_pad, cin_pad / (k32 ? 32 : CF_BK), scale, reinterpret_cast<unsigned*>(packed), total, k32, 0);
-  CF_CHECK_LAUNCH("cf_pack_conv_weight_winograd43_f16x2");
-  return CF_OK;
-}
-
-extern "C" int cf_pack_conv_weight_winograd43(const float* w, int cout, int cin, int cout_pad, int cin_pad, void* packed, cf_stream_t stream) {
-  CF_REQUIRE(w && packed, "cf_pack_conv_weight_winograd43: null pointer");
-  CF_REQUIRE(cin_pad % CF_BK == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % 64 == 0,
-             "cf_pack_conv_weight_winograd43: bad padding cin %d->%d cout %d->%d", cin, cin_pad, cout, cout_pad);
-  const long total = 36L * cin_pad * cout_pad;  // fp32 words
-  const int k32 = cout_pad % 128 == 0 && cin_pad % 32 == 0 && f4_k32_enabled();   // (the rule of the split-half packing: the form cf_conv2d will run)
-  hipLaunchKernelGGL(pack_weight_wf43_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
-                     cout_pad, cin_pad / (k32 ? 32 : CF_BK), 1.f, reinterpret_cast<unsigned*>(packed), total, k32, 1);
-  CF_CHECK_LAUNCH("cf_pack_conv_weight_winograd43");
-  return CF_OK;
-}
-
-extern "C" int cf_pack_conv_weight_winograd42_up(const float* w, int cout, int cin, int cout_pad, int cin_pad, void* packed, cf_stream_t stream) {
-  CF_REQUIRE(w && packed, "cf_pack_conv_weight_winograd42_up: null pointer");
-  CF_REQUIRE(cin_pad == cin && cout_pad == cout && cin > 0 && cout > 0 && cin % 32 == 0 && cout % 128 == 0,
-             "cf_pack_conv_weight_winograd42_up: bad padding cin %d->%d cout %d->%d (cin %% 32 == 0, cout %% 128 == 0, no padding)", cin, cin_pad, cout, cout_pad);
-  CF_REQUIRE(f4_k32_enabled(), "cf_pack_conv_weight_winograd42_up: the sub-pixel form runs on 32-channel slabs (CF_F43_WIDE=k16 is set)");
-  const long total = 100L * cin * cout;  // fp32 words: 4 phases x 25 positions
-  hipLaunchKernelGGL(pack_weight_wf42_up_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin, cin / 32,
-                     reinterpret_cast<float*>(packed), total);
-  CF_CHECK_LAUNCH("cf_pack_conv_weight_winograd42_up");
-  return CF_OK;
+  return cout % 128 == 0 && cin % 32 == 0 && enabled;
 }
 
 // Called by cf_conv2d (cf_igemm.hip) for descriptors with winograd == 2; the common argument checks have run there.
@@ -1114,8 +971,7 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
   // (weights: cf_pack_conv_weight_winograd42_up; what the network runs).  upsample == 1: F(4,3) on the virtually upsampled image through the
   // upsampling gather (weights: the plain cf_pack_conv_weight_winograd43 packing of the 3x3 kernel).
   const bool sub = d->upsample == 2;
-  CF_REQUIRE(!d->upsample || (f32 && d->prologue == CF_PRO_NONE && d->epilogue == CF_EPI_NONE && d->c1 == 0 && d->cout % 128 == 0 && d->c0 % 32 == 0 &&
-                              f4_k32_enabled()),
+  CF_REQUIRE(!d->upsample || (f32 && d->prologue == CF_PRO_NONE && d->epilogue == CF_EPI_NONE && d->c1 == 0 && cf_wf43_k32(d->cout, d->c0)),
              "cf_conv2d(winograd 2, upsample): fp32 operands, one input with c0 %% 32 == 0, cout %% 128 == 0, no prologue / epilogue operand");
   CF_REQUIRE(!sub || (d->hin % F4_TH == 0 && d->win % F4_TW == 0 && d->hout == 2 * d->hin && d->wout == 2 * d->win),
              "cf_conv2d(winograd 2, upsample 2): needs an input of %dx%d multiples (got %dx%d)", F4_TH, F4_TW, d->hin, d->win);
@@ -1129,7 +985,7 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
   CF_REQUIRE((long)d->hout * d->wout <= (1L << 21), "cf_conv2d(winograd 2): at most 2^21 pixels per image (got %dx%d)", d->hout, d->wout);
   CF_REQUIRE((long)d->hout * d->wout * (d->c0 > d->cout ? d->c0 : d->cout) * 4 < (1L << 31) && (long)d->hout * d->wout * d->c1 * 4 < (1L << 31),
              "cf_conv2d(winograd 2): an image of a tensor must stay below 2^31 bytes (%dx%d, %d / %d / %d channels)", d->hout, d->wout, d->c0, d->c1, d->cout);
-  const int tab_max = (d->cout % 128 == 0 && (d->c0 + d->c1) % 32 == 0 && f4_k32_enabled()) ? F4_TAB_32 : F4_TAB;   // (the 32-channel-slab form holds 512 GroupNorm rows)
+  const int tab_max = cf_wf43_k32(d->cout, d->c0 + d->c1) ? F4_TAB_32 : F4_TAB;   // (the 32-channel-slab form holds 512 GroupNorm rows)
   CF_REQUIRE(d->c0 + d->c1 <= tab_max, "cf_conv2d(winograd 2): at most %d input channels in this form (got %d)", tab_max, d->c0 + d->c1);
   CF_REQUIRE(cf_epi_is_quad_triple(d), "cf_conv2d(winograd 2): epilogues are none / residual / SFT");
   CF_REQUIRE(cf_dense_zero_pad(d) && d->split_k < 1, "cf_conv2d(winograd 2): reads / writes dense tensors with zero padding, no split_k");
@@ -1147,7 +1003,7 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
   a.tiles_per_img = a.tiles_x * (d->hout / F4_TH);
   a.nparts = a.tiles_per_img;
   const bool wide = d->cout % 128 == 0;                      // 16 waves x 128 channels where the layer has them ...
-  const bool k32 = wide && (d->c0 + d->c1) % 32 == 0 && f4_k32_enabled();   // ... on 32-channel slabs where cin allows: the rule the pack functions lay the weight out by
+  const bool k32 = cf_wf43_k32(d->cout, d->c0 + d->c1);   // ... on 32-channel slabs where cin allows: the rule the pack functions lay the weight out by
   CF_REQUIRE(!k32 || d->c0 % 32 == 0, "cf_conv2d(winograd 2): with cout %% 128 == 0 and cin %% 32 == 0 the concat boundary must be a multiple of 32 (c0 = %d)", d->c0);
   a.ntn = d->cout / (wide ? 128 : 64);
   a.nt_out = cf_nt_store((long)d->batch * d->hout * d->wout * d->cout * 4);

@@ -480,117 +480,7 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
   }
 }
 
-// U = G g G^T per (n, c), evaluated in fp64 and rounded once, stored in MFMA-operand order
-// [pos][cin_pad/16][cout_pad/32][kg 2][lane 64][4]: element = U[n = tile*32 + (lane&31)][c = chunk*16 + kg*8 + (lane>>5)*4 + e]
-__global__ void pack_weight_winograd_kernel(const float* __restrict__ w, int cout, int cin, int cout_pad, int nchunks,
-                                            float* __restrict__ packed, long total) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int e = (int)(i & 3), ln = (int)((i >> 2) & 63), kg = (int)((i >> 8) & 1);
-  long r = i >> 9;
-  const int ntiles = cout_pad / 32;
-  const int n = (int)(r % ntiles) * 32 + (ln & 31);
-  r /= ntiles;
-  const int chunk = (int)(r % nchunks);
-  const int pos = (int)(r / nchunks);
-  const int c = chunk * CF_BK + kg * 8 + (ln >> 5) * 4 + e;
-  float val = 0.f;
-  if (n < cout && c < cin) {
-    const float* g = w + ((long)n * cin + c) * 9;
-    const int xi = pos >> 2, nu = pos & 3;
-    // row xi of G g : combination of the three kernel rows
-    double row[3];
-#pragma unroll
-    for (int x = 0; x < 3; ++x) {
-      const double g0 = g[x], g1 = g[3 + x], g2 = g[6 + x];
-      row[x] = xi == 0 ? g0 : (xi == 1 ? 0.5 * (g0 + g1 + g2) : (xi == 2 ? 0.5 * (g0 - g1 + g2) : g2));
-    }
-    const double u = nu == 0 ? row[0] : (nu == 1 ? 0.5 * (row[0] + row[1] + row[2]) : (nu == 2 ? 0.5 * (row[0] - row[1] + row[2]) : row[2]));
-    val = (float)u;
-  }
-  packed[i] = val;
-}
-
-// H2 operands: U' = scale * G g G^T (fp64, rounded once to fp32) as hi = f16(U'), lo = f16(U' - hi), in MFMA-operand order
-// [pos][cin_pad/16][cout_pad/32][part: hi, lo][lane 64][4 words]; a lane's 16 bytes are the 8 halves of
-// U'[n = tile*32 + (lane&31)][c = chunk*16 + (lane>>5)*8 + 0..7]  (v_mfma_f32_32x32x16_f16 B operand).
-// bf16_single: the hi slot holds bf16(U') instead and the lo slot zeros (the single-operand bf16 form of cf_wsplit.hip; its IEEE-half
-// form reads the hi slot of the split packing as it is).
-__global__ void pack_weight_winograd_f16x2_kernel(const float* __restrict__ w, int cout, int cin, int cout_pad, int nchunks, float scale,
-                                                  unsigned* __restrict__ packed, long total, int bf16_single) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // one 32-bit word = two halves
-  if (i >= total) return;
-  const int e = (int)(i & 3), ln = (int)((i >> 2) & 63), part = (int)((i >> 8) & 1);
-  long r = i >> 9;
-  const int ntiles = cout_pad / 32;
-  const int n = (int)(r % ntiles) * 32 + (ln & 31);
-  r /= ntiles;
-  const int chunk = (int)(r % nchunks);
-  const int pos = (int)(r / nchunks);
-  const int xi = pos >> 2, nu = pos & 3;
-  unsigned out = 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int c = chunk * CF_BK + (ln >> 5) * 8 + e * 2 + h;
-    float val = 0.f;
-    if (n < cout && c < cin) {
-      const float* g = w + ((long)n * cin + c) * 9;
-      double row[3];
-#pragma unroll
-      for (int x = 0; x < 3; ++x) {
-        const double g0 = g[x], g1 = g[3 + x], g2 = g[6 + x];
-        row[x] = xi == 0 ? g0 : (xi == 1 ? 0.5 * (g0 + g1 + g2) : (xi == 2 ? 0.5 * (g0 - g1 + g2) : g2));
-      }
-      const double u = nu == 0 ? row[0] : (nu == 1 ? 0.5 * (row[0] + row[1] + row[2]) : (nu == 2 ? 0.5 * (row[0] - row[1] + row[2]) : row[2]));
-      val = (float)(u * (double)scale);
-    }
-    if (bf16_single) {
-      const __bf16 bv = (__bf16)(part ? 0.f : val);
-      out |= (unsigned)__builtin_bit_cast(unsigned short, bv) << (16 * h);
-    } else {
-      const _Float16 hi = (_Float16)val;
-      const _Float16 hv = part ? (_Float16)(val - (float)hi) : hi;
-      out |= (unsigned)__builtin_bit_cast(unsigned short, hv) << (16 * h);
-    }
-  }
-  packed[i] = out;
-}
-
 }  // namespace
-
-static int pack_winograd_halves(const float* w, int cout, int cin, int cout_pad, int cin_pad, float scale, void* packed, cf_stream_t stream,
-                                int bf16_single) {
-  CF_REQUIRE(w && packed, "cf_pack_conv_weight_winograd_f16x2: null pointer");
-  CF_REQUIRE(cin_pad % CF_BK == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % 64 == 0,
-             "cf_pack_conv_weight_winograd_f16x2: bad padding cin %d->%d cout %d->%d", cin, cin_pad, cout, cout_pad);
-  int ex = 0;
-  CF_REQUIRE(scale > 0.f && frexpf(scale, &ex) == 0.5f, "cf_pack_conv_weight_winograd_f16x2: scale %g is not a power of two", (double)scale);
-  const long total = 16L * cin_pad * cout_pad;  // 32-bit words: hi + lo half per weight
-  hipLaunchKernelGGL(pack_weight_winograd_f16x2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                     cout, cin, cout_pad, cin_pad / CF_BK, scale, reinterpret_cast<unsigned*>(packed), total, bf16_single);
-  CF_CHECK_LAUNCH("cf_pack_conv_weight_winograd_f16x2");
-  return CF_OK;
-}
-extern "C" int cf_pack_conv_weight_winograd_f16x2(const float* w, int cout, int cin, int cout_pad, int cin_pad, float scale, void* packed,
-                                                  cf_stream_t stream) {
-  return pack_winograd_halves(w, cout, cin, cout_pad, cin_pad, scale, packed, stream, 0);
-}
-extern "C" int cf_pack_conv_weight_winograd_bf16(const float* w, int cout, int cin, int cout_pad, int cin_pad, float scale, void* packed,
-                                                 cf_stream_t stream) {
-  return pack_winograd_halves(w, cout, cin, cout_pad, cin_pad, scale, packed, stream, 1);
-}
-
-extern "C" int cf_pack_conv_weight_winograd(const float* w, int cout, int cin, int cout_pad, int cin_pad, float* packed,
-                                            cf_stream_t stream) {
-  CF_REQUIRE(w && packed, "cf_pack_conv_weight_winograd: null pointer");
-  CF_REQUIRE(cin_pad % CF_BK == 0 && cin_pad >= cin && cout_pad >= cout && cout_pad % 64 == 0,
-             "cf_pack_conv_weight_winograd: bad padding cin %d->%d cout %d->%d", cin, cin_pad, cout, cout_pad);
-  const long total = 16L * cin_pad * cout_pad;
-  hipLaunchKernelGGL(pack_weight_winograd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                     cout, cin, cout_pad, cin_pad / CF_BK, packed, total);
-  CF_CHECK_LAUNCH("cf_pack_conv_weight_winograd");
-  return CF_OK;
-}
 
 // Called by cf_conv2d (cf_igemm.hip) for descriptors with winograd != 0; the common argument checks have run there.
 int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {

@@ -340,20 +340,25 @@ def pack_scale(wmax):
     return 1.0 if wmax == 0.0 or not math.isfinite(wmax) else 2.0 ** (14 - math.frexp(wmax)[1] + 1)
 
 
+# The weight-side Winograd matrices (what cf_pack.hip evaluates in fp64): G of F(2x2,3x3); G' = D^-1 G of F(4x4,3x3) for the points (0, +-1/2, +-2, inf),
+# the matrix cf_wf43.hip documents; G42 of the sub-pixel F(4x4,2x2) form below.
+G23 = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+G43 = ((4.0, 0.0, 0.0), (-32 / 15, -16 / 15, -8 / 15), (-32 / 15, 16 / 15, -8 / 15), (1 / 15, 2 / 15, 4 / 15), (1 / 15, -2 / 15, 4 / 15), (0.0, 0.0, 4.0))
+G42 = ((1.0, 0.0), (-2 / 9, 2 / 9), (-8 / 9, -4 / 9), (1 / 9, 2 / 9), (0.0, 1.0))
+
+
+def _domain_max(w, G):
+    """max |G g G^T| over a (cout, cin, 3, 3) weight in fp64: every position in one tensor, ONE reduction / host read-back per weight."""
+    Gm = torch.tensor(G, dtype=torch.float64, device=w.device)
+    return float(torch.einsum('xa,kcab,yb->kcxy', Gm, w.double(), Gm).abs().max())
+
+
 def _f23_max(w):
-    """max |G g G^T| of Winograd F(2x2,3x3) in fp64 (elementwise: G's rows are g0, (g0 + g1 + g2)/2, (g0 - g1 + g2)/2, g2), all 16 positions
-    in one tensor and ONE reduction / host read-back per weight."""
-    g = w.double()
-    r = torch.stack((g[:, :, 0], 0.5 * (g[:, :, 0] + g[:, :, 1] + g[:, :, 2]), 0.5 * (g[:, :, 0] - g[:, :, 1] + g[:, :, 2]), g[:, :, 2]), dim=2)
-    u = torch.stack((r[..., 0], 0.5 * (r[..., 0] + r[..., 1] + r[..., 2]), 0.5 * (r[..., 0] - r[..., 1] + r[..., 2]), r[..., 2]), dim=3)
-    return float(u.abs().max())
+    return _domain_max(w, G23)
 
 
 def _f43_max(w):
-    """max |G' g G'^T| of Winograd F(4x4,3x3) in fp64; G' = D^-1 G of the points (0, +-1/2, +-2, inf), the matrix cf_wf43.hip documents."""
-    Gm = torch.tensor([[4.0, 0.0, 0.0], [-32 / 15, -16 / 15, -8 / 15], [-32 / 15, 16 / 15, -8 / 15], [1 / 15, 2 / 15, 4 / 15],
-                       [1 / 15, -2 / 15, 4 / 15], [0.0, 0.0, 4.0]], dtype=torch.float64, device=w.device)
-    return float(torch.einsum('xa,kcab,yb->kcxy', Gm, w.double(), Gm).abs().max())
+    return _domain_max(w, G43)
 
 
 # Winograd F(4,2) for the sub-pixel phases of nearest x2 + 3x3 (conv2d(upsample=True) in precision 'fp32'): output parity a along an axis is the
@@ -364,7 +369,6 @@ def _f43_max(w):
 # 6.65: max 1.90e-5, mean 7.7e-7 (its mirror (0, 1, -1/2, -2) measures the same), against max 2.69e-5, mean 1.25e-6 of F(4x4,3x3) on the
 # upsampled image and mean 1.2e-6 of the symmetric sets (0, +-1, x).  Every entry of B42^T and A42^T is exact in fp32, so no row scaling is needed.
 B42T = ((1.0, -1.5, -1.5, 1.0, 0.0), (0.0, 1.0, -2.5, 1.0, 0.0), (0.0, -2.0, -1.0, 1.0, 0.0), (0.0, -0.5, 0.5, 1.0, 0.0), (0.0, 1.0, -1.5, -1.5, 1.0))
-G42 = ((1.0, 0.0), (-2 / 9, 2 / 9), (-8 / 9, -4 / 9), (1 / 9, 2 / 9), (0.0, 1.0))
 A42T = ((1.0, 1.0, 1.0, 1.0, 0.0), (0.0, -1.0, 0.5, 2.0, 0.0), (0.0, 1.0, 0.25, 4.0, 0.0), (0.0, -1.0, 0.125, 8.0, 1.0))
 
 

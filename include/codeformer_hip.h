@@ -227,7 +227,8 @@ int cf_conv2d_stats_parts(const cf_conv_desc* d);
 int64_t cf_conv2d_workspace_bytes(const cf_conv_desc* d);
 int cf_conv2d_tiles(const cf_conv_desc* d);
 
-/* Pack a PyTorch conv/linear weight [cout][cin][kh*kw] (taps = 1 or 9) into the kernel layout
+/* ---- weight packers (every cf_pack_* below is defined in csrc/cf_pack.hip, whatever kernel file reads its layout) --------
+ * Pack a PyTorch conv/linear weight [cout][cin][kh*kw] (taps = 1 or 9) into the kernel layout
  * [tap][cin_pad/16][cout_pad][16] (zero padded). */
 int cf_pack_conv_weight(const float* w, int cout, int cin, int taps, int cout_pad, int cin_pad,
                         float* packed, cf_stream_t stream);

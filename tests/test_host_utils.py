@@ -139,7 +139,7 @@ def test_layernorm_bound_decides_the_operands_of_the_transformer_gemms():
 
 
 def test_stride2_space_to_depth_identity():
-    """The algebra the stride-2 form of the split-half kernel rests on (cf_split.hip, split_weight_value_s2): Downsample's
+    """The algebra the stride-2 form of the split-half kernel rests on (cf_split.hip; its weight: Stride2Value of cf_pack.hip): Downsample's
     pad(0,1,0,1) + 3x3 stride-2 conv (vqgan_arch.py:117-126) equals a 2x2 stride-1 conv of the space-to-depth view
     X[(p,q,c)][i][j] = x[c][2i+p][2j+q] (zero row / column appended bottom / right) with W'[n][(p,q,c)][ty][tx] = w[n][c][2ty+p][2tx+q]
     where that tap exists and 0 elsewhere -- checked in fp64 on CPU, with the channel order (p, q, c) the gather uses."""
