@@ -659,6 +659,8 @@ int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query)
                "cf_conv2d(f16x2): stride 2 needs one dense input with c0 %% 16 == 0 (got %d), even size, padding bottom / right", d->c0);
   else
     CF_REQUIRE(d->c0 % 32 == 0 && d->c1 % 32 == 0, "cf_conv2d(f16x2): input channels (%d, %d) must be multiples of 32", d->c0, d->c1);
+  // (the space-to-depth view has 4 c0 channels and the kernel indexes its prologue tables by them: a [batch][c0] table would be read past its end)
+  CF_REQUIRE(!s2 || d->prologue == CF_PRO_NONE || d->prologue == CF_PRO_LEAKY, "cf_conv2d(f16x2): stride 2 takes prologue none / leaky (got %d)", d->prologue);
   CF_REQUIRE(d->cout % 64 == 0 && d->cout_pad == d->cout, "cf_conv2d(f16x2): cout %d / cout_pad %d must be one multiple of 64", d->cout,
              d->cout_pad);
   constexpr int TH = SP_WM * 4;

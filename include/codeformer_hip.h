@@ -93,7 +93,15 @@ enum cf_operand {
                            stride-1 NHWC convolutions (plain or `upsample`), channels % 32 == 0, cout % 64 == 0, 16x16-tile sizes;
                            prologues as the fp32 kernels, epilogues none / residual / SFT, statistics supported.  Since ABI v17 also
                            stride 2 (Downsample, vqgan_arch.py:117-126: pad_lo == 0, one dense input, c0 % 16 == 0, output a multiple
-                           of 8x16): a 2x2 convolution of the space-to-depth view of the input, weight packed with form 2 */
+                           of 8x16): a 2x2 convolution of the space-to-depth view of the input, weight packed with form 2; prologue none /
+                           leaky only (an affine prologue is refused: its [batch][c0] tables would be indexed by the view's 4 c0 channels).
+                           NON-FINITE INPUTS in that form: seven of its sixteen (tap, parity) weight blocks are zero by construction.
+                           With c0 % 32 == 0 each is a whole 32-channel slab and is skipped, and a NaN / inf pixel reaches exactly the
+                           outputs whose 3x3 window holds it.  With c0 % 32 == 16 (and under the A/B switch CF_S2_SKIP=0 at any c0) the
+                           zeros are multiplied, 0 * NaN is NaN, and the pixel (r, q) reaches every output (oy, ox) with
+                           2 oy <= r <= 2 oy + 3 and 2 ox <= q <= 2 ox + 3 -- the 2x2 window of the space-to-depth view, one output row /
+                           column more than the 3x3 window for an odd r / q.  Finite inputs give the same bits either way; the network's
+                           own stride-2 layers have c0 % 32 == 0 (tests/test_gpu_conv_geom.py pins both sets) */
 };
 
 /* Border handling of the 3x3 gather (general instantiations; CodeFormer itself only uses zero padding) */

@@ -219,29 +219,29 @@ def tap_perm(cin, cout, seed=5):
     return p, sign
 
 
-def tap_weight(cin, cout, tap):
+def tap_weight(cin, cout, tap, k=3):
     p, sign = tap_perm(cin, cout)
-    w = torch.zeros(cout, cin, 3, 3)
-    w[torch.arange(cout), p, tap // 3, tap % 3] = sign
+    w = torch.zeros(cout, cin, k, k)
+    w[torch.arange(cout), p, tap // k, tap % k] = sign
     return w
 
 
-@functools.lru_cache(maxsize=None)
-def family(name, key, variant=0):
-    """-> dict(x, w, b, sc, sh, res, ss, pro, epi, sft_w, acted): float32 CPU tensors.  Upsampling shapes take prologue none and no epilogue operand
-    (the only form w43_up has).  variant: int_coded's (prologue, epilogue) pair; tap_shift's tap."""
-    B, H, W, cin, cout, cs, up = SHAPES[key]
-    Ho, Wo = (2 * H, 2 * W) if up else (H, W)
-    seed = 1000 + 17 * sorted(SHAPES).index(key)
+def family_at(name, geom, seed, variant=0, k=3, out_hw=None, positions=None, key=None, bare_up=True):
+    """The recipe of family() at any geometry: geom = (B, H, W of the input, cin, cout, upsample); k = 3 | 1 the kernel's side; out_hw the output
+    size where it is neither the input's nor twice it (stride 2); positions(image) -> the one-hot pixels of an image (default: onehot_positions); bare_up: upsampling shapes take prologue none and no
+    epilogue operand.
+    family(name, key, variant) is this function at SHAPES[key] with the seed of the key, bit for bit (tools/conv_geom_check.py draws its cases here)."""
+    B, H, W, cin, cout, up = geom
+    Ho, Wo = out_hw if out_hw is not None else (2 * H, 2 * W) if up else (H, W)
     pro, epi, sft_w = PRO_AFFINE, EPI_NONE, 0.7
     sc, sh = torch.rand(B, cin, generator=torch.Generator().manual_seed(seed + 1)) + 0.5, rnd((B, cin), seed + 2, 0.1)
-    x, w, b = rnd((B, H, W, cin), seed + 3), rnd((cout, cin, 3, 3), seed + 4, (2.0 / (9 * cin)) ** 0.5), rnd((cout,), seed + 5, 0.1)
+    x, w, b = rnd((B, H, W, cin), seed + 3), rnd((cout, cin, k, k), seed + 4, (2.0 / (k * k * cin)) ** 0.5), rnd((cout,), seed + 5, 0.1)
     res, ss = rnd((B, Ho, Wo, cout), seed + 6), rnd((B, Ho, Wo, cout), seed + 7, 0.3)
     if name == 'int_coded':
         i = torch.arange(B * H * W * cin).view(B, H, W, cin)
         x = ((i * 7 + (i // cin) * 3 + (i % 251)) % 7 - 3).float()
-        j = torch.arange(cout * cin * 9).view(cout, cin, 3, 3)
-        w = ((j * 5 + (j // 9) * 11 + (j % 241)) % 7 - 3).float() * 2.0 ** -5
+        j = torch.arange(cout * cin * k * k).view(cout, cin, k, k)
+        w = ((j * 5 + (j // (k * k)) * 11 + (j % 241)) % 7 - 3).float() * 2.0 ** -5
         b = (torch.arange(cout) % 9 - 4).float()
         o = torch.arange(B * Ho * Wo * cout).view(B, Ho, Wo, cout)
         res, ss = ((o * 3 + o // cout) % 11 - 5).float(), ((o * 5 + o // cout) % 5 - 2).float()
@@ -252,11 +252,11 @@ def family(name, key, variant=0):
     elif name == 'onehot_pixels':
         x = torch.zeros(B, H, W, cin)
         for bi in range(B):
-            for c, (r, q) in enumerate(onehot_positions(H, W, cin)):
+            for c, (r, q) in enumerate(onehot_positions(H, W, cin) if positions is None else positions(bi)):
                 x[bi, r, q, (c + 5 * bi) % cin] = 1.0
         pro = PRO_NONE
     elif name == 'tap_shift':
-        w, b, pro = tap_weight(cin, cout, variant), torch.zeros(cout), PRO_NONE
+        w, b, pro = tap_weight(cin, cout, variant, k), torch.zeros(cout), PRO_NONE
     elif name == 'mixed_cout':
         e = torch.round(torch.arange(cout).float() * (MIXED_SPAN / (cout - 1)))
         w = w * torch.pow(2.0, -e)[:, None, None, None]
@@ -271,12 +271,12 @@ def family(name, key, variant=0):
         half = cin // 2
         x = rnd((B, H, W, half), seed + 8).repeat_interleave(2, dim=3)
         sc, sh = sc[:, :half].repeat_interleave(2, dim=1), sh[:, :half].repeat_interleave(2, dim=1)
-        w0 = rnd((cout, half, 3, 3), seed + 9, (2.0 / (9 * cin)) ** 0.5) * (1.0 + (torch.arange(half) % 16).float())[None, :, None, None]
-        delta = rnd((cout, half, 3, 3), seed + 10, (2.0 / (9 * cin)) ** 0.5 * 2.0 ** -9) * (1.0 + (torch.arange(half) % 16).float())[None, :, None, None]
-        w = torch.stack((w0, -(w0 + delta)), dim=2).reshape(cout, cin, 3, 3)
+        w0 = rnd((cout, half, k, k), seed + 9, (2.0 / (k * k * cin)) ** 0.5) * (1.0 + (torch.arange(half) % 16).float())[None, :, None, None]
+        delta = rnd((cout, half, k, k), seed + 10, (2.0 / (k * k * cin)) ** 0.5 * 2.0 ** -9) * (1.0 + (torch.arange(half) % 16).float())[None, :, None, None]
+        w = torch.stack((w0, -(w0 + delta)), dim=2).reshape(cout, cin, k, k)
     elif name == 'dc_plus_ripple':
         x = 256.0 + x
-        w = w - w.mean(dim=(2, 3), keepdim=True)
+        w = w - w.mean(dim=(2, 3) if k > 1 else 1, keepdim=True)                # (a 1x1's "taps" are its input channels)
         pro, epi = PRO_NONE, EPI_RESIDUAL
     elif name in ('swish_leaky_edges', 'swish_leaky_edges_sft'):
         i = torch.arange(B * H * W * cin).view(B, H, W, cin)
@@ -286,9 +286,17 @@ def family(name, key, variant=0):
         pro, epi = (PRO_AFFINE_SWISH, EPI_RESIDUAL) if name == 'swish_leaky_edges' else (PRO_LEAKY, EPI_SFT)
     else:
         raise KeyError(name)
-    if up:
+    if up and bare_up:
         pro, epi = PRO_NONE, EPI_NONE
     return dict(x=x.contiguous(), w=w.contiguous(), b=b, sc=sc.contiguous(), sh=sh.contiguous(), res=res, ss=ss, pro=pro, epi=epi, sft_w=sft_w, up=up, key=key)
+
+
+@functools.lru_cache(maxsize=None)
+def family(name, key, variant=0):
+    """-> dict(x, w, b, sc, sh, res, ss, pro, epi, sft_w, acted): float32 CPU tensors.  Upsampling shapes take prologue none and no epilogue operand
+    (the only form w43_up has).  variant: int_coded's (prologue, epilogue) pair; tap_shift's tap."""
+    B, H, W, cin, cout, cs, up = SHAPES[key]
+    return family_at(name, (B, H, W, cin, cout, up), 1000 + 17 * sorted(SHAPES).index(key), variant, key=key)
 
 
 # ---- fp64 reference and gate -----------------------------------------------------------------------------------------------------------------
