@@ -365,7 +365,11 @@ int cf_attention(const float* q, int ldq, const float* k, int ldk, const float* 
                  int batch, int heads, int head_dim, int nkeys, float scale, cf_stream_t stream);
 
 /* ---- code prediction (codeformer_arch.py:257-258 softmax+topk(1)) ------------------------------
- * argmax over each fp32 row, lowest index wins ties; idx is int64 like the reference's top_idx. */
+ * argmax over each fp32 row, lowest index wins ties; idx is int64 like the reference's top_idx.  n % 4 == 0, any n >= 4 and any row count.
+ * NaN: the comparisons skip a NaN element, so idx is the lowest index of the largest NON-NaN element (numpy.argmax would name the NaN).  A row
+ * without a single comparable element -- every element NaN -- has no such index and gets 0x7fffffff, which is out of range for every caller:
+ * cf_codebook_gather_adain clamps it to the last code, cf_label_lut_f32 maps it to entry 0.  Nothing reads memory through it; a row of -inf
+ * only ties at index 0.  (tests/test_gpu_misc_kernels.py pins all of this for both entry points.) */
 int cf_argmax_rows(const float* logits, int rows, int n, int64_t* idx, cf_stream_t stream);
 /* The same argmax plus the top-2 logit gap (the logit guard of CodeFormer.forward; entry point added, ABI version unchanged):
  * idx[row]  bitwise cf_argmax_rows';
@@ -403,7 +407,9 @@ int cf_pixel_unshuffle_nhwc(const float* x, int batch, int c, int h, int w, int 
 
 /* ---- tensor boundary (basicsr/utils/img_util.py:9-35 img2tensor + normalize, :38-94 tensor2img) ---
  * u8 HWC BGR [batch][h][w][3] -> fp32 NCHW RGB in [-1,1] ((x/255 - 0.5)/0.5), and back
- * (clamp[-1,1], (x+1)/2*255, round-half-even, RGB->BGR). */
+ * (clamp[-1,1], (x+1)/2*255, round-half-even, RGB->BGR).  +-inf clamp to bytes 255 / 0.  A NaN gives byte 0 (fmaxf(NaN, -1) is -1): the
+ * reference's tensor2img has no defined answer there (a NaN -> uint8 cast), this one is pinned by tests/test_gpu_misc_kernels.py.
+ * Images with h * w % 4 == 0 are converted four pixels per thread through aligned 4-byte words, every other size pixel by pixel. */
 int cf_img_u8_to_tensor(const uint8_t* img, int batch, int h, int w, float* out, cf_stream_t stream);
 int cf_tensor_to_img_u8(const float* t, int batch, int h, int w, uint8_t* img, cf_stream_t stream);
 /* inpainting composite (inference_inpainting.py:68-74): x, y, out are [batch][3][h][w]; mask = (x0+x1+x2 == 3);
