@@ -17,7 +17,9 @@ import os
 import threading
 
 import math
+import numbers
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -39,6 +41,94 @@ _CAPTURE_STREAMS = {}    # device -> the stream every graph of this process is c
 def _min_nan(a, b):
     """min of two floats that keeps a NaN once it has one (Python's min() does not)."""
     return b if (b < a or b != b) else a
+
+
+class FaceWeights:
+    """One fidelity weight per face of a batch, read on the host: `host` the B values as the float32 numbers the kernels see, `fused` the
+    faces whose weight is > 0 (a NaN is not: the rule `if w > 0` of the scalar call).  With a CUDA `device`: `dev` the float32 (B,) tensor
+    the SFT epilogues index by image, and -- for a mixed batch -- `sel_f` / `sel_u`, the int64 row indices of the fused and un-fused faces."""
+
+    def __init__(self, values, device=None):
+        values = [float(v) for v in values]
+        self.host = tuple(float(np.float32(v)) for v in values)
+        self.fused = tuple(v > 0 for v in values)
+        self.device = None if device is None else torch.device(device)
+        self.dev = self.sel_f = self.sel_u = None
+        if self.device is not None and self.device.type == 'cuda':
+            self.dev = torch.tensor(self.host, dtype=torch.float32).to(self.device)
+            if self.mixed:
+                self.sel_f = torch.tensor(self.rows_fused, dtype=torch.int64).to(self.device)
+                self.sel_u = torch.tensor(self.rows_unfused, dtype=torch.int64).to(self.device)
+
+    def __len__(self):
+        return len(self.host)
+
+    @property
+    def rows_fused(self):
+        return [i for i, f in enumerate(self.fused) if f]
+
+    @property
+    def rows_unfused(self):
+        return [i for i, f in enumerate(self.fused) if not f]
+
+    @property
+    def all_fused(self):
+        return all(self.fused)
+
+    @property
+    def none_fused(self):
+        return not any(self.fused)
+
+    @property
+    def mixed(self):
+        return not self.all_fused and not self.none_fused
+
+    def rows(self, idx):
+        """The weights of faces `idx` (a list of ints), as a batch of their own."""
+        return FaceWeights([self.host[i] for i in idx], self.device)
+
+
+def is_scalar_weight(w):
+    """Whether face_weights() leaves w as it is: the scalar call."""
+    return isinstance(w, (numbers.Real, np.number, np.bool_)) or ((torch.is_tensor(w) or isinstance(w, np.ndarray)) and w.ndim == 0)
+
+
+def face_weights(w, batch, device=None):
+    """Normalise the `w` of a call on `batch` faces.  A number (Python / numpy scalar, 0-dim array or tensor) is returned as it is: the
+    scalar call.  A sequence, numpy array or tensor of `batch` real values becomes a FaceWeights; the values are read on the host, so a
+    device tensor costs one synchronisation.  Another length raises ValueError, anything that is not real numbers TypeError."""
+    if isinstance(w, FaceWeights):
+        if len(w) != batch:
+            raise ValueError(f'w holds {len(w)} weights for a batch of {batch} faces')
+        return w
+    if isinstance(w, (numbers.Real, np.number, np.bool_)):      # (what `w > 0` and float(w) take today; np.str_ and the like are no numbers)
+        return w
+    if torch.is_tensor(w):
+        if w.dim() == 0:
+            return w
+        if w.dtype == torch.bool or w.is_complex():
+            raise TypeError(f'w: expected real weights, got a {w.dtype} tensor')
+        if w.dim() != 1 or w.numel() != batch:
+            raise ValueError(f'w: expected one weight per face ({batch}), got a tensor of shape {tuple(w.shape)}')
+        vals = w.detach().to('cpu', torch.float64).tolist()      # (a device tensor: the one synchronisation)
+    elif isinstance(w, np.ndarray):
+        if w.ndim == 0:
+            return w.item()
+        if w.dtype.kind not in 'fiu':
+            raise TypeError(f'w: expected real weights, got a numpy array of {w.dtype}')
+        if w.ndim != 1 or w.shape[0] != batch:
+            raise ValueError(f'w: expected one weight per face ({batch}), got an array of shape {w.shape}')
+        vals = w.astype(np.float64).tolist()
+    elif isinstance(w, (list, tuple)):
+        if len(w) != batch:
+            raise ValueError(f'w: expected one weight per face ({batch}), got {len(w)} values')
+        for v in w:
+            if isinstance(v, (bool, np.bool_)) or not (isinstance(v, (numbers.Real, np.number)) or (torch.is_tensor(v) and v.dim() == 0 and v.dtype != torch.bool)):
+                raise TypeError(f'w: expected real weights, got {type(v).__name__} in the sequence')
+        vals = [float(v) for v in w]
+    else:
+        raise TypeError(f'w: expected a number or one weight per face (sequence, numpy array, tensor), got {type(w).__name__}')
+    return FaceWeights(vals, device)
 
 
 def calc_mean_std(feat, eps=1e-5):
@@ -215,14 +305,21 @@ class Fuse_sft_block(HipModule):
             h = ops.conv2d(e, pws[2], act=act_e, emit_stats=rs[3])
             act_s, act_h = (ops.act_scale(s0) if rs[1] else None), (ops.act_scale(h) if rs[3] else None)
         s = ops.conv2d(s0, pws[1], prologue=PRO_LEAKY, act=act_s)
-        return ops.conv2d(h, pws[3], prologue=PRO_LEAKY, epilogue=EPI_SFT, res=dec, sft_scale=s, sft_w=float(w), emit_stats=True, act=act_h)
+        # w: a number, or a float32 (B,) tensor on the device -- one weight per face, indexed by image in the epilogue (cf_conv2d_sft_w)
+        per_face = torch.is_tensor(w) and w.dim() == 1
+        return ops.conv2d(h, pws[3], prologue=PRO_LEAKY, epilogue=EPI_SFT, res=dec, sft_scale=s, sft_w=w if per_face else float(w), emit_stats=True, act=act_h)
 
     def forward(self, enc_feat, dec_feat, w=1):
+        """w: a number, or a tensor of B values -- one weight per face (GPU: float32 on the inputs' device)."""
+        if torch.is_tensor(w) and w.dim() == 1 and w.shape[0] != dec_feat.shape[0]:
+            raise ValueError(f'w: expected one weight per face ({dec_feat.shape[0]}), got {w.shape[0]}')
         if enc_feat.is_cuda:
             with torch.no_grad():
                 out = self.forward_nhwc(ops.to_nhwc(enc_feat.float()), ops.to_nhwc(dec_feat.float()), w)
                 return ops.to_nchw(out)
         enc = self.encode_enc(torch.cat([enc_feat, dec_feat], dim=1))
+        if torch.is_tensor(w) and w.dim() == 1:
+            w = w.to(dec_feat.dtype).view(-1, 1, 1, 1)
         return dec_feat + w * (dec_feat * self.scale(enc) + self.shift(enc))
 
 
@@ -318,9 +415,12 @@ class CodeFormer(VQAutoEncoder):
         # and storage addresses, ~70 us per call): a versioned in-place update, load_state_dict, .to() or invalidate_packed_weights() all
         # re-capture; only an un-versioned `.data` edit needs the explicit invalidate_packed_weights() the packed-weight cache needs too.
         # '1': every batch size; '0': never.  At most four captured graphs are kept (each pins the activations of its shape).
+        # A scalar w is part of the key (each value its own graph); one weight per face is a static device buffer of the graph and the key
+        # holds only which faces are fused, so every all-positive vector of a batch size replays one graph.  `graph_captures` counts captures.
         self.use_hip_graphs = {'0': False, '1': True}.get(os.environ.get('CODEFORMER_HIP_GRAPHS', 'auto'), 'auto')
         self.graph_max_batch = 4
         self._graphs = {}
+        self.graph_captures = 0
         self.connect_list = connect_list
         self.n_layers = n_layers
         self.n_head = n_head
@@ -345,12 +445,13 @@ class CodeFormer(VQAutoEncoder):
             self.fuse_convs_dict[f_size] = Fuse_sft_block(ch, ch)
 
     # ------------------------------------------------------------------ GPU (HIP) path
-    def _forward_hip(self, x, w, code_only, adain, f43_encoder=None, guard=False, u8=False, out_u8=None):
-        """f43_encoder: the encoder's F(4x4,3x3) choice of THIS call (None: self.winograd_f43_encoder; the logit guard's second pass
+    def _encode_hip(self, x, code_only, adain, f43_encoder=None, guard=False, u8=False):
+        """Everything of the forward that does not depend on w: encoder, Transformer, code argmax, codebook gather (+ AdaIN).  Returns a
+        dict: logits, lq_feat, idx (B, T), quant (B,16,16,256; None with code_only), enc_feat (the encoder taps by size).
+        f43_encoder: the encoder's F(4x4,3x3) choice of THIS call (None: self.winograd_f43_encoder; the logit guard's second pass
         hands False down instead of flipping the attribute -- two threads may share a network).  guard: take the argmax on
         cf_argmax_rows_gap and leave the per-face minimum top-2 gap in `last_min_gap` (with code_only too).
-        u8 (restore_u8, which checked the tensors): x is the uint8 (B,512,512,3) BGR batch, read by the first conv, and the first returned
-        tensor is the uint8 (B,512,512,3) image the last conv wrote -- into out_u8 when given."""
+        u8 (restore_u8, which checked the tensors): x is the uint8 (B,512,512,3) BGR batch, read by the first conv."""
         if u8:
             B = x.shape[0]
         else:
@@ -380,28 +481,33 @@ class CodeFormer(VQAutoEncoder):
             X = layer.forward_tokens(X, self.position_emb, B, code=gcode, code_ln=gcode_ln)
         ln, head = self.idx_pred_layer[0], self.idx_pred_layer[1]
         logits2d = ops.linear(ops.layernorm(X, ln.weight, ln.bias, ln.eps), self._pw_conv(head, bf16=ln_code(self, ln, gcode_ln)))
-        logits = logits2d.view(B, T, -1)
-        lq_feat = ops.to_nchw(lq)
+        res = {'logits': logits2d.view(B, T, -1), 'lq_feat': ops.to_nchw(lq), 'idx': None, 'quant': None, 'enc_feat': enc_feat}
         if guard:
             idx, _, self.last_min_gap = ops.argmax_rows_gap(logits2d, T)   # the same indices + each face's smallest top-2 logit gap
-            if code_only:
-                self.last_indices = idx.view(B, T)
+            res['idx'] = idx.view(B, T)
         if code_only:
-            return logits, lq_feat
+            return res
 
         if not guard:
             idx = ops.argmax_rows(logits2d)                                 # == topk(softmax(logits), 1)
+            res['idx'] = idx.view(B, T)
         quant = ops.codebook_gather(idx, self.quantize.embedding.weight, B, T,
                                     lq=tokens.view(B, T, -1) if adain else None)
-        quant = quant.view(B, lq.shape[1], lq.shape[2], -1)
-
+        res['quant'] = quant.view(B, lq.shape[1], lq.shape[2], -1)
         if self.precision not in ('fp32', 'f16x2', 'bf16', 'fp16'):
             raise ValueError(f"precision must be 'fp32', 'f16x2', 'bf16' or 'fp16', got {self.precision!r}")
+        return res
+
+    def _generate_hip(self, quant, enc_feat, w, u8=False, out_u8=None):
+        """The generator on `quant` (B,16,16,256) with the fusion blocks reading `enc_feat`.  w: a number (a 0-dim tensor included) -- fused iff w > 0 -- or a float32
+        (B,) device tensor, one weight per face, all of them fused.  u8: the last conv writes the uint8 (B,512,512,3) image (into out_u8
+        when given), which is returned in place of the NCHW tensor."""
+        B = quant.shape[0]
         # operand code of the generator + CFT 3x3 convs; 'fp32': F(4x4,3x3) on fp32 operands (four v_mfma_f32_16x16x4_f32 per 16 channels
-        # instead of three f16 MFMAs); 'f16x2': the encoder gets SPLIT_F43 through winograd_f43_encoder only, above
+        # instead of three f16 MFMAs); 'f16x2': the encoder gets SPLIT_F43 through winograd_f43_encoder only (_encode_hip)
         bf16 = {'fp32': ops.WINOGRAD_F43, 'f16x2': ops.SPLIT_F43, 'bf16': 1, 'fp16': 2}[self.precision]
         gen_taps = None
-        if w > 0:
+        if (torch.is_tensor(w) and w.dim() == 1) or w > 0:      # (a 0-dim tensor is a number: `w > 0` decides, as ever)
             def fuse(t):
                 f = str(t.shape[2])
                 enc = enc_feat[f]
@@ -410,14 +516,43 @@ class CodeFormer(VQAutoEncoder):
                 return self.fuse_convs_dict[f].forward_nhwc(enc, t, w, bf16=bf16)
             gen_taps = {self.fuse_generator_block[f]: fuse for f in self.connect_list}
         if u8 and out_u8 is None:
-            out_u8 = torch.empty((B, 512, 512, 3), dtype=torch.uint8, device=x.device)
-        out = self.generator.forward_nhwc(quant, gen_taps, bf16=bf16, storage_bf16=bool(self.bf16_storage) and bf16 == 1,
-                                          img_out=out_u8 if u8 else None)      # (B,3,512,512) NCHW, or the uint8 (B,512,512,3) image
-        self.last_indices = idx.view(B, T)
-        return out, logits, lq_feat
+            out_u8 = torch.empty((B, 512, 512, 3), dtype=torch.uint8, device=quant.device)
+        return self.generator.forward_nhwc(quant, gen_taps, bf16=bf16, storage_bf16=bool(self.bf16_storage) and bf16 == 1,
+                                           img_out=out_u8 if u8 else None)      # (B,3,512,512) NCHW, or the uint8 (B,512,512,3) image
+
+    def _generate_rows_hip(self, e, w, u8=False, out_u8=None):
+        """The generator for the faces of _encode_hip's result `e` under w, a number or a FaceWeights.  A mixed FaceWeights runs it twice --
+        the fused faces with their weights, the others un-fused, each selected with ops.select_rows from quant and the encoder taps --
+        and scatters the rows back into place; the forward is bitwise batch-invariant, so every row is bitwise its own scalar call."""
+        quant, enc_feat = e['quant'], e['enc_feat']
+        if not isinstance(w, FaceWeights):
+            return self._generate_hip(quant, enc_feat, w, u8, out_u8)
+        if w.none_fused:
+            return self._generate_hip(quant, enc_feat, 0.0, u8, out_u8)
+        if w.all_fused:
+            return self._generate_hip(quant, enc_feat, w.dev, u8, out_u8)
+        B = quant.shape[0]
+        out = out_u8 if out_u8 is not None else torch.empty((B, 512, 512, 3) if u8 else (B, 3, 512, 512), dtype=torch.uint8 if u8 else torch.float32, device=quant.device)
+        taps = {f: ops.select_rows(t, w.sel_f) for f, t in enc_feat.items()}
+        out.index_copy_(0, w.sel_f, self._generate_hip(ops.select_rows(quant, w.sel_f), taps, w.dev.index_select(0, w.sel_f), u8))
+        out.index_copy_(0, w.sel_u, self._generate_hip(ops.select_rows(quant, w.sel_u), None, 0.0, u8))
+        return out
+
+    def _forward_hip(self, x, w, code_only, adain, f43_encoder=None, guard=False, u8=False, out_u8=None):
+        """w: a number or a FaceWeights (one weight per face).  f43_encoder / guard / u8: see _encode_hip; with u8 the first returned
+        tensor is the uint8 (B,512,512,3) image the last conv wrote -- into out_u8 when given."""
+        e = self._encode_hip(x, code_only, adain, f43_encoder, guard, u8)
+        if code_only:
+            if guard:
+                self.last_indices = e['idx']
+            return e['logits'], e['lq_feat']
+        out = self._generate_rows_hip(e, w, u8, out_u8)
+        self.last_indices = e['idx']
+        return out, e['logits'], e['lq_feat']
 
     # ------------------------------------------------------------------ host (CPU tensors) path
-    def _forward_host(self, x, w, detach_16, code_only, adain):
+    def _encode_host(self, x, detach_16, code_only, adain):
+        """The part of the host forward that does not depend on w -> (logits, lq_feat, quant or None, enc_feat)."""
         enc_feat = {}
         out_list = [self.fuse_encoder_block[f] for f in self.connect_list]
         for i, block in enumerate(self.encoder.blocks):
@@ -434,29 +569,59 @@ class CodeFormer(VQAutoEncoder):
             self.last_min_gap = top2_gap(logits)[0].min(dim=1).values
             self._guard_count(self.last_min_gap)
         if code_only:
-            return logits, lq_feat
+            return logits, lq_feat, None, enc_feat
         _, top_idx = torch.topk(F.softmax(logits, dim=2), 1, dim=2)
         quant = self.quantize.get_codebook_feat(top_idx, shape=[x.shape[0], 16, 16, 256])
         if detach_16:
             quant = quant.detach()
         if adain:
             quant = adaptive_instance_normalization(quant, lq_feat)
-        x = quant
+        return logits, lq_feat, quant, enc_feat
+
+    def _generate_host(self, x, enc_feat, w):
+        """The generator on the host; w: a number (fused iff w > 0) or a (B,) tensor of positive weights, one per face."""
+        fused = (torch.is_tensor(w) and w.dim() == 1) or w > 0      # (a 0-dim tensor is a number: `w > 0` decides, as ever)
         fuse_list = [self.fuse_generator_block[f] for f in self.connect_list]
         for i, block in enumerate(self.generator.blocks):
             x = block(x)
-            if i in fuse_list and w > 0:
+            if i in fuse_list and fused:
                 f = str(x.shape[-1])
                 x = self.fuse_convs_dict[f](enc_feat[f].detach(), x, w)
-        return x, logits, lq_feat
+        return x
+
+    def _generate_rows_host(self, quant, enc_feat, w):
+        """_generate_rows_hip on the host: a FaceWeights partitions the rows the same way."""
+        if not isinstance(w, FaceWeights):
+            return self._generate_host(quant, enc_feat, w)
+        if w.none_fused:
+            return self._generate_host(quant, enc_feat, 0.0)
+        wt = torch.tensor(w.host, dtype=torch.float32)
+        if w.all_fused:
+            return self._generate_host(quant, enc_feat, wt)
+        rf, ru = w.rows_fused, w.rows_unfused
+        of = self._generate_host(quant[rf], {f: t[rf] for f, t in enc_feat.items()}, wt[rf])
+        ou = self._generate_host(quant[ru], None, 0.0)
+        out = of.new_empty((quant.shape[0],) + tuple(of.shape[1:]))
+        out[rf] = of
+        out[ru] = ou
+        return out
+
+    def _forward_host(self, x, w, detach_16, code_only, adain):
+        logits, lq_feat, quant, enc_feat = self._encode_host(x, detach_16, code_only, adain)
+        if code_only:
+            return logits, lq_feat
+        return self._generate_rows_host(quant, enc_feat, w), logits, lq_feat
 
     def _forward_graphed(self, x, w, code_only, adain, guard=False, u8=False, out_u8=None):
         """Capture-once / replay-many execution of _forward_hip on the current stream.  Outputs are copies, so callers may
         keep them across calls.  A graph is re-captured when any packed weight was rebuilt since its capture.
         u8: the uint8 form of _forward_hip -- the static input is the uint8 batch, the boundary form is part of the key, and the image
-        is copied into out_u8 when given."""
+        is copied into out_u8 when given.
+        w: a number -- part of the key, as ever -- or a FaceWeights: the key then holds which faces are fused, not the values; the weights
+        are a static device buffer of the graph (the FaceWeights of the capturing call), copied into before each replay."""
         with _GRAPH_LOCK:   # static buffers per shape: two threads replaying one graph would race on them
-            key = (tuple(x.shape), float(w), bool(code_only), bool(adain), self.precision, bool(self.bf16_storage), self.encoder_precision, self.gemm_precision, bool(self.winograd_f43_encoder), str(x.device), ops.switches(), bool(guard), bool(u8))
+            per_face = isinstance(w, FaceWeights)
+            key = (tuple(x.shape), ('per-face', w.fused) if per_face else float(w), bool(code_only), bool(adain), self.precision, bool(self.bf16_storage), self.encoder_precision, self.gemm_precision, bool(self.winograd_f43_encoder), str(x.device), ops.switches(), bool(guard), bool(u8))
             ent = self._graphs.get(key)
             sig = self._param_signature()
             if ent is None or ent['epoch'] != PACK_EPOCH[0] or ent['sig'] != sig:
@@ -485,12 +650,15 @@ class CodeFormer(VQAutoEncoder):
                     if gc_on:
                         gc.enable()
                 ent = {'graph': graph, 'x': static_x, 'outs': outs, 'epoch': PACK_EPOCH[0], 'sig': sig, 'idx': getattr(self, 'last_indices', None),
-                       'gap': self.last_min_gap if guard else None}
+                       'gap': self.last_min_gap if guard else None, 'w': w if per_face else None}
+                self.graph_captures += 1
                 self._graphs.pop(key, None)
                 while len(self._graphs) >= 4:           # oldest first: a graph pins the activations of its shape
                     self._graphs.pop(next(iter(self._graphs)))
                 self._graphs[key] = ent
             ent['x'].copy_(x)
+            if per_face and ent['w'] is not w:
+                ent['w'].dev.copy_(w.dev)
             ent['graph'].replay()
             if ent['idx'] is not None:
                 self.last_indices = ent['idx'].clone()   # (a fresh tensor per call, as the eager path returns: the next replay overwrites the graph's own)
@@ -588,38 +756,60 @@ class CodeFormer(VQAutoEncoder):
             st['min_gap'] = _min_nan(st['min_gap'], float(gmin))
             pend.clear()
 
-    def _forward_guarded(self, x, w, code_only, adain, graphed, u8=False, out_u8=None):
-        guard = self.logit_guard
-        outs = (self._forward_graphed if graphed else self._forward_hip)(x, w, code_only, adain, guard=True, u8=u8, out_u8=out_u8)
+    def _guard_first_pass(self, faces):
+        """The bookkeeping behind a first pass that ran with guard=True on `faces` faces (forward, restore_u8, restore_sweep) -> (flag, gmin):
+        gmin that pass's last_min_gap; flag the host mask of the faces to run again, or None when nothing is ('report': the minima are
+        queued, no read-back; 'rerun': the one read-back of the call -- no face flagged, or an F(2x2,3x3) encoder, which has nothing to
+        fall back to: faces are counted only)."""
         gmin = self.last_min_gap
-        if guard == 'report':
+        if self.logit_guard == 'report':
             st = self._guard_totals
             st['calls'] += 1
-            st['faces'] += int(x.shape[0])
+            st['faces'] += int(faces)
             self._guard_pending.append((gmin, float(self.logit_guard_gap), None))
             if len(self._guard_pending) >= 64:
                 self._guard_fold(sync=False)
-            return outs
-        flag = self._guard_count(gmin.cpu())            # the one read-back of the call
+            return None, gmin
+        flag = self._guard_count(gmin.cpu())
         if not bool(flag.any()) or not self.winograd_f43_encoder:
-            return outs                                 # (an F(2x2,3x3) encoder has nothing to fall back to: faces are counted only)
+            return None, gmin
+        return flag, gmin
+
+    def _guard_second_pass(self, sel, gmin, idx, idx2):
+        """... and behind the second pass on the faces `sel`: the totals, and the flagged rows of last_min_gap (gmin: the first pass's,
+        self.last_min_gap: the second's).  idx / idx2: the code indices of all faces in the first pass / of the flagged ones in the second."""
+        st = self._guard_totals
+        st['rerun_faces'] += int(sel.numel())
+        st['index_changes'] += int((idx.index_select(0, sel) != idx2).sum())
+        self.last_min_gap = gmin.index_copy_(0, sel, self.last_min_gap)
+
+    def _forward_guarded(self, x, w, code_only, adain, graphed, u8=False, out_u8=None):
+        outs = (self._forward_graphed if graphed else self._forward_hip)(x, w, code_only, adain, guard=True, u8=u8, out_u8=out_u8)
+        flag, gmin = self._guard_first_pass(x.shape[0])
+        if flag is None:
+            return outs
         sel = flag.nonzero().flatten().to(x.device)
         idx = self.last_indices
         # second pass: the flagged faces as one batch, eagerly (it neither captures a graph nor evicts one)
-        outs2 = self._forward_hip(x.index_select(0, sel), w, code_only, adain, f43_encoder=False, guard=True, u8=u8)
-        st = self._guard_totals
-        st['rerun_faces'] += int(sel.numel())
-        st['index_changes'] += int((idx.index_select(0, sel) != self.last_indices).sum())
+        w2 = w.rows(flag.nonzero().flatten().tolist()) if isinstance(w, FaceWeights) else w    # (the flagged faces keep their own weights)
+        outs2 = self._forward_hip(x.index_select(0, sel), w2, code_only, adain, f43_encoder=False, guard=True, u8=u8)
+        self._guard_second_pass(sel, gmin, idx, self.last_indices)
         for o, o2 in zip(outs, outs2):
             o.index_copy_(0, sel, o2)
         self.last_indices = idx.index_copy_(0, sel, self.last_indices)
-        self.last_min_gap = gmin.index_copy_(0, sel, self.last_min_gap)
         return outs
 
     def _forward_cuda(self, x, w, code_only, adain, **u8):
         """The dispatch forward and restore_u8 share: graph replay by the use_hip_graphs / graph_max_batch rule, the logit guard, else eager."""
         ops.L.ensure_device(x.device)   # kernel attributes on the tensor's device, before (never inside) a capture
         with torch.no_grad(), torch.cuda.device(x.device):
+            if torch.cuda.is_current_stream_capturing() and not is_scalar_weight(w):
+                raise RuntimeError('w: one weight per face is read on the host and uploaded on every call, which a stream capture of the '
+                                   "caller's does not allow; inside your own capture pass a number (or capture per fused pattern yourself "
+                                   'around Fuse_sft_block / ops.conv2d with a device tensor)')
+            w = face_weights(w, x.shape[0], x.device)
+            if isinstance(w, FaceWeights) and w.none_fused:
+                w = 0.0      # no face is fused: the scalar call's un-fused path, and its graph
             graphed = self.use_hip_graphs is True or (self.use_hip_graphs == 'auto' and x.shape[0] <= self.graph_max_batch)
             graphed = graphed and ops.PROFILE is None and not torch.cuda.is_current_stream_capturing()
             if self.logit_guard != 'off':
@@ -629,17 +819,98 @@ class CodeFormer(VQAutoEncoder):
             return self._forward_hip(x, w, code_only, adain, **u8)
 
     def forward(self, x, w=0, detach_16=True, code_only=False, adain=False):
+        """w: the fidelity weight -- a number for the whole batch, or one weight per face (a sequence, numpy array or tensor of B values;
+        they are read on the host and uploaded on every call: a device tensor costs one synchronisation, and neither form can be used while
+        the caller is capturing a stream of their own -- a number can, as ever).  Face b is fused iff w_b > 0 (a NaN is not).  All fused:
+        one generator pass with the weights on the device; none: the un-fused pass; mixed: encoder, Transformer and code lookup once for
+        all faces, the generator once for the fused faces and once un-fused for the rest.  Every row is bitwise the one-face call with
+        its own scalar w; logits, lq_feat, last_indices and last_min_gap do not depend on w."""
         if self.logit_guard not in ('off', 'report', 'rerun'):
             raise ValueError(f"logit_guard must be 'off', 'report' or 'rerun', got {self.logit_guard!r}")
         if x.is_cuda:
             return self._forward_cuda(x, w, code_only, adain)
-        return self._forward_host(x, w, detach_16, code_only, adain)
+        return self._forward_host(x, face_weights(w, x.shape[0]), detach_16, code_only, adain)
+
+    def restore_sweep(self, x, ws, adain=False):
+        """One batch at several fidelity weights: x (B,3,512,512), ws K weights -> (outs (K,B,3,512,512), logits, lq_feat), with
+        outs[k, b] bitwise forward(x[b:b+1], w=ws[k], adain=adain)[0][0] on the GPU.  Encoder, Transformer, code argmax, gather and AdaIN run
+        once for the B faces; the positive weights are ONE generator pass over B x (their number) rows (quant and the encoder taps repeated
+        per weight, the weights per row on the device), all weights <= 0 (or NaN) share one un-fused pass.  Eager (no graph is captured or
+        replayed); logit_guard is honoured ('rerun': the flagged faces take the encoder again before any generator pass and go through the
+        generator as a batch of their own)."""
+        if self.logit_guard not in ('off', 'report', 'rerun'):
+            raise ValueError(f"logit_guard must be 'off', 'report' or 'rerun', got {self.logit_guard!r}")
+        ws = np.asarray(ws.detach().cpu() if torch.is_tensor(ws) else ws)
+        if ws.ndim != 1 or ws.shape[0] < 1:
+            raise ValueError(f'restore_sweep: ws must hold K >= 1 weights, got shape {ws.shape}')
+        wk = face_weights(ws, ws.shape[0])        # (K "faces": the same reading of the values and of what is fused)
+        B, K = x.shape[0], len(wk)
+        pos, neg = wk.rows_fused, wk.rows_unfused
+        with torch.no_grad():
+            if x.is_cuda:
+                ops.L.ensure_device(x.device)
+                with torch.cuda.device(x.device):
+                    e, groups = self._encode_guarded_hip(x, adain)
+                    outs = torch.empty((K, B, 3, 512, 512), dtype=torch.float32, device=x.device)
+                    pos_idx = torch.tensor(pos, dtype=torch.int64).to(x.device)
+                    for rows, quant, taps in groups:       # (one group -- all faces -- unless the logit guard re-ran some of them)
+                        n = quant.shape[0]
+                        rows = torch.arange(B, dtype=torch.int64).to(x.device) if rows is None else rows
+                        if pos:
+                            rep = torch.arange(n, dtype=torch.int64).repeat(len(pos)).to(x.device)
+                            wv = torch.tensor([wk.host[k] for k in pos for _ in range(n)], dtype=torch.float32).to(x.device)
+                            o = self._generate_hip(ops.select_rows(quant, rep), {f: ops.select_rows(t, rep) for f, t in taps.items()}, wv)
+                            outs[pos_idx[:, None], rows[None, :]] = o.view(len(pos), n, 3, 512, 512)
+                        if neg:
+                            o = self._generate_hip(quant, None, 0.0)
+                            for k in neg:
+                                outs[k].index_copy_(0, rows, o)
+                    self.last_indices = e['idx']
+                    return outs, e['logits'], e['lq_feat']
+            logits, lq_feat, quant, enc_feat = self._encode_host(x, True, False, adain)
+            outs = None
+            if pos:
+                rep = list(range(B)) * len(pos)
+                wv = torch.tensor([wk.host[k] for k in pos for _ in range(B)], dtype=torch.float32)
+                o = self._generate_host(quant[rep], {f: t[rep] for f, t in enc_feat.items()}, wv)
+                outs = o.new_empty((K, B) + tuple(o.shape[1:]))
+                outs[pos] = o.view((len(pos), B) + tuple(o.shape[1:]))
+            if neg:
+                o = self._generate_host(quant, None, 0.0)
+                outs = o.new_empty((K, B) + tuple(o.shape[1:])) if outs is None else outs
+                for k in neg:
+                    outs[k] = o
+            return outs, logits, lq_feat
+
+    def _encode_guarded_hip(self, x, adain):
+        """_encode_hip under the logit guard, for restore_sweep -> (e, groups): e with the logits, lq_feat and indices of all faces, and
+        groups = [(rows or None, quant, encoder taps)], what the generator reads, per group of faces.  One group (rows None: all faces)
+        unless 'rerun' flagged some: those ran again, as a batch of their own, with the encoder on F(2x2,3x3) -- their rows of logits, lq_feat,
+        indices and last_min_gap are replaced, and they form the second group (the taps of the two encoders carry statistics partials of
+        different kernels: they are not merged).  'report' queues the minima as a forward does."""
+        e = self._encode_hip(x, False, adain, guard=self.logit_guard != 'off')
+        one = [(None, e['quant'], e['enc_feat'])]
+        if self.logit_guard == 'off':
+            return e, one
+        flag, gmin = self._guard_first_pass(x.shape[0])
+        if flag is None:
+            return e, one
+        sel, keep = flag.nonzero().flatten().to(x.device), (~flag).nonzero().flatten().to(x.device)
+        e2 = self._encode_hip(x.index_select(0, sel), False, adain, f43_encoder=False, guard=True)
+        self._guard_second_pass(sel, gmin, e['idx'], e2['idx'])
+        groups = [(sel, e2['quant'], e2['enc_feat'])]
+        if keep.numel():
+            groups.append((keep, ops.select_rows(e['quant'], keep), {f: ops.select_rows(t, keep) for f, t in e['enc_feat'].items()}))
+        for k in ('logits', 'lq_feat', 'idx'):
+            e[k].index_copy_(0, sel, e2[k])
+        return e, groups
 
     def restore_u8(self, faces, w=0.5, adain=True, out=None):
         """uint8 (B,512,512,3) BGR aligned faces -> the restored faces in the same form: the bytes of
         ops.tensor_to_img_u8(self(ops.img_u8_to_tensor(faces), w=w, adain=adain)[0]), with the conversions folded into the first and the
         last conv (cf_conv2d_u8) -- no fp32 image tensor exists at either end.  Dispatch (graph replay, logit guard: 'rerun' replaces the
         flagged faces' rows), `last_indices` and `last_min_gap` are those of forward.
+        w: a number or one weight per face, as in forward.
         out: a contiguous uint8 (B,512,512,3) destination on faces' device (e.g. a `[:m]` slice of a larger buffer); it is returned.
         CPU tensors take the host path with the converters of utils/img_util.py."""
         if self.logit_guard not in ('off', 'report', 'rerun'):
@@ -657,6 +928,6 @@ class CodeFormer(VQAutoEncoder):
         from ..utils.img_util import img2tensor, normalize_, tensor2img
         with torch.no_grad():
             x = torch.stack([normalize_(img2tensor(f / 255., bgr2rgb=True, float32=True), (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)) for f in faces.numpy()])
-            y = self._forward_host(x, w, True, False, adain)[0]
+            y = self._forward_host(x, face_weights(w, x.shape[0]), True, False, adain)[0]
             res = torch.stack([torch.from_numpy(tensor2img(y[i], rgb2bgr=True, min_max=(-1, 1))) for i in range(y.shape[0])])
         return res if out is None else out.copy_(res)

@@ -24,12 +24,13 @@
 #include "cf_common.h"
 
 // ---- launchers and geometry queries of the kernel families (conv_dispatch / splitk_geometry in cf_igemm.hip call them) --------------------
-int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);  // cf_winograd.hip: F(2,3), fp32 or split-half operands
+// sft_w_img (cf_conv2d_sft_w; the families with an SFT epilogue): [batch] device floats, image b's weight of CF_EPI_SFT in place of d->sft_w.
+int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img = nullptr);  // cf_winograd.hip: F(2,3), fp32 or split-half operands
 bool cf_wsplit_covers(const cf_conv_desc* d);                                         // cf_wsplit.hip: the eight-wave, 128-channel F(2,3) form,
-int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);   // called by cf_winograd_launch for what it covers
-int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);      // cf_wf43.hip: F(4,3)
+int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img = nullptr);   // called by cf_winograd_launch for what it covers
+int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img = nullptr);      // cf_wf43.hip: F(4,3)
 bool cf_wf43_k32(int cout, int cin);                                                  // cf_wf43.hip: F(4,3) / F(4,2) on 32-channel slabs? (cf_wf43_launch and the packers of cf_pack.hip)
-int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);     // cf_split.hip: direct, split-half operands
+int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img = nullptr);     // cf_split.hip: direct, split-half operands
 int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);  // cf_gemm_split.hip: split-half token GEMM
 int cf_gemm_f32_tile_try(const cf_conv_desc* d, hipStream_t stream);                  // cf_gemm_split.hip: fp32 token tiles (CF_OK: launched, 1: not its shape)
 // split-K geometry: output tiles of the launch and accumulator bytes one (tile, split) parks in the workspace
@@ -41,7 +42,7 @@ int cf_split_splitk_geometry(const cf_conv_desc* d, int* tiles, long* bytes_per_
 // launcher: K-slab count, image size fields, tiling, nparts, the stats_cpg default, acc_scale / act_scale, strides.  The structs keep
 // their own members, order and size (the kernarg size feeds register allocation; each has a static_assert on its sizeof).
 template <class A>
-inline void cf_fill_conv_args(A& a, const cf_conv_desc* d) {
+inline void cf_fill_conv_args(A& a, const cf_conv_desc* d, const float* sft_w_img = nullptr) {
   a.in0 = d->in0;
   a.in1 = d->in1;
   a.c0 = d->c0;
@@ -58,6 +59,7 @@ inline void cf_fill_conv_args(A& a, const cf_conv_desc* d) {
   a.res = d->res;
   a.sft_scale = d->sft_scale;
   a.sft_w = d->sft_w;
+  a.sft_w_img = sft_w_img;
   a.out = d->out;
   a.stats_out = d->stats_out;
 }
@@ -185,8 +187,12 @@ __device__ __forceinline__ f32x4 cf_epi_bias(f32x4 v, float s, f32x4 bias4) {
   for (int e = 0; e < 4; ++e) v[e] = SCALED ? v[e] * s + bias4[e] : v[e] + bias4[e];
   return v;
 }
-// RESIDUAL: v + r0.  SFT: r0 + w * (r0 * r1 + v).  (The vector epilogue of cf_igemm.hip -- edge-tile mask, GELU / LEAKY / AXPY of the
+// RESIDUAL: v + r0.  SFT: r0 + w * (r0 * r1 + v), w = cf_sft_weight of the image the quad belongs to.  (The vector epilogue of cf_igemm.hip -- edge-tile mask, GELU / LEAKY / AXPY of the
 // general instantiations -- keeps its own text: written with these helpers most of its instantiations compiled to other code.)
+// The SFT weight of image b: the descriptor's scalar, or -- cf_conv2d_sft_w -- entry b of the per-image table.  One expression for both
+// launches, so the arithmetic that follows (FMA contraction included) is the same instruction sequence; b is wave-uniform at every call
+// site (a patch or tile lies in one image), so this is one scalar load per patch, like act_scale.
+__device__ __forceinline__ float cf_sft_weight(const float* sft_w_img, float sft_w, int b) { return sft_w_img ? sft_w_img[b] : sft_w; }
 __device__ __forceinline__ f32x4 cf_epi_apply(f32x4 v, int epi, f32x4 r0, f32x4 r1, float w) {
   if (epi == CF_EPI_RESIDUAL) {
 #pragma unroll

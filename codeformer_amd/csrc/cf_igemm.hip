@@ -35,11 +35,12 @@ struct ConvArgs {
   const float* bias;
   const float* res;
   const float* sft_scale;
-  float sft_w;
+  const float* sft_w_img;  // SFT: [batch] weights, one per image (cf_conv2d_sft_w), or null: sft_w for all of them
   float* out;
   double* stats_out;  // optional [batch][cout/stats_cpg][nparts][2] partial (sum, sumsq) of the OUTPUT
   int stats_cpg, nparts;
   int tiles_x, tiles_per_img, ntn;
+  float sft_w;  // (behind ntn: the block keeps its size)
 };
 // The general (EXT) instantiations take a longer argument block; the CodeFormer kernels keep the exact ConvArgs layout
 // (the kernarg size feeds register allocation: growing it perturbed every instantiation's code).
@@ -165,6 +166,9 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
     m0 = mt * C::BM;
     b = m0 / (a.hout * a.wout);
   }
+  // SFT weight of the tile's image (a tile lies in one image), read before the kernel's first store so that it is a scalar load; the
+  // general instantiations have no SFT epilogue
+  [[maybe_unused]] const float sft_w = EXT ? 0.f : cf_sft_weight(a.sft_w_img, a.sft_w, b);
 
   // ---- gather geometry: item j of this thread is float4 #k4 of halo pixel p = (tid>>2) + 64*j ----
   const int k4 = tid & 3;
@@ -740,7 +744,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
           } else if (EPI == CF_EPI_SFT) {
             const f32x4 dec = r0[p], sc = r1[p];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = dec[e] + a.sft_w * (dec[e] * sc[e] + v[e]);
+            for (int e = 0; e < 4; ++e) v[e] = dec[e] + sft_w * (dec[e] * sc[e] + v[e]);
           } else if (EPI == CF_EPI_GELU) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = 0.5f * v[e] * (1.0f + erff(v[e] * 0.70710678118654752440f));
@@ -835,7 +839,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
               v += a.res[o];
             } else if (EPI == CF_EPI_SFT) {
               const float dec = a.res[o];
-              v = dec + a.sft_w * (dec * a.sft_scale[o] + v);
+              v = dec + sft_w * (dec * a.sft_scale[o] + v);
             } else if (EPI == CF_EPI_GELU) {
               v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
             }
@@ -1310,8 +1314,8 @@ static int conv_validate(const cf_conv_desc* d, const int* pq, ConvFacts& f) {
   return CF_OK;
 }
 
-static void conv_fill_args(ConvArgsExt& a, const cf_conv_desc* d, const ConvFacts& f) {
-  cf_fill_conv_args(a, d);
+static void conv_fill_args(ConvArgsExt& a, const cf_conv_desc* d, const ConvFacts& f, const float* sft_w_img = nullptr) {
+  cf_fill_conv_args(a, d, sft_w_img);
   a.nchunks = d->bf16_mfma ? a.cin / 32 : (a.cin + CF_BK - 1) / CF_BK;
   a.hin = d->hin;
   a.win = d->win;
@@ -1430,24 +1434,33 @@ static int launch_direct(ConvArgsExt& a, const cf_conv_desc* d, const ConvFacts&
   return CF_ERR_ARG;
 }
 
-static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq) {
+static int conv_dispatch(const cf_conv_desc* d, hipStream_t stream, int* pq, const float* sft_w_img = nullptr) {
   ConvFacts f;
   if (const int rc = conv_validate(d, pq, f); rc != CF_OK) return rc;
   if (d->taps == 1 && d->bf16_mfma == CF_OPERAND_F16X2) {  // (the other four kernel families first)
     // images of more than CF_TOKEN_IMAGE_MAX pixels: the streaming 1x1 form of the split-half convolution kernel (weight: form 3 of
     // cf_pack_conv_weight_f16x2); token matrices (the Transformer's 16x16 "images"): the token GEMM (cf_pack_linear_weight_f16x2)
-    if ((long)d->hout * d->wout > CF_TOKEN_IMAGE_MAX) return cf_split_launch(d, stream, pq);
+    if ((long)d->hout * d->wout > CF_TOKEN_IMAGE_MAX) return cf_split_launch(d, stream, pq, sft_w_img);
     return cf_gemm_split_launch(d, stream, pq);
   }
-  if (d->winograd == 2) return cf_wf43_launch(d, stream, pq);  // F(4x4,3x3), split-half operands (cf_wf43.hip)
-  if (d->winograd) return cf_winograd_launch(d, stream, pq);   // F(2x2,3x3), fp32 or split-half operands
-  if (d->bf16_mfma == CF_OPERAND_F16X2) return cf_split_launch(d, stream, pq);
+  if (d->winograd == 2) return cf_wf43_launch(d, stream, pq, sft_w_img);  // F(4x4,3x3), split-half operands (cf_wf43.hip)
+  if (d->winograd) return cf_winograd_launch(d, stream, pq, sft_w_img);   // F(2x2,3x3), fp32 or split-half operands
+  if (d->bf16_mfma == CF_OPERAND_F16X2) return cf_split_launch(d, stream, pq, sft_w_img);
   ConvArgsExt a;
-  conv_fill_args(a, d, f);
+  conv_fill_args(a, d, f, sft_w_img);
   return launch_direct(a, d, f, stream, pq);
 }
 
 extern "C" int cf_conv2d(const cf_conv_desc* d, cf_stream_t stream) { return conv_dispatch(d, (hipStream_t)stream, nullptr); }
+
+// cf_conv2d with one SFT weight per image: every kernel family's SFT epilogue reads w_img[b] where the scalar launch reads d->sft_w (one
+// expression, cf_sft_weight), so image b is bitwise the scalar launch with sft_w = w_img[b].  Checked before anything is launched.
+extern "C" int cf_conv2d_sft_w(const cf_conv_desc* d, const float* w_img, cf_stream_t stream) {
+  CF_REQUIRE(d, "cf_conv2d_sft_w: null descriptor");
+  CF_REQUIRE(w_img, "cf_conv2d_sft_w: w_img is NULL (one float per image on the device; a scalar weight is cf_conv2d's sft_w)");
+  CF_REQUIRE(d->epilogue == CF_EPI_SFT, "cf_conv2d_sft_w: the per-image weight belongs to the SFT epilogue (got epilogue %d)", d->epilogue);
+  return conv_dispatch(d, (hipStream_t)stream, nullptr, w_img);
+}
 
 // cf_conv2d with the uint8 HWC BGR image at one end: the two vector-ALU boundary kernels in their U8 forms, nothing else.  The image
 // pointer takes the place of d->in0 / d->out in a copy of the descriptor; the copy then passes every check of cf_conv2d, and the rules

@@ -88,6 +88,7 @@ struct SplitArgs {
   int batch, hin, win, hout, wout;
   int cout, cout_pad;
   int prologue, epilogue;
+  int s2_skip;  // stride-2 form: 1 = skip the (tap, parity) steps whose weight block is zero by construction (C % 32 == 0)
   const float* pro_scale;
   const float* pro_shift;
   const float* weight;  // [class][cin/32][tap][cout_pad][hi 32 | lo 32] halves = 32 floats per row
@@ -96,13 +97,13 @@ struct SplitArgs {
   const float* sft_scale;
   float sft_w;
   float acc_scale;  // exact power of two: 1 / (weight scale applied at pack time)
+  const float* sft_w_img;  // SFT: [batch] weights, one per image (cf_conv2d_sft_w), or null: sft_w for all of them
   const float* act_scale;  // [batch][2] (s, 1/s) powers of two for un-normalised inputs (prologue NONE / LEAKY), or null
   float* out;
   double* stats_out;
   int stats_cpg, nparts;
   int tiles_x, tiles_per_img, ntn;
   int nt_out;   // non-temporal output stores (cf_common.h: cf_store16)
-  int s2_skip;  // stride-2 form: 1 = skip the (tap, parity) steps whose weight block is zero by construction (C % 32 == 0)
 };
 static_assert(sizeof(SplitArgs) == 184, "the kernarg block keeps its size: it feeds the register allocation of every instantiation");
 
@@ -204,6 +205,8 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
   const bool affine = a.prologue == CF_PRO_AFFINE || a.prologue == CF_PRO_AFFINE_SWISH;
   // cf_act_scales (cf_conv_parts.h) written out: the prologue is a runtime value here, and behind a runtime flag the helper compiled to
   // another branch structure
+  // SFT weight of the tile's image, read here like the range scale below -- before the kernel's first store, so that it is a scalar load
+  const float sft_w = cf_sft_weight(a.sft_w_img, a.sft_w, b);
   float act_s = 1.f, act_is = 1.f;
   if (!affine && a.act_scale) {
     act_s = a.act_scale[2 * b];
@@ -568,7 +571,7 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? (NI == 1 && TAPS != 1 && !(S2 &
 #pragma unroll
       for (int p = 0; p < PASSES; ++p) {
         f32x4 v = cf_epi_bias<true>(t[p], s, bias4);
-        v = cf_epi_apply(v, EPI, r0[mi][p], r1[mi][p], a.sft_w);
+        v = cf_epi_apply(v, EPI, r0[mi][p], r1[mi][p], sft_w);
         t[p] = v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -647,7 +650,7 @@ int split_launch(SplitArgs& k, int batch, hipStream_t stream) {
 }  // namespace
 
 // Called by cf_conv2d (cf_igemm.hip) for descriptors with bf16_mfma == CF_OPERAND_F16X2; the common argument checks have run.
-int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {
+int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img) {
   const bool s2 = d->stride == 2;
   const bool one = d->taps == 1;
   CF_REQUIRE((d->taps == 9 || one) && (d->stride == 1 || s2) && !d->in_nchw && !d->out_nchw && !d->winograd,
@@ -670,7 +673,7 @@ int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query)
   CF_REQUIRE(cf_dense_zero_pad(d), "cf_conv2d(f16x2): dense tensors with zero padding only");
   if (const int e = cf_require_acc_scale(d, "cf_conv2d(f16x2)")) return e;
   SplitArgs a;
-  cf_fill_conv_args(a, d);
+  cf_fill_conv_args(a, d, sft_w_img);
   a.hin = d->hin;
   a.win = d->win;
   if (s2) {  // space-to-depth view: even tensor rows through in0, odd rows through in1, 2C channels (two pixels) each

@@ -131,6 +131,7 @@ struct F4Args {
   const float* sft_scale;
   float sft_w;
   float acc_scale;
+  const float* sft_w_img;  // SFT: [batch] weights, one per image (cf_conv2d_sft_w), or null: sft_w for all of them
   const float* act_scale;
   float* out;
   double* stats_out;
@@ -138,7 +139,7 @@ struct F4Args {
   int tiles_x, tiles_per_img, ntn;
   int nt_out;   // non-temporal output stores (cf_common.h: cf_store16)
 };
-static_assert(sizeof(F4Args) == 160, "the kernarg block keeps its size: it feeds the register allocation of every instantiation");
+static_assert(sizeof(F4Args) == 168, "the kernarg block is 168 bytes (160 before sft_w_img, which found no padding to take): its size feeds the register allocation of every instantiation, so a change is re-checked with tools/kernel_resources.py");
 
 // quad swizzle of V: tile row ty -> 0, 2, 3, 1
 __device__ __forceinline__ int f4_vs(int ty) { return (0x78 >> (2 * ty)) & 3; }
@@ -764,6 +765,9 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   float* const Mst = smem;
   const int e_cp = (lane & 31) + 32 * (wave >> 3), e_rh = lane >> 5, e_tp = wave & 7;   // (channel pair within the workgroup's F4_BN / 2)
   const float acc_s = a.acc_scale * act_is;                // (a product of powers of two: exact)
+  // SFT weight of the patch's image: one scalar read, here -- behind the slab loop, whose scalar registers are all taken (at the kernel's
+  // head it cost the SFT instantiations 20 to 60 spilled registers), and before the first store (behind one it would be a vector load)
+  [[maybe_unused]] const float sft_w = EPI == CF_EPI_SFT ? cf_sft_weight(a.sft_w_img, a.sft_w, b) : 0.f;
   const int nn = n0 + 2 * e_cp;
   f4_f32x2 bias2 = {0.f, 0.f};
   if (a.bias) bias2 = *reinterpret_cast<const f4_f32x2*>(a.bias + nn);
@@ -877,7 +881,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
       for (int c = 0; c < 4; ++c) {
         f4_f32x2 v = o[aa][c] * acc_s + bias2;
         if (EPI == CF_EPI_RESIDUAL) v += r0[aa][c];
-        else if (EPI == CF_EPI_SFT) v = r0[aa][c] + a.sft_w * (r0[aa][c] * r1[aa][c] + v);
+        else if (EPI == CF_EPI_SFT) v = r0[aa][c] + sft_w * (r0[aa][c] * r1[aa][c] + v);
         o[aa][c] = v;   // (stored below: the eight stores of a pass sit behind ONE wave-uniform choice of their cache policy)
         rs += v;
         rq += v * v;
@@ -962,7 +966,7 @@ bool cf_wf43_k32(int cout, int cin) {
 }
 
 // Called by cf_conv2d (cf_igemm.hip) for descriptors with winograd == 2; the common argument checks have run there.
-int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {
+int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img) {
   CF_REQUIRE(d->taps == 9 && d->stride == 1 && !d->in_nchw && !d->out_nchw &&
                  (d->bf16_mfma == CF_OPERAND_F16X2 || d->bf16_mfma == CF_OPERAND_F32),
              "cf_conv2d(winograd 2): F(4x4,3x3) covers 3x3 stride-1 NHWC convolutions with split-half or fp32 operands");
@@ -992,7 +996,7 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) 
   CF_REQUIRE(d->stats_cpg == 0 || (d->stats_cpg <= 64 && (d->stats_cpg & (d->stats_cpg - 1)) == 0 && d->stats_cpg >= 2),
              "cf_conv2d(winograd 2): stats_cpg %d (a power of two, 2..64)", d->stats_cpg);
   F4Args a;
-  cf_fill_conv_args(a, d);
+  cf_fill_conv_args(a, d, sft_w_img);
   a.nchunks = a.cin / CF_BK;
   a.h = d->hout;
   a.w = d->wout;

@@ -66,6 +66,7 @@ struct WinoArgs {
   int batch, h, w;
   int cout, cout_pad;
   int prologue, epilogue;
+  int ntn;
   const float* pro_scale;
   const float* pro_shift;
   const float* weight;  // [16 pos][nchunks][cout_pad][16]
@@ -74,11 +75,12 @@ struct WinoArgs {
   const float* sft_scale;
   float sft_w;
   float acc_scale;  // H2: inverse of the pack-time weight scale (a power of two); 1 otherwise
+  const float* sft_w_img;  // SFT: [batch] weights, one per image (cf_conv2d_sft_w), or null: sft_w for all of them
   const float* act_scale;  // H2: [batch][2] (s, 1/s) powers of two for un-normalised inputs (prologue NONE / LEAKY), or null
   float* out;
   double* stats_out;
   int stats_cpg, nparts;
-  int tiles_x, tiles_per_img, ntn;
+  int tiles_x, tiles_per_img;
 };
 // split-K instantiation (layers of at most 32x32 pixels per face, see cf_common.h): workspace, ticket counters, split count
 struct WinoArgsSK : WinoArgs {
@@ -167,6 +169,9 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
   // store_patch put an s_waitcnt vmcnt(0) there, which also drained the weight fragments requested just before.
   const bool affine = a.prologue == CF_PRO_AFFINE || a.prologue == CF_PRO_AFFINE_SWISH;
   // cf_act_scales (cf_conv_parts.h) written out: called as the helper, the two H2 instantiations got another branch structure
+  // SFT weight of the patch's image, read here like the range scale below -- before the kernel's first store, so that it is a scalar load
+  // (split-K: every split reads it, the one that draws the last ticket uses it)
+  const float sft_w = cf_sft_weight(a.sft_w_img, a.sft_w, b);
   float act_s = 1.f, act_is = 1.f;
   if (H2 && !affine && a.act_scale) {
     act_s = a.act_scale[2 * b];
@@ -430,7 +435,7 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
     for (int i = 0; i < 4; ++i) {
       f32x4 v = o[i];
       v = cf_epi_bias<H2>(v, acc_s, bias4);
-      v = cf_epi_apply(v, a.epilogue, r0[pass][i], r1[pass][i], a.sft_w);
+      v = cf_epi_apply(v, a.epilogue, r0[pass][i], r1[pass][i], sft_w);
       cf_epi_store<false>(a.out, offs[pass][i], v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -483,7 +488,7 @@ __global__ __launch_bounds__(256, 2) void winograd_kernel(const std::conditional
 }  // namespace
 
 // Called by cf_conv2d (cf_igemm.hip) for descriptors with winograd != 0; the common argument checks have run there.
-int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {
+int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img) {
   CF_REQUIRE(d->taps == 9 && d->stride == 1 && !d->upsample && !d->in_nchw && !d->out_nchw &&
                  d->bf16_mfma >= CF_OPERAND_F32 && d->bf16_mfma <= CF_OPERAND_F16X2,
              "cf_conv2d: winograd covers 3x3 stride-1 NHWC convolutions");
@@ -498,10 +503,10 @@ int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_que
              d->cout_pad);
   CF_REQUIRE(cf_epi_is_quad_triple(d), "cf_conv2d: winograd epilogues are none / residual / SFT");
   CF_REQUIRE(cf_dense_zero_pad(d), "cf_conv2d: winograd reads / writes dense tensors with zero padding");
-  if (h2 && cf_wsplit_covers(d)) return cf_wsplit_launch(d, stream, parts_query);
+  if (h2 && cf_wsplit_covers(d)) return cf_wsplit_launch(d, stream, parts_query, sft_w_img);
   CF_REQUIRE(!h1, "cf_conv2d(winograd, single 16-bit operands): not covered");
   WinoArgs a;
-  cf_fill_conv_args(a, d);
+  cf_fill_conv_args(a, d, sft_w_img);
   a.nchunks = a.cin / CF_BK;
   a.h = d->hout;
   a.w = d->wout;

@@ -72,13 +72,14 @@ struct WsArgs {
   const float* sft_scale;
   float sft_w;
   float acc_scale;
+  const float* sft_w_img;  // SFT: [batch] weights, one per image (cf_conv2d_sft_w), or null: sft_w for all of them
   const float* act_scale;  // [batch][2] (s, 1/s) powers of two for un-normalised inputs (PRO NONE / LEAKY), or null
   float* out;
   double* stats_out;
   int stats_cpg, nparts;
   int tiles_x, tiles_per_img, ntn;
 };
-static_assert(sizeof(WsArgs) == 160, "the kernarg block keeps its size: it feeds the register allocation of every instantiation");
+static_assert(sizeof(WsArgs) == 168, "the kernarg block is 168 bytes (160 before sft_w_img, which found no padding to take): its size feeds the register allocation of every instantiation, so a change is re-checked with tools/kernel_resources.py");
 
 // PRO = the prologue (enum cf_prologue) as a template parameter: with a switch inside the slab loop hipcc's wait-count pass merged the
 // branches into s_waitcnt vmcnt(0) before the patch store, i.e. every iteration waited for the weight fragments it had just requested.
@@ -129,6 +130,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wsplit_kernel(const WsArgs a) {
   }
   constexpr bool affine = PRO == CF_PRO_AFFINE || PRO == CF_PRO_AFFINE_SWISH;
   // cf_act_scales (cf_conv_parts.h) written out: called as the helper, the branch on the null pointer came out with the other polarity
+  // SFT weight of the patch's image, read here like the range scale below -- before the kernel's first store, so that it is a scalar load
+  const float sft_w = cf_sft_weight(a.sft_w_img, a.sft_w, b);
   float act_s = 1.f, act_is = 1.f;
   if (!affine && a.act_scale) {
     act_s = a.act_scale[2 * b];
@@ -385,7 +388,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void wsplit_kernel(const WsArgs a) {
     for (int i = 0; i < 4; ++i) {
       f32x4 v = o[i];
       v = cf_epi_bias<true>(v, acc_s, bias4);
-      v = cf_epi_apply(v, a.epilogue, r0[pass][i], r1[pass][i], a.sft_w);
+      v = cf_epi_apply(v, a.epilogue, r0[pass][i], r1[pass][i], sft_w);
       cf_epi_store<BIO>(a.out, offs[pass][i], v);   // (bf16 tensors: rounded here, once; the statistics see the fp32 values)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -409,9 +412,9 @@ bool cf_wsplit_covers(const cf_conv_desc* d) {
          d->hout % WS_TH == 0 && d->wout % WS_TW == 0 && (long)d->hout * d->wout >= 32 * 32 && (d->stats_cpg == 0 || d->stats_cpg >= 4);
 }
 
-int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query) {
+int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img) {
   WsArgs a;
-  cf_fill_conv_args(a, d);
+  cf_fill_conv_args(a, d, sft_w_img);
   a.nchunks = a.cin / CF_BK;
   a.h = d->hout;
   a.w = d->wout;

@@ -57,6 +57,7 @@ SIGNATURES = {
     'cf_device_init': (_I, []),
     'cf_conv2d': (_I, [ctypes.POINTER(ConvDesc), _P]),
     'cf_conv2d_u8': (_I, [ctypes.POINTER(ConvDesc), _P, _P, _P]),
+    'cf_conv2d_sft_w': (_I, [ctypes.POINTER(ConvDesc), _P, _P]),
     'cf_conv2d_stats_parts': (_I, [ctypes.POINTER(ConvDesc)]),
     'cf_conv2d_workspace_bytes': (_L, [ctypes.POINTER(ConvDesc)]),
     'cf_conv2d_tiles': (_I, [ctypes.POINTER(ConvDesc)]),

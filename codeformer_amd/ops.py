@@ -64,6 +64,18 @@ class GNStats:
         self.part, self.parts, self.cpg = part, parts, cpg
 
 
+def select_rows(x, sel):
+    """x.index_select(0, sel) for an activation of the network (sel: int64 indices on x's device; an index may repeat): the images `sel`
+    names, as a batch of their own.  The GroupNorm partials the producing conv attached (`._cf_stats`, [image][group][part][2]) travel with
+    their images, so the consumers of the selection compute per image exactly what they compute for the whole batch; a parked range-scale
+    table is not carried -- act_scale() rebuilds it from those partials, per image."""
+    y = x.index_select(0, sel)
+    st = getattr(x, '_cf_stats', None)
+    if st is not None:
+        y._cf_stats = GNStats(st.part.view(x.shape[0], -1).index_select(0, sel).reshape(-1), st.parts, st.cpg)
+    return y
+
+
 class PackedWeight:
     """A conv / linear weight in the kernel layout [tap][cin_pad/16][cout_pad][16] (+ bias).
     `bf16` is the operand code of cf_conv_desc.bf16_mfma: 0 / False fp32, 1 / True bf16, 2 IEEE half."""
@@ -578,6 +590,8 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     x, x2 and `out` (optional destination) may be channel slices `buf[..., a:b]` of wider NHWC buffers -- the dense-block
     pattern of RRDBNet, where torch.cat never materialises; res / sft_scale (= res2 of EPI_AXPY2) then share out's stride.
     EPI_LEAKY / EPI_AXPY / EPI_AXPY2 use sft_w as alpha (see cf_epilogue in the header).
+    sft_w with EPI_SFT: a float, or a contiguous float32 tensor of B values on x's device -- one weight per image (cf_conv2d_sft_w); image b
+    is then bitwise the launch on that image alone with sft_w = float(sft_w[b]).
     pad_mode: PAD_ZERO, PAD_REFLECT (ReflectionPad2d(1) + unpadded 3x3) or PAD_EDGE (with upsample: reflection padding of the
     upsampled image); pad_lo=1 with stride 2: one padded row / column on every side instead of right / bottom only.
     act: (B, 2) range-scale table of an un-normalised input (act_scale(x)); dropped when the layer's kernel has fp32 operands.
@@ -663,6 +677,15 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     for t in (scale, shift):
         if t is not None and tuple(t.shape) != (B, c0 + c1):
             raise ValueError(f'prologue table shape {tuple(t.shape)} != {(B, c0 + c1)}')
+    w_img = None
+    if torch.is_tensor(sft_w):
+        if epilogue != EPI_SFT or u8_in is not None or u8_out is not None:
+            raise ValueError('sft_w: a tensor (one weight per image) belongs to epilogue=EPI_SFT; the other epilogues take a float')
+        if sft_w.dtype != torch.float32:
+            raise TypeError(f'sft_w: expected a float32 tensor of {B} values, got {sft_w.dtype}')
+        if sft_w.dim() != 1 or sft_w.shape[0] != B or sft_w.device != dev:
+            raise ValueError(f'sft_w: expected {B} values (one per image) on {dev}, got shape {tuple(sft_w.shape)} on {sft_w.device}')
+        w_img, sft_w = L.ptr(sft_w), 0.0
     d = L.ConvDesc(
         in0=None if img_in is not None else L.ptr(x, not in_nchw, dtype=io), in1=L.ptr(x2, True, dtype=io), c0=c0, c1=c1, batch=B, hin=H, win=W, hout=Ho, wout=Wo, cout=pw.cout,
         cout_pad=pw.cout_pad, taps=pw.taps, stride=stride, upsample=2 if f42_up else int(bool(upsample)), in_nchw=int(bool(in_nchw)),
@@ -701,7 +724,9 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
         out._cf_stats = GNStats(part, parts, d.stats_cpg)
 
     def launch():
-        if u8_in is None and u8_out is None:
+        if w_img is not None:
+            L.check(lib.cf_conv2d_sft_w(ctypes.byref(d), w_img, L.stream_ptr()), 'cf_conv2d_sft_w')
+        elif u8_in is None and u8_out is None:
             L.check(lib.cf_conv2d(ctypes.byref(d), L.stream_ptr()), 'cf_conv2d')
         else:      # the same descriptor; the image pointer takes the place of in0 / out
             L.check(lib.cf_conv2d_u8(ctypes.byref(d), u8_in, u8_out, L.stream_ptr()), 'cf_conv2d_u8')

@@ -38,6 +38,8 @@ class AlignedFacePipeline:
 
     net:      a CodeFormer module on a ROCm device (anything with the reference call signature net(x, w=, adain=) -> (out, ...))
     post:     optional callable(face_bgr_u8, restored_bgr_u8, meta) -> image to write (runs in a worker; default: the restored face)
+    w:        restore(..., w=): one fidelity weight for every face, or one weight per path (sequence / array / tensor of len(paths) values,
+              read on the host once); each batch gets its slice, so faces with different weights share a batch
     Returns a dict of stage timings; `failures` counts faces that fell back to their input (the reference's behaviour on an
     inference error, inference_codeformer.py:207-209) unless strict=True.
     """
@@ -69,6 +71,11 @@ class AlignedFacePipeline:
         from . import ops
         assert len(paths) == len(out_paths)
         n, B = len(paths), self.batch
+        per_path = None
+        if not isinstance(w, (int, float)) and getattr(w, 'ndim', 1) != 0:   # one weight per path: host floats, sliced per batch below
+            per_path = [float(v) for v in (w.detach().cpu().tolist() if torch.is_tensor(w) else w)]
+            if len(per_path) != n:
+                raise ValueError(f'restore: w holds {len(per_path)} weights for {n} paths')
         nb = (n + B - 1) // B
         stats = {'faces': n, 'batches': nb, 'failures': 0, 'wait_decode_s': 0.0, 'wait_slot_s': 0.0}
         t0 = time.perf_counter()
@@ -101,6 +108,8 @@ class AlignedFacePipeline:
                     slot.ev_in.record(self.h2d)
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(slot.ev_in)
+                if per_path is not None:
+                    w = per_path[lo:hi]
                 try:
                     if hasattr(self.net, 'restore_u8'):      # bytes in, bytes out: the first / last conv read / write the uint8 faces,
                         self.net.restore_u8(slot.dev_in[:m], w=w, adain=adain, out=slot.dev_out[:m])   # straight into the slot

@@ -47,7 +47,9 @@ class VideoRestorer:
 
     @torch.no_grad()
     def restore(self, frames, affines, w=0.5, adain=True, return_tensors=False, keep_faces=False, gray=None):
-        """keep_faces: also keep every frame's (crops, restored faces) as uint8 host arrays in `self.faces_out[i]` (the reference saves
+        """w: ONE fidelity weight for all faces of all frames (a number: the faces of a frame are batched across frames, so a weight per
+        face has no caller-visible order here; CodeFormer.forward / AlignedFacePipeline take one weight per face).
+        keep_faces: also keep every frame's (crops, restored faces) as uint8 host arrays in `self.faces_out[i]` (the reference saves
         them next to the pasted image, inference_codeformer.py:232-247).  gray: per-frame flags; the faces of a gray frame take the
         reference's gray colour transfer (face_restoration_helper.py:364-369: bgr2gray + adain_npy against the crop) on the host and are
         rounded back to uint8 before the paste (the reference pastes the float result: at most half a grey level of difference); with a

@@ -136,7 +136,7 @@ typedef struct cf_conv_desc {
   const float* bias;      /* [cout] or NULL */
   const float* res;       /* [batch][hout][wout][cout] (RESIDUAL / SFT: the `dec` tensor) */
   const float* sft_scale; /* [batch][hout][wout][cout] (SFT) */
-  float sft_w;
+  float sft_w;            /* SFT: the weight w of every image (one per image: cf_conv2d_sft_w); LEAKY / AXPY family: alpha */
   float* out;
   double* stats_out;      /* optional: fp64 partial (sum, sumsq) of the OUTPUT per (image, group of stats_cpg channels,
                              tile part), layout [batch][cout/stats_cpg][parts][2], parts = cf_conv2d_stats_parts(d);
@@ -229,6 +229,14 @@ int cf_conv2d(const cf_conv_desc* d, cf_stream_t stream);
                     a dense input (io_bf16 0 or 1).
    Exactly one of the two is non-NULL.  Anything else: CF_ERR_ARG, nothing launched. */
 int cf_conv2d_u8(const cf_conv_desc* d, const uint8_t* img_in, uint8_t* img_out, cf_stream_t stream);
+/* cf_conv2d with d->epilogue == CF_EPI_SFT and one weight per image (entry point added, ABI version unchanged): w_img holds [batch]
+   floats on the device and image b computes res + w_img[b] * (res * sft_scale + (acc + bias)); d->sft_w is ignored.  Every kernel family
+   that has the SFT epilogue takes it (direct fp32 / bf16 / f16, split halves, F(2x2,3x3), F(4x4,3x3), their split-K and bf16-storage
+   forms); the weight is one wave-uniform read per output patch, and the kernels form it by the same expression as the scalar launch, so
+   image b's output and statistics partials are bitwise those of cf_conv2d on that image alone with sft_w = w_img[b] -- for any value,
+   non-positive and non-finite ones included (whether a non-positive weight means "no fusion" is the caller's rule, not the kernel's).
+   A NULL w_img or any other epilogue: CF_ERR_ARG with a message, nothing launched (checked before any device call). */
+int cf_conv2d_sft_w(const cf_conv_desc* d, const float* w_img, cf_stream_t stream);
 /* number of statistics partials per (image, group) the launch described by d will write (>0), or <0 on error */
 int cf_conv2d_stats_parts(const cf_conv_desc* d);
 /* split-K launches: bytes of workspace / number of output tiles (= counters) the launch described by d needs (0 when split_k <= 1) */

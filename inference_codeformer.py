@@ -9,6 +9,8 @@ Same flags, same result tree (results/<input>_<w>/restored_faces/<basename>.png)
 Whole images (and directories of extracted video frames) take the reference's full flow: RetinaFace detection + alignment fit on the
 host (facelib), crop warp / batched restoration / paste-back on the device; --affine_npz replaces the detector by a file of matrices.
 --face_upsample (faces through Real-ESRGAN x2 in batches before the paste, -s 2) and --draw_box run on the device too.
+--fidelity_sweep W [W ...] (with --has_aligned): every face at several fidelity weights, restored_faces/<name>_w<W>.png each; the encoder
+and the Transformer run once per face.
 Video container files (.mp4 ...) need ffmpeg, which this image lacks: extract the frames to a directory first.
 """
 import argparse
@@ -56,6 +58,10 @@ def parse_args(argv=None):
     p.add_argument('--save_video_fps', type=float, default=None, help='Frame rate for saving video. Default: None')
     # --- additions (do not change the behaviour of the flags above) ---
     p.add_argument('--batch_size', type=int, default=None, help='Faces per forward. Default: 16 on GPU, 1 on CPU')
+    p.add_argument('--fidelity_sweep', type=float, nargs='+', default=None, metavar='W',
+                   help='--has_aligned only: restore every face at each of these fidelity weights in one pass over the encoder '
+                        '(CodeFormer.restore_sweep) and write restored_faces/<name>_w<W with two decimals>.png per face and weight; '
+                        '-w keeps its meaning (result folder name)')
     p.add_argument('--device', type=str, default=None, help="Override the device pick (e.g. 'cpu')")
     p.add_argument('--random_init_seed', type=int, default=None,
                    help='Use torch.manual_seed(SEED) random weights when weights/CodeFormer/codeformer.pth is absent '
@@ -255,8 +261,20 @@ def build_net(device, args):
 FACE_UPSAMPLER_SCALE = 2   # RealESRGAN_x2plus, the reference's face upsampler (inference_codeformer.py:19-45)
 
 
+def sweep_name(name, w, suffix=None):
+    """File name of face `name` restored at fidelity weight w by --fidelity_sweep: <name>_w<W with two decimals>[_<suffix>].png."""
+    return f'{name}_w{w:.2f}.png' if suffix is None else f'{name}_w{w:.2f}_{suffix}.png'
+
+
 def check_args(args):
     """Argument checks that need no device."""
+    if getattr(args, 'fidelity_sweep', None) is not None:
+        if not args.has_aligned:
+            raise NotImplementedError('--fidelity_sweep restores aligned faces at several weights and needs --has_aligned; whole images and '
+                                      'frames are pasted back at one weight (-w)')
+        names = [f'{v:.2f}' for v in args.fidelity_sweep]
+        if len(set(names)) != len(names):
+            raise ValueError(f'--fidelity_sweep: two weights share a file name (two decimals): {names}')
     if args.face_upsample and not args.has_aligned and args.upscale != FACE_UPSAMPLER_SCALE:
         raise NotImplementedError(f'--face_upsample with -s {args.upscale}: the x{FACE_UPSAMPLER_SCALE} face upsampler pastes at -s '
                                   f'{FACE_UPSAMPLER_SCALE} only; other scales need the LANCZOS4 resize of its output (cv2.INTER_LANCZOS4), '
@@ -313,7 +331,33 @@ def main(argv=None):
         name = os.path.splitext(os.path.basename(img_path))[0]
         return os.path.join(result_root, 'restored_faces', f'{name}.png' if args.suffix is None else f'{name}_{args.suffix}.png')
 
-    if device.type == 'cuda':
+    if args.fidelity_sweep is not None:
+        # every face at K weights: encoder, Transformer and code lookup once per face, the generator once per (face, positive weight)
+        ws = [float(v) for v in args.fidelity_sweep]
+        per_call = max(1, bs // len(ws))                 # faces per call: about `bs` generator rows
+        for s0 in range(0, len(my_list), per_call):
+            chunk = my_list[s0:s0 + per_call]
+            faces = []
+            for j, img_path in enumerate(chunk):
+                print(f'[{first + s0 + j + 1}/{total}] Processing: {os.path.basename(img_path)}')
+                faces.append(resize_bilinear(imread_bgr(img_path), (512, 512)))
+            grays = [is_gray(f, threshold=10) for f in faces]
+            try:
+                with torch.no_grad():
+                    outs = net.restore_sweep(faces_to_tensor(faces, device), ws, adain=True)[0]
+                restored = [tensor_to_faces(outs[k]) for k in range(len(ws))]
+            except Exception as error:  # as below: the reference returns the input face
+                if args.strict:
+                    raise
+                print(f'\tFailed inference for CodeFormer: {error}')
+                failures += len(faces)
+                restored = [tensor_to_faces(faces_to_tensor(faces, device))] * len(ws)
+            for k, wk in enumerate(ws):
+                for img_path, face, out, g in zip(chunk, faces, restored[k], grays):
+                    name = os.path.splitext(os.path.basename(img_path))[0]
+                    imwrite(finish_face(face, out, g), os.path.join(result_root, 'restored_faces', sweep_name(name, wk, args.suffix)))
+        my_list = []
+    elif device.type == 'cuda':
         # overlapped pipeline: PNG decode / encode in a worker pool, uint8 over PCIe through pinned staging on side streams
         from codeformer_amd.pipeline import AlignedFacePipeline
         for j, img_path in enumerate(my_list):
