@@ -36,10 +36,61 @@ def _act_dtype(t, what='activation'):
     return t.dtype
 
 
+# ---- state kept on tensor objects ---------------------------------------------------------------------------------------------------
+# Three attributes travel on a tensor OBJECT from the launch that wrote it to the launches that read it: `_cf_stats` (GNStats: the GroupNorm
+# partials of a conv epilogue), `_cf_act` (a cached range-scale table) and `_cf_act_pair` (the table of a concatenated pair, on its first
+# member).  The contract (tests/test_gpu_tensor_state.py):
+#   1. they describe the values the object holds NOW, or they are absent;
+#   2. every ops.* call that writes into a caller-supplied tensor drops all three from that object, and from its `._base` where PyTorch
+#      records one, before it attaches anything new -- after its own validation, so a refused call leaves the state alone;
+#   3. state carries the STAMP of its tensor at attach and is ignored once the stamp has moved.  The stamp is (PyTorch's version counter,
+#      the library's own write count of the tensor's storage): the first sees a user's y.mul_() / y.copy_() -- outside torch.inference_mode,
+#      where tensors keep no counter and such a write cannot be seen --, the second sees the library's writes, which go through raw
+#      pointers and never move the version.  The write count is what reaches the state of `buf` when a slice buf[..., a:b] is written
+#      under inference_mode (inference tensors record no `._base`), of any other alias, and of a pair's second member;
+#   4. the copies to_bf16 / select_rows make carry state of their own (their own stamp, the partials of copy time): rewriting the source
+#      does not touch them.
+_STATE_ATTRS = ('_cf_stats', '_cf_act', '_cf_act_pair')
+_WRITE_EPOCH = {}    # storage address -> library writes into a caller-supplied destination there (a recycled address just goes on counting)
+
+
+def tensor_version(t):
+    """Version counter of a tensor, or None for inference tensors (torch.inference_mode), which do not track one -- reading
+    `._version` there raises.  Callers skip their version-keyed caches for None."""
+    return None if t.is_inference() else t._version
+
+
+def tensor_stamp(t):
+    """(version counter or None, library writes into t's storage): equal stamps <=> no write to t that the library can see."""
+    return (tensor_version(t), _WRITE_EPOCH.get(t.untyped_storage().data_ptr(), 0) if _WRITE_EPOCH else 0)
+
+
+def _drop_state(t):
+    """Rule 2: `t` is about to be overwritten through its raw pointer.  Its state goes, its base's state goes, and whatever other object
+    shares the storage finds its stamp moved."""
+    for o in (t, t._base):
+        if o is not None:
+            for a in _STATE_ATTRS:
+                o.__dict__.pop(a, None)
+    p = t.untyped_storage().data_ptr()
+    _WRITE_EPOCH[p] = _WRITE_EPOCH.get(p, 0) + 1
+
+
+def live_stats(t):
+    """t's `_cf_stats` if it still describes t (rule 3), else None.  Statistics without a stamp (attached by hand) are trusted."""
+    st = getattr(t, '_cf_stats', None)
+    if st is None:
+        return None
+    stamp = getattr(st, 'stamp', None)
+    return st if stamp is None or stamp == tensor_stamp(t) else None
+
+
 def to_bf16(x):
     """fp32 NHWC activation -> its bf16 copy (round to nearest even, cf_f32_to_bf16): the tensors that ENTER the bf16-storage part of the
     generator (the decoder feature in front of the first bf16 Upsample, the encoder taps of the fusion blocks).  The GroupNorm partials /
-    range-scale table the producer attached travel with the copy: they were taken from the fp32 values, as the bf16 epilogues take theirs."""
+    range-scale table the producer attached travel with the copy: they were taken from the fp32 values, as the bf16 epilogues take theirs.
+    State that no longer describes x (rule 3 above) is not copied; what is copied describes x at copy time and stays valid for the copy
+    when x is rewritten afterwards (a rewrite takes fresh partials, it does not touch the ones the copy holds)."""
     if x.dtype == torch.bfloat16:
         return x
     _f32(x)
@@ -47,32 +98,38 @@ def to_bf16(x):
         raise ValueError('to_bf16: expected a dense tensor with a multiple of 8 elements')
     y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     L.check(L.load().cf_f32_to_bf16(L.ptr(x), x.numel(), L.ptr(y, dtype=torch.bfloat16), L.stream_ptr()), 'cf_f32_to_bf16')
-    for attr in ('_cf_stats', '_cf_act'):
-        v = getattr(x, attr, None)
-        if v is not None:
-            setattr(y, attr, v)
+    st = live_stats(x)
+    if st is not None:
+        y._cf_stats = GNStats(st.part, st.parts, st.cpg, tensor_stamp(y)) if isinstance(st, GNStats) else st
+    cached = getattr(x, '_cf_act', None)
+    if cached is not None and cached[0] == _act_key(x, cached[0][0]):
+        key = _act_key(y, cached[0][0])
+        if key is not None:
+            y._cf_act = (key, cached[1])
     return y
 
 
 class GNStats:
     """fp64 (sum, sumsq) partials of one NHWC tensor: [batch][channels/cpg][parts][2] (see cf_groupnorm_finalize).
-    Produced by a conv epilogue (attached to the conv's output tensor as `._cf_stats`) or by the stand-alone pass."""
+    Produced by a conv epilogue (attached to the conv's output tensor as `._cf_stats`) or by the stand-alone pass.
+    stamp: tensor_stamp() of the carrying tensor when the partials were attached (None: not attached to a tensor)."""
 
-    __slots__ = ('part', 'parts', 'cpg')
+    __slots__ = ('part', 'parts', 'cpg', 'stamp')
 
-    def __init__(self, part, parts, cpg):
-        self.part, self.parts, self.cpg = part, parts, cpg
+    def __init__(self, part, parts, cpg, stamp=None):
+        self.part, self.parts, self.cpg, self.stamp = part, parts, cpg, stamp
 
 
 def select_rows(x, sel):
     """x.index_select(0, sel) for an activation of the network (sel: int64 indices on x's device; an index may repeat): the images `sel`
     names, as a batch of their own.  The GroupNorm partials the producing conv attached (`._cf_stats`, [image][group][part][2]) travel with
     their images, so the consumers of the selection compute per image exactly what they compute for the whole batch; a parked range-scale
-    table is not carried -- act_scale() rebuilds it from those partials, per image."""
+    table is not carried -- act_scale() rebuilds it from those partials, per image.  The selection is a copy with partials of its own:
+    they describe x at the time of the call and stay valid when x is rewritten; partials that no longer describe x are not carried."""
     y = x.index_select(0, sel)
-    st = getattr(x, '_cf_stats', None)
+    st = live_stats(x)
     if st is not None:
-        y._cf_stats = GNStats(st.part.view(x.shape[0], -1).index_select(0, sel).reshape(-1), st.parts, st.cpg)
+        y._cf_stats = GNStats(st.part.view(x.shape[0], -1).index_select(0, sel).reshape(-1), st.parts, st.cpg, tensor_stamp(y))
     return y
 
 
@@ -239,51 +296,53 @@ def needs_act_scale(pw):
 
 
 _ACT_CELLS = {}
+_RETIRED_SCRATCH = []   # replaced _act_cells / _counters tensors: a captured graph keeps their raw address and runs atomics on it for as long as it is replayed
+
+
+def _scratch(table, device, n, floor):
+    """n zero-initialised int32 words per (device, stream).  A tensor too small for a later caller is replaced by a larger one and kept
+    allocated for the life of the process: the graphs that captured its address are not tracked."""
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    t = table.get(key)
+    if t is None or t.numel() < n:
+        if t is not None:
+            _RETIRED_SCRATCH.append(t)
+        t = table[key] = torch.zeros(max(n, floor), dtype=torch.int32, device=device)
+    return t
 
 
 def _act_cells(device, batch):
     """2 * batch zero-initialised words per (device, stream) for cf_act_scale_fused; every launch leaves them at zero."""
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-    t = _ACT_CELLS.get(key)
-    if t is None or t.numel() < 2 * batch:
-        t = torch.zeros(max(2 * batch, 256), dtype=torch.int32, device=device)
-        _ACT_CELLS[key] = t
-    return t
-
-
-def tensor_version(t):
-    """Version counter of a tensor, or None for inference tensors (torch.inference_mode), which do not track one -- reading
-    `._version` there raises.  Callers skip their version-keyed caches for None."""
-    return None if t.is_inference() else t._version
+    return _scratch(_ACT_CELLS, device, 2 * batch, 256)
 
 
 def act_scale(x, x2=None, growth=4.0):
     """(B, 2) float32 table (s_b, 1 / s_b): power-of-two scale that puts growth * max|x_b| into [2^13, 2^14) -- from the statistics
     partials the producing conv wrote (no pass over x; the bound is loose by a few bits, which is harmless) or, for tensors without
     them, from x itself; one launch (cf_act_scale_fused).  x2: the second half of a concatenated input -- the table then covers both.
-    Cached on the tensor under (growth, tensor version): one table serves every conv that reads the tensor, and an in-place write
-    (out= reuse, a user-held buffer) or another growth factor gets a fresh table; pairs are not cached."""
-    ver = tensor_version(x)   # None under torch.inference_mode(): inference tensors keep no version counter
-    if ver is None and getattr(x, '_cf_stats', None) is not None:
-        # ... but a tensor that carries its producer's statistics is a conv2d output of THIS forward (a fresh torch.empty per launch, never
-        # written again): keyed on the object itself, one table serves all its consumers -- without this every consumer relaunched the
-        # kernel under inference_mode (and baked the extra launches into captured graphs).  User-held inference tensors (no statistics
-        # attached) still compute their table on every call.
-        ver = 'inference'
-    if x2 is None and ver is not None:
+    Cached on the tensor under (growth, tensor_stamp(x)): one table serves every conv that reads the tensor; another growth factor, a
+    write by this library (conv2d(out=x), also through a slice of x or into x as the second member of a parked pair) and, outside
+    torch.inference_mode, a user's in-place write (x.mul_(), x.copy_()) get a fresh table -- and the partials such a write made stale are
+    not used for it: the table then comes from x itself.  Under inference_mode a USER's in-place write cannot be seen (inference tensors
+    keep no version counter): a tensor that carries statistics must not be written there except through this library."""
+    key = _act_key(x, growth)
+    # key is None for a user-held inference tensor (no version counter, no statistics attached): its table is computed on every call.  A
+    # tensor that carries its producer's statistics is a conv2d output: keyed on the object and the library's own write count, one table
+    # serves all its consumers under inference_mode too (else every consumer relaunched the kernel, and captured graphs baked that in).
+    if x2 is None and key is not None:
         cached = getattr(x, '_cf_act', None)
-        if cached is not None and cached[0] == (float(growth), ver):
+        if cached is not None and cached[0] == key:
             return cached[1]
-    if x2 is not None:      # a table groupnorm_tables([x, x2], act_growth=...) wrote in its own launch
+    if x2 is not None:      # a table groupnorm_tables([x, x2], act_growth=...) wrote in its own launch: valid while BOTH members are unwritten
         cached = getattr(x, '_cf_act_pair', None)
-        if cached is not None and cached[2]() is x2 and cached[0] == _act_key(x, growth) and cached[1] == _act_key(x2, growth):
+        if cached is not None and cached[2]() is x2 and cached[0] == key and cached[1] == _act_key(x2, growth):
             return cached[3]
     lib = L.load()
     B = x.shape[0]
     act = torch.empty(B, 2, dtype=torch.float32, device=x.device)
     cells = L.ptr(_act_cells(x.device, B), dtype=torch.int32)
-    st = getattr(x, '_cf_stats', None)
-    st2 = None if x2 is None else getattr(x2, '_cf_stats', None)
+    st = live_stats(x)
+    st2 = None if x2 is None else live_stats(x2)
     if x2 is not None and (st is None or st2 is None):
         # a half without statistics partials: two single tables combined on the host side of the stream (rare: every conv that feeds a
         # concatenation writes partials)
@@ -299,8 +358,8 @@ def act_scale(x, x2=None, growth=4.0):
             raise ValueError('act_scale: expected a dense tensor with a multiple of 4 elements per image')
         L.check(lib.cf_act_scale_fused(None, 0, None, 0, L.ptr(_f32(x)), x.numel() // B, B, float(growth), cells, L.ptr(act), L.stream_ptr()),
                 'cf_act_scale_fused')
-    if x2 is None and ver is not None:
-        x._cf_act = ((float(growth), ver), act)
+    if x2 is None and key is not None:
+        x._cf_act = (key, act)
     return act
 
 
@@ -554,12 +613,8 @@ def splitk_for(pw, ho, wo, cin, batch=1):
 
 
 def _counters(device, n):
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-    t = _COUNTERS.get(key)
-    if t is None or t.numel() < n:
-        t = torch.zeros(max(n, 4096), dtype=torch.int32, device=device)   # every split-K launch leaves its counters at zero again
-        _COUNTERS[key] = t
-    return t
+    """n zero-initialised tile counters per (device, stream); every split-K launch leaves its counters at zero again."""
+    return _scratch(_COUNTERS, device, n, 4096)
 
 
 def _roofline_kind(pw, io, stride, upsample, c0, in_nchw, out_nchw, out_pixels, split_k):
@@ -589,6 +644,13 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     returned tensor (`._cf_stats`), so a following groupnorm_tables() does not re-read the tensor.
     x, x2 and `out` (optional destination) may be channel slices `buf[..., a:b]` of wider NHWC buffers -- the dense-block
     pattern of RRDBNet, where torch.cat never materialises; res / sft_scale (= res2 of EPI_AXPY2) then share out's stride.
+    A caller-supplied destination (`out`, `img_out` -- the only destination arguments of this module that take an activation) loses what
+    earlier launches left on it: `_cf_stats`, `_cf_act` and `_cf_act_pair` are dropped from the object and from its `._base`, and the
+    write is counted against its storage (tensor_stamp), so state held by any other object on that memory -- the buffer behind a slice
+    under torch.inference_mode, the first member of a pair parked by groupnorm_tables -- is ignored from then on.  That happens once every
+    check of this function has passed: a call refused with ValueError / TypeError leaves the state alone.  Statistics attached here
+    carry the stamp of `out`; outside inference_mode a later in-place write by the caller (y.mul_(), y.copy_()) retires them, under
+    inference_mode such a write cannot be seen.
     EPI_LEAKY / EPI_AXPY / EPI_AXPY2 use sft_w as alpha (see cf_epilogue in the header).
     sft_w with EPI_SFT: a float, or a contiguous float32 tensor of B values on x's device -- one weight per image (cf_conv2d_sft_w); image b
     is then bitwise the launch on that image alone with sft_w = float(sft_w[b]).
@@ -652,6 +714,7 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     shape = (B, pw.cout, Ho, Wo) if out_nchw else (B, Ho, Wo, pw.cout)
     ldo = 0
     odt = torch.float32 if out_nchw else io      # (the NCHW network output stays fp32)
+    caller_out = out is not None or img_out is not None
     if img_out is not None:
         if not out_nchw or out is not None or tuple(img_out.shape) != (B, Ho, Wo, pw.cout) or img_out.device != dev:
             raise ValueError(f'img_out stands for the NCHW output: pass out_nchw=True, no out, and a uint8 {(B, Ho, Wo, 3)} image on {dev}')
@@ -713,6 +776,7 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
                 raise RuntimeError(f'cf_conv2d_workspace_bytes failed: {L.last_error()}')
             ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
             d.workspace, d.counters = L.ptr(ws), L.ptr(_counters(dev, tiles), dtype=torch.int32)
+    stats = None
     if emit_stats and not out_nchw and pw.cout % GN_GROUPS == 0 and pw.cout // GN_GROUPS >= 2:
         d.stats_cpg = pw.cout // GN_GROUPS
         parts = lib.cf_conv2d_stats_parts(ctypes.byref(d))
@@ -721,7 +785,11 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
         n_part = B * GN_GROUPS * parts * 2
         part = torch.empty(n_part, dtype=torch.float64, device=dev) if stats_into is None else stats_into.take(n_part, dev)
         d.stats_out = L.ptr(part, dtype=torch.float64)
-        out._cf_stats = GNStats(part, parts, d.stats_cpg)
+        stats = (part, parts, d.stats_cpg)
+    if caller_out:
+        _drop_state(out)      # every check of this function has passed: from here on `out` is written
+    if stats is not None:
+        out._cf_stats = GNStats(*stats, tensor_stamp(out))
 
     def launch():
         if w_img is not None:
@@ -776,7 +844,9 @@ def groupnorm_tables(xs, gamma, beta, eps=GN_EPS, groups=GN_GROUPS, act_growth=N
     parameters into per-(b,c) scale / shift tables (B, sum Ci), to be applied by a conv prologue.
 
     Tensors that carry epilogue statistics (`._cf_stats`, see conv2d(emit_stats=True)) are not read again; the others
-    go through the stand-alone statistics pass.
+    go through the stand-alone statistics pass -- and so do tensors whose statistics no longer describe them (live_stats): written since
+    by this library (conv2d(out=t), also through a slice of t) or, outside torch.inference_mode, in place by the caller (t.mul_(),
+    t.copy_()).  Under inference_mode a caller's in-place write cannot be seen: there, write such tensors through this library only.
     act_growth: the caller will also ask act_scale(*xs, growth=act_growth) (the block input that feeds both norm1 and the 1x1 skip
     convolution): when every tensor carries statistics the SAME launch writes that table (cf_groupnorm_finalize2) and parks it where
     act_scale finds it -- bitwise the table of the separate launch."""
@@ -797,7 +867,7 @@ def groupnorm_tables(xs, gamma, beta, eps=GN_EPS, groups=GN_GROUPS, act_growth=N
         c = t.shape[3]
         if c % cpg:
             raise ValueError('concat boundary splits a group')
-        st = getattr(t, '_cf_stats', None)
+        st = live_stats(t)
         if st is None or cpg % st.cpg:
             # ~128 KB of input per block, enough blocks to cover 256 CUs several times, at most 256 partials per group
             nblk = max(1, min(256, (hw * c * 4 + (1 << 17) - 1) >> 17))
@@ -834,10 +904,14 @@ def groupnorm_tables(xs, gamma, beta, eps=GN_EPS, groups=GN_GROUPS, act_growth=N
 
 
 def _act_key(x, growth):
-    ver = tensor_version(x)
-    if ver is None and getattr(x, '_cf_stats', None) is not None:
-        ver = 'inference'     # (see act_scale: a conv output of this forward)
-    return None if ver is None else (float(growth), ver)
+    """What a range-scale table of x is cached under: the growth factor and x's stamp.  None: x shows no writes at all (an inference tensor
+    without statistics of this library), so nothing is cached for it."""
+    ver, epoch = tensor_stamp(x)
+    if ver is None:
+        if live_stats(x) is None:
+            return None
+        ver = 'inference'     # (see act_scale: a conv output, written through this library only)
+    return (float(growth), ver, epoch)
 
 
 def _park_act(xs, growth, act):
