@@ -1,4 +1,5 @@
-"""Python surface of the reference's two bundled CUDA extensions, on the HIP C ABI (inference only).
+"""Python surface of two of the reference's three bundled CUDA extensions, on the HIP C ABI (inference only); the third, basicsr/ops/dcn,
+is codeformer_amd/dcn.py.
 
 Mirrors basicsr/ops/fused_act/fused_act.py:74-89 (`FusedLeakyReLU`, `fused_leaky_relu`) and
 basicsr/ops/upfirdn2d/upfirdn2d.py:147-154 (`upfirdn2d`).  Neither op is used by CodeFormer.forward;

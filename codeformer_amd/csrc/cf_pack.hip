@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "cf_conv_parts.h"
+#include "cf_dcn.h"
 
 namespace {
 
@@ -412,4 +413,21 @@ extern "C" int cf_pack_conv_weight_winograd42_up(const float* w, int cout, int c
   CF_REQUIRE(cf_wf43_k32(cout, cin), "cf_pack_conv_weight_winograd42_up: the sub-pixel form runs on 32-channel slabs (CF_F43_WIDE=k16 is set)");
   // fp32 words: 4 phases x 25 positions
   return pack<ENC_F32>(name, F42Value{{w, cout, cin, 9}}, Frag16<false>{32, cout / 16, cin / 32}, packed, 100L * cin * cout, stream);
+}
+
+// Deformable convolution (cf_dcn.hip): the fp32 rows of each group, [group][tap][cin_g/16][cout_pad_g][16] with cout_pad_g whole 64-wide
+// channel tiles of the group (cf_dcn_cout_pad); any tap count up to CF_DCN_MAX_TAPS.
+extern "C" int cf_pack_deform_conv_weight(const float* w, int cout, int cin, int taps, int groups, float* packed, cf_stream_t stream) {
+  const char* name = "cf_pack_deform_conv_weight";
+  CF_REQUIRE(w && packed, "%s: null pointer", name);
+  CF_REQUIRE(cout > 0 && cin > 0 && groups > 0 && cin % groups == 0 && cout % groups == 0, "%s: groups %d must divide cin %d and cout %d", name, groups, cin, cout);
+  CF_REQUIRE((cin / groups) % CF_BK == 0, "%s: cin per group %d must be a multiple of %d", name, cin / groups, CF_BK);
+  CF_REQUIRE(taps >= 1 && taps <= CF_DCN_MAX_TAPS, "%s: taps must be in [1, %d] (got %d)", name, CF_DCN_MAX_TAPS, taps);
+  const int cout_g = cout / groups, cin_g = cin / groups, cout_pad_g = cf_dcn_cout_pad(cout_g);
+  const long words = (long)taps * cin_g * cout_pad_g;
+  for (int g = 0; g < groups; ++g) {
+    const Weight wg{w + (long)g * cout_g * cin_g * taps, cout_g, cin_g, taps};
+    if (const int e = pack<ENC_F32>(name, TapValue{wg, 1.f}, Rows<CF_BK, 1>{cout_pad_g, cin_g / CF_BK}, packed + g * words, words, stream)) return e;
+  }
+  return CF_OK;
 }

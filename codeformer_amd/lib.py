@@ -99,7 +99,10 @@ SIGNATURES = {
     'cf_fused_bias_act': (_I, [_P, _P, _L, _I, _I, _F, _F, _P, _P]),
     'cf_fused_bias_act_ex': (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _F, _F, _I, _P, _P]),
     'cf_upfirdn2d': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    'cf_warp_affine_u8': (_I, [_P, _L, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'cf_deform_conv2d_packed_elems': (_L, [_I, _I, _I, _I]),
+    'cf_pack_deform_conv_weight': (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    'cf_deform_conv2d': (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 17 + [_P]),
+    'cf_warp_affine_u8':(_I, [_P, _L, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'cf_warp_affine_f32': (_I, [_P, _I, _I, ctypes.POINTER(ctypes.c_double), _P, _I, _I, _I, _I, _P]),
     'cf_erode_f32': (_I, [_P, _P, _P, _I, _I, _I, _P]),
     'cf_gaussian_blur_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),

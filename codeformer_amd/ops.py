@@ -1112,6 +1112,123 @@ def upfirdn2d(x, kernel, up=1, down=1, pad=(0, 0)):
     return y
 
 
+# ---- deformable convolution (cf_dcn.hip; codeformer_amd/dcn.py is the basicsr.ops.dcn surface on top) --------------------------------
+DCN_MAX_TAPS = 49   # CF_DCN_MAX_TAPS of cf_dcn.h
+
+
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def deform_conv2d_route(x_shape, weight_shape, groups=1, deformable_groups=1):
+    """'mfma' | 'general': the kernel deform_conv2d runs for an input (B, Cin, H, W) and a weight (Cout, Cin/G, kh, kw).  The MFMA route
+    takes every shape in which a float4 of channels lies in one deformable group and a 16-channel K slab in one group:
+    (Cin/DG) % 4 == 0, (Cin/G) % 16 == 0, kh*kw <= 49, Cin < 65536 and an image (H*W*Cin floats) below 2^31 bytes (cf_dcn_mfma_covers of cf_dcn.h);
+    stride, padding and dilation do not matter."""
+    cin, (kh, kw) = int(x_shape[1]), (int(weight_shape[2]), int(weight_shape[3]))
+    ok = cin % groups == 0 and cin % deformable_groups == 0 and (cin // deformable_groups) % 4 == 0 and (cin // groups) % 16 == 0 and \
+        kh * kw <= DCN_MAX_TAPS and cin < 65536 and int(x_shape[2]) * int(x_shape[3]) * cin * 4 < 2 ** 31
+    return 'mfma' if ok else 'general'
+
+
+def deform_conv2d_out_hw(h, w, kh, kw, stride, padding, dilation):
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    return (h + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1, (w + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+
+
+def deform_conv2d_check(x, offset, weight, mask, bias, stride, padding, dilation, groups, deformable_groups):
+    """The shape and dtype rules of the op, for GPU and CPU tensors alike: TypeError for anything but float32, ValueError for a shape that
+    does not fit.  Returns (Ho, Wo)."""
+    for t, what in ((x, 'input'), (offset, 'offset'), (weight, 'weight'), (mask, 'mask'), (bias, 'bias')):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f'deform_conv2d: {what} is {t.dtype}; the op is float32 only')
+    if x.dim() != 4 or weight.dim() != 4 or offset.dim() != 4 or (mask is not None and mask.dim() != 4):
+        raise ValueError('deform_conv2d: input, offset, mask and weight are 4-D tensors')
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0:
+        raise ValueError('deform_conv2d: stride and dilation must be positive, padding non-negative')
+    B, cin, H, W = x.shape
+    cout, cin_g, kh, kw = weight.shape
+    G, DG = int(groups), int(deformable_groups)
+    if G < 1 or cin % G or cout % G or cin_g != cin // G:
+        raise ValueError(f'deform_conv2d: groups {G} must divide cin {cin} and cout {cout}, and the weight hold cin/groups = {cin // max(G, 1)} input channels (it has {cin_g})')
+    if DG < 1 or cin % DG:
+        raise ValueError(f'deform_conv2d: deformable_groups {DG} must divide cin {cin}')
+    Ho, Wo = deform_conv2d_out_hw(H, W, kh, kw, stride, padding, dilation)
+    if H + 2 * ph < dh * (kh - 1) + 1 or W + 2 * pw < dw * (kw - 1) + 1:
+        raise ValueError(f'deform_conv2d: the input ({H}x{W}) is smaller than the dilated kernel')
+    if tuple(offset.shape) != (B, DG * 2 * kh * kw, Ho, Wo):
+        raise ValueError(f'deform_conv2d: offset shape {tuple(offset.shape)}, expected {(B, DG * 2 * kh * kw, Ho, Wo)}')
+    if mask is not None and tuple(mask.shape) != (B, DG * kh * kw, Ho, Wo):
+        raise ValueError(f'deform_conv2d: mask shape {tuple(mask.shape)}, expected {(B, DG * kh * kw, Ho, Wo)}')
+    if bias is not None and tuple(bias.shape) != (cout,):
+        raise ValueError(f'deform_conv2d: bias shape {tuple(bias.shape)}, expected {(cout,)}')
+    return Ho, Wo
+
+
+def _dcn_packed(weight, groups):
+    """The MFMA route's packing of `weight`, kept on the tensor object until its version, storage or device moves (as the arch modules keep
+    theirs: an edit of `weight.data` in place is not versioned -- delete `weight._cf_dcn` after one).  Inference tensors keep no version
+    and are packed per call."""
+    ver = tensor_version(weight)
+    key = (weight.data_ptr(), ver, str(weight.device), int(groups))
+    ent = weight.__dict__.get('_cf_dcn') if ver is not None else None
+    if ent is not None and ent[0] == key:
+        return ent[1]
+    lib = L.load()
+    cout, cin_g, kh, kw = weight.shape
+    w = weight.detach().contiguous()
+    n = lib.cf_deform_conv2d_packed_elems(cout, cin_g * groups, kh * kw, groups)
+    if n <= 0:
+        raise RuntimeError(f'cf_deform_conv2d_packed_elems failed ({n})')
+    packed = torch.empty(n, dtype=torch.float32, device=w.device)
+    L.check(lib.cf_pack_deform_conv_weight(L.ptr(w), cout, cin_g * groups, kh * kw, groups, L.ptr(packed), L.stream_ptr()), 'cf_pack_deform_conv_weight')
+    if ver is not None:
+        weight._cf_dcn = (key, packed)
+    return packed
+
+
+def _is_channels_last(x):
+    """Dense (B,C,H,W) tensor whose memory is [b][h][w][c] (torch.channels_last), 16-byte aligned: read in place as NHWC."""
+    B, C, H, W = x.shape
+    return x.stride() == (H * W * C, 1, W * C, C) and x.data_ptr() % 16 == 0
+
+
+def deform_conv2d(x, offset, weight, mask=None, bias=None, stride=1, padding=0, dilation=1, groups=1, deformable_groups=1, route=None):
+    """Deformable convolution, forward, float32: x (B,Cin,H,W), offset (B,DG*2*kh*kw,Ho,Wo), weight (Cout,Cin/G,kh,kw), mask (B,DG*kh*kw,Ho,Wo)
+    or None (the plain op: mask == 1), bias (Cout) or None -> (B,Cout,Ho,Wo); the definition stands in include/codeformer_hip.h
+    (cf_deform_conv2d).  stride / padding / dilation: an int or a (vertical, horizontal) pair.
+    A torch.channels_last x is read in place; any other x is brought to channels-last by to_nhwc for the MFMA route and read as NCHW by
+    the general one.  route: None (deform_conv2d_route decides), 'general' (any shape) or 'mfma' (ValueError where it does not cover)."""
+    Ho, Wo = deform_conv2d_check(x, offset, weight, mask, bias, stride, padding, dilation, groups, deformable_groups)
+    lib = L.load()
+    auto = deform_conv2d_route(x.shape, weight.shape, groups, deformable_groups)
+    if route not in (None, 'mfma', 'general'):
+        raise ValueError(f"deform_conv2d: route {route!r} (None, 'mfma' or 'general')")
+    if route == 'mfma' and auto != 'mfma':
+        raise ValueError('deform_conv2d: the mfma route needs (Cin/DG) % 4 == 0, (Cin/G) % 16 == 0 and kh*kw <= 49')
+    route = route or auto
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    B, cin, H, W = x.shape
+    cout, _, kh, kw = weight.shape
+    x = x.detach()
+    if _is_channels_last(x):
+        xin, nhwc = x.permute(0, 2, 3, 1), 1
+    elif route == 'mfma':
+        xin, nhwc = to_nhwc(x), 1
+    else:
+        xin, nhwc = x.contiguous(), 0
+    w = _dcn_packed(weight, groups) if route == 'mfma' else weight.detach().contiguous()
+    offset = offset.detach().contiguous()
+    mask = None if mask is None else mask.detach().contiguous()
+    bias = None if bias is None else bias.detach().contiguous()
+    out = torch.empty(B, cout, Ho, Wo, dtype=torch.float32, device=x.device)
+    L.check(lib.cf_deform_conv2d(L.ptr(xin), L.ptr(offset), L.ptr(mask), L.ptr(w), L.ptr(bias), L.ptr(out), B, cin, H, W, cout, kh, kw,
+                                 sh, sw, ph, pw, dh, dw, int(groups), int(deformable_groups), nhwc, int(route == 'mfma'), L.stream_ptr()),
+            'cf_deform_conv2d')
+    return out
+
+
 # ---- alignment warp / paste-back primitives (cf_paste.hip) -- see codeformer_amd/facelib/paste.py for the orchestration --------------
 def _c6(m):
     """6 doubles in host memory for the ctypes call (a 2x3 destination->source matrix)."""

@@ -445,6 +445,29 @@ int cf_upfirdn2d(const float* x, int nplanes, int in_h, int in_w, const float* k
                  int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, float* y,
                  cf_stream_t stream);
 
+/* ---- deformable convolution, forward (basicsr/ops/dcn; no registered arch uses it) ------------------------------------------
+ * One definition for the modulated (v2) and the plain (v1: mask == NULL, bias == NULL) op, K = kh*kw, tap k = i*kw + j, d = c / (cin /
+ * deform_groups) the deformable group of input channel c:
+ *   out[b][o][y][x] = bias[o] + sum_{c in the group of o, k} weight[o][c_local][i][j] * mask[b][d*K + k][y][x] * val
+ *   val = bilinear sample of x[b][c], zeros outside the image, at
+ *     h = (float)(y*stride_h - pad_h + i*dil_h) + offset[b][(d*K + k)*2][y][x],  w likewise with offset channel (d*K + k)*2 + 1;
+ *   val = 0 unless h > -1 && w > -1 && h < hin && w < win on those fp32 values (so a NaN offset samples nothing).
+ * hout = (hin + 2 pad_h - (dil_h (kh-1) + 1)) / stride_h + 1, wout likewise.  offset [batch][deform_groups*2*K][hout][wout], mask
+ * [batch][deform_groups*K][hout][wout], out [batch][cout][hout][wout], all fp32.
+ * route 1: the bilinear gather fused into an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32 operands).  x is channels-last
+ *   [batch][hin][win][cin] (x_nhwc = 1), weight is packed by cf_pack_deform_conv_weight ([group][tap][cin_g/16][cout_pad_g][16] floats,
+ *   cf_deform_conv2d_packed_elems of them); needs (cin/deform_groups) % 4 == 0, (cin/groups) % 16 == 0 and kh*kw <= 49 (and cin < 65536,
+ *   one image below 2^31 bytes).  The image is read through a buffer descriptor of its own size: a corner that fails its bounds check
+ *   gets an offset beyond it, for which the hardware makes no memory access.
+ * route 0: one thread per output element, any shape.  weight is the plain [cout][cin/groups][kh][kw] tensor; x is channels-last
+ *   (x_nhwc = 1) or [batch][cin][hin][win] (x_nhwc = 0).
+ * Every argument is checked before anything is launched. */
+int64_t cf_deform_conv2d_packed_elems(int cout, int cin, int taps, int groups); /* -1: groups does not divide the channels */
+int cf_pack_deform_conv_weight(const float* w, int cout, int cin, int taps, int groups, float* packed, cf_stream_t stream);
+int cf_deform_conv2d(const float* x, const float* offset, const float* mask, const float* weight, const float* bias, float* out,
+                     int batch, int cin, int hin, int win, int cout, int kh, int kw, int stride_h, int stride_w, int pad_h,
+                     int pad_w, int dil_h, int dil_w, int groups, int deform_groups, int x_nhwc, int route, cf_stream_t stream);
+
 /* ---- alignment warp and paste-back of the whole-image / video path ----------------------------------------------------------
  * Replaces the OpenCV calls of facelib/utils/face_restoration_helper.py: cv2.warpAffine of align_warp_face (:343-344) and of
  * paste_faces_to_input_image (:400, :428, :479), cv2.erode (:430-431, :447), cv2.GaussianBlur (:449), np.sum (:433), the soft-mask
