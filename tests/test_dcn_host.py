@@ -89,6 +89,60 @@ def test_routes(name):
     assert ops.deform_conv2d_route((c[0], c[1], c[3], c[4]), (c[2], c[1] // c[9], *c[5]), c[9], c[10]) == c[12]
 
 
+def test_which_cases_keep_a_sample_across_slabs():
+    """The MFMA kernel's reuse branch by dcn_ref.reuse_counts, the model of its rule: the four reuse cases take it, the five first cases never do --
+    an edit of the table cannot lose the coverage unnoticed."""
+    mfma = [n for n, c in dcn_ref.CASES.items() if c[12] == 'mfma']
+    assert set(dcn_ref.REUSE_CASES) | set(dcn_ref.NO_REUSE_CASES) <= set(mfma)
+    counts = {n: dcn_ref.case_reuse_counts(n) for n in mfma}
+    print('dcn reuse (reused, gathers):', counts)
+    assert {n: counts[n] for n in dcn_ref.NO_REUSE_CASES} == {'mod_dg4': (0, 72), 'v1_s2d2': (0, 36), 'groups': (0, 72), 'k1': (0, 4), 'tiles': (0, 36)}
+    for n in dcn_ref.REUSE_CASES:
+        assert 0 < counts[n][0] < counts[n][1], n
+    assert counts['reuse'] == (36, 72)
+    # reuse24: of a pixel's four threads some reuse at a slab and some resample (channels 16..23 against 24..31)
+    cin, dg = dcn_ref.CASES['reuse24'][1], dcn_ref.CASES['reuse24'][10]
+    d_of = [[(4 * k4 + 16 * slab) // (cin // dg) for slab in range(cin // 16)] for k4 in range(4)]
+    assert d_of == [[0, 0, 1], [0, 0, 1], [0, 1, 1], [0, 1, 1]]
+    for n in set(dcn_ref.PIXELS) & set(dcn_ref.REUSE_CASES):                 # the property cases put an entry where the sample is a kept one
+        c = dcn_ref.CASES[n]
+        assert any(e[1] in dcn_ref.reused_channels(c[1], c[9], c[10]) for e in dcn_ref.PIXELS[n]), n
+    # the modules at their default deformable_groups = 1 take it too, the benchmark's shape (64 channels, 8 deformable groups) does not
+    assert dcn_ref.reuse_counts(64, 1, 1, 9) == (108, 144) and dcn_ref.reuse_counts(32, 1, 1, 9) == (36, 72) and dcn_ref.reuse_counts(64, 1, 8, 9)[0] == 0
+    # the step counts of the pipeline cases: taps x slabs
+    steps = {n: c[5][0] * c[5][1] * (c[1] // c[9] // 16) for n, c in dcn_ref.CASES.items()}
+    assert steps['steps2'] == 2 and steps['steps3'] == 3 and steps['k1'] == 1 and steps['k7'] == 49
+    # gtiles: two N tiles per group, the second 16 channels wide; straddle(2): a deformable group spans a group boundary and the reverse
+    c = dcn_ref.CASES['gtiles']
+    assert c[9] == 2 and c[2] // c[9] == 64 + 16 and c[0] == 3 and c[3] % 4 and c[4] % 16
+    for n in ('straddle', 'straddle2'):
+        c = dcn_ref.CASES[n]
+        assert (c[1] // c[9]) % (c[1] // c[10]) and (c[1] // c[10]) % (c[1] // c[9])
+
+
+@pytest.mark.parametrize('name', list(dcn_ref.PIXELS))
+def test_one_pixel_and_nan_pixel_on_the_host_formula(name):
+    """The property cases of the GPU file on the float32 host formula: one entry of x reaches only the outputs whose samples read it, and a NaN
+    entry makes exactly those NaN."""
+    for which in range(3):
+        inp = dcn_ref.one_pixel_case(name, which)[0]
+        dcn_ref.check_one_pixel(_host(inp).numpy(), name, which, label='host ')
+    c = dcn_ref.CASES[name]
+    cpdg, cin_g = c[1] // c[10], c[1] // c[9]
+    assert (dcn_ref.PIXELS[name][2][1] + 1) % cpdg == 0                         # the last channel of a deformable group
+    if c[9] > 1:                                                              # ... of one that the groups cut
+        d = dcn_ref.PIXELS[name][2][1] // cpdg
+        assert d * cpdg // cin_g != ((d + 1) * cpdg - 1) // cin_g
+    inp, val, _ = dcn_ref.nan_pixel_case(name)
+    dcn_ref.check_nan_pixel(_host(inp).numpy(), name, label='host ')
+    nan = np.isnan(val)
+    g = dcn_ref.PIXELS[name][0][1] // cin_g                                   # every channel of the entry's group alike, no other channel
+    cout_g = c[2] // c[9]
+    assert (nan[:, g * cout_g:(g + 1) * cout_g] == nan[:, g * cout_g:g * cout_g + 1]).all() and nan.sum() == cout_g * nan[:, g * cout_g].sum()
+    if name == 'reuse24':
+        assert abs(nan.mean() - 0.157) < 0.0005
+
+
 def test_route_rule():
     r = ops.deform_conv2d_route
     assert r((1, 64, 8, 8), (64, 64, 3, 3), 1, 8) == 'mfma' and r((1, 64, 8, 8), (64, 64, 7, 7), 1, 16) == 'mfma'
