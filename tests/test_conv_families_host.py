@@ -29,11 +29,12 @@ def cc():
 LARGEST = ('d', 'f', 'g', 'u1')        # most pixels, most input channels, most output channels, folded
 ALL_KEYS = ('a', 'b', 'c', 'd', 'e', 'f', 'g', 'u1', 'u2')
 GATE_FAMILIES = ('mixed_cout', 'mixed_cin', 'mixed_cin_act', 'cancel_pairs', 'dc_plus_ripple', 'swish_leaky_edges', 'swish_leaky_edges_sft')
-PROLOGUE_ONLY = ('mixed_cin', 'swish_leaky_edges', 'swish_leaky_edges_sft')      # families that ARE their prologue: not on upsampling shapes
+PROLOGUE_ONLY = ('mixed_cin', 'swish_leaky_edges', 'swish_leaky_edges_sft', 'solo_cin')      # families that ARE their prologue: not on upsampling shapes
+SOLO_FAMILIES = ('solo_cin', 'solo_cin_act')
 
 
 def test_families_and_shapes_are_the_issue_s(cc):
-    assert cc.GATE_FAMILIES == GATE_FAMILIES
+    assert cc.GATE_FAMILIES == GATE_FAMILIES and cc.SOLO_FAMILIES == SOLO_FAMILIES
     assert {k: v[:5] for k, v in cc.SHAPES.items()} == {'a': (1, 16, 16, 16, 64), 'b': (2, 16, 32, 32, 64), 'c': (2, 32, 32, 64, 128), 'd': (3, 32, 48, 48, 128),
                                                         'e': (1, 16, 16, 256, 64), 'f': (1, 16, 16, 512, 128), 'g': (1, 48, 32, 192, 192),
                                                         'u1': (2, 16, 16, 32, 128), 'u2': (1, 16, 16, 64, 64)}
@@ -48,7 +49,7 @@ def _schemes(cc, key):
     return list(seen.values())
 
 
-@pytest.mark.parametrize('family,key', [(f, k) for f in GATE_FAMILIES + ('onehot_pixels',) for k in ALL_KEYS if not (k.startswith('u') and f in PROLOGUE_ONLY)])
+@pytest.mark.parametrize('family,key', [(f, k) for f in GATE_FAMILIES + SOLO_FAMILIES + ('onehot_pixels',) for k in ALL_KEYS if not (k.startswith('u') and f in PROLOGUE_ONLY)])
 def test_emulation_within_half_of_the_gate(cc, family, key):
     assert not (cc.SHAPES[key][6] and family in PROLOGUE_ONLY)            # (upsampling shapes take no prologue)
     for cname, code, route in _schemes(cc, key):
@@ -88,7 +89,7 @@ def test_int_coded_preconditions_and_exact_emulation(cc, key):
 
 @pytest.mark.parametrize('key', ('b', 'c', 'u1'))
 def test_reference_is_conv_case_reference_and_both_transforms_are_the_convolution(cc, key):
-    for fam in GATE_FAMILIES + ('onehot_pixels', 'int_coded'):
+    for fam in GATE_FAMILIES + SOLO_FAMILIES + ('onehot_pixels', 'int_coded'):
         if cc.SHAPES[key][6] and fam in PROLOGUE_ONLY:
             continue
         d, ref = cc.prepared(fam, key)
@@ -178,6 +179,77 @@ def test_hard_families_are_hard(cc):
     d = cc.family('swish_leaky_edges', 'c')
     assert {float(v) for v in d['x'].flatten()[:4096]} == {float(v) for v in cc.EDGE_VALUES} and bool((d['x'] == 0).logical_and(torch.signbit(d['x'])).any())
     assert float(d['res'].abs().mean()) > 300 * float(cc.reference(d)['pre'].abs().mean())
+
+
+@pytest.mark.parametrize('key', ALL_KEYS)
+def test_solo_families_read_small_and_large_channels_each_alone_in_its_sum(cc, key):
+    B, H, W, cin, cout, _, up = cc.SHAPES[key]
+    p = cc.solo_perm(cin, cout)
+    read = sorted(set(p.tolist()))
+    assert 0 in read and cin - 1 in read and {c // 16 for c in read} == set(range(cin // 16)), (key, read)
+    assert cout >= cin or len(read) == cout                                    # (fewer outputs than inputs: no channel read twice)
+    for fam in SOLO_FAMILIES:
+        if up and fam in PROLOGUE_ONLY:
+            continue
+        d = cc.family(fam, key)
+        live = cc.live_channels(d)
+        assert torch.equal(live.nonzero()[:, 1], p) and bool((live.sum(1) == 1).all())
+        assert bool((d['w'][live] != 0).all()) and not bool((d['w'][live].abs() == 1).any()) and d['epi'] == cc.EPI_NONE and bool((d['b'] != 0).all())
+        e = cc.solo_exponents(fam, cin)
+        assert float(e[read].min()) == float(e.min()) and float(e[read].max()) == float(e.max()) and float(e.max() - e.min()) == 2 * cc.SOLO_EXP
+        assert d['pro'] == (cc.PRO_AFFINE if fam == 'solo_cin' else cc.PRO_NONE)
+        s = cc.act_scale_of(d)
+        assert bool((s == 1).all()) if fam == 'solo_cin' else bool((s < 2.0 ** -4).all())       # (the range scale brings 2^16 N(0, 1) below 2^12)
+        hw = cc.emulate(d, 'd32', 0)
+        assert bool(torch.isfinite(hw).all())
+        lo_sub, hi_sub = cc.solo_kinds(d)
+        print(f'{fam} {key}: read channels with subnormal lo halves {lo_sub.sum(1).tolist()}, with subnormal hi halves {hi_sub.sum(1).tolist()} (per image)')
+        assert bool((lo_sub.sum(1) >= 2).all()) and bool((hi_sub.sum(1) >= 2).all()), (fam, key)
+        # under the prologue no operand leaves the IEEE half range: the largest channel is normal and finite as a half
+        top = (d['x'] * d['sc'][:, None, None, :] + d['sh'][:, None, None, :] if fam == 'solo_cin' else d['x'] * s.float()[:, None, None, None]).abs().max()
+        assert 2.0 ** 10 <= float(top) < 2.0 ** 14, (fam, key, float(top))
+
+
+@pytest.mark.parametrize('key', ALL_KEYS)
+def test_dropped_small_lo_halves_exceed_the_solo_gate_and_no_other(cc, key):
+    """conv_check.drop_small_lo: the lo half of an activation (of V on the Winograd routes) zeroed where it is a subnormal half, |a| < 2^-3 under the
+    range scale.  Every split-half scheme of every shape the GPU test launches, cin 256 and 512 included: the solo families' emulation then stands at
+    >= 10 times their gate.  At shape b every older gate family's ratio stays where it was (within 0.005 of the gate, and below 0.5): with one gate per
+    output element a small input channel hides behind the large ones of the same sum -- the gap the solo families close."""
+    half2 = [(cname, code, route) for cname, code, route in _schemes(cc, key) if cc.scheme_of(route, code)[1] == 'half2']
+    assert half2
+    for fam in SOLO_FAMILIES:
+        if cc.SHAPES[key][6] and fam in PROLOGUE_ONLY:
+            continue
+        d, ref = cc.prepared(fam, key)
+        for cname, code, route in half2:
+            r, err = cc.ratio(cc.emulate(d, route, code, cc.drop_small_lo), ref, cc.gate(fam, key, route, code))
+            print(f'{fam} {key} {route} {cname}: small lo halves dropped {r:.1f} of the gate (unedited {cc.emulated(fam, key, route, code)[0]:.3f})')
+            assert r >= 10.0, (fam, key, route, cname, r)
+            r_all, _ = cc.ratio(cc.emulate(d, route, code, cc.drop_every_lo), ref, cc.gate(fam, key, route, code))
+            assert r_all >= r, (fam, key, route, cname, r_all, r)              # (every activation lo half dropped: no less)
+    if key == 'e':      # the second gap, pinned: at cin 256 an evaluation with NO activation lo half at all stays inside every older family's gate
+        for fam in GATE_FAMILIES:
+            d, ref = cc.prepared(fam, key)
+            for cname, code, route in half2:
+                r, _ = cc.ratio(cc.emulate(d, route, code, cc.drop_every_lo), ref, cc.gate(fam, key, route, code))
+                print(f'{fam} {key} {route} {cname}: every activation lo half dropped {r:.3f} of the gate')
+                assert r < 1.0, (fam, route, r)
+    if key == 'b':
+        assert {route for _, _, route in half2} == {'dsplit', 'w23_h4', 'w43_8'}
+        for fam in GATE_FAMILIES:
+            d, ref = cc.prepared(fam, key)
+            for cname, code, route in half2:
+                r0 = cc.emulated(fam, key, route, code)[0]
+                r, _ = cc.ratio(cc.emulate(d, route, code, cc.drop_small_lo), ref, cc.gate(fam, key, route, code))
+                print(f'{fam} {key} {route} {cname}: unedited {r0:.4f}, small lo halves dropped {r:.4f} of the gate')
+                assert abs(r - r0) <= 0.005 and r <= 0.5, (fam, route, r0, r)
+
+
+def test_the_activation_hook_defaults_to_the_unedited_split(cc):
+    d, _ = cc.prepared('solo_cin_act', 'b')
+    for cname, code, route in _schemes(cc, 'b'):
+        assert cc.bits_equal(cc.emulate(d, route, code), cc.emulate(d, route, code, lambda a, hi, lo: (hi, lo))), route
 
 
 EXPECTED_FORMS = {

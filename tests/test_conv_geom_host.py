@@ -242,6 +242,40 @@ def test_emulation_within_half_of_the_gate(gc, key):
     assert n >= 4
 
 
+SOLO_FAMILIES = ('solo_cin', 'solo_cin_act')
+SOLO_ROUTES = ('s2_d32', 's2_dsplit', 'c1_d32', 'c1_dsplit')
+
+
+@pytest.mark.parametrize('route', SOLO_ROUTES)
+def test_solo_emulation_within_half_of_the_gate_and_the_dropped_lo_halves_far_above_it(gc, route):
+    """Every case and form the GPU test launches.  On the split-half routes the emulation with the small activations' lo halves dropped
+    (conv_check.drop_small_lo) exceeds the gate at least 10 times."""
+    assert gc.SOLO_FAMILIES == SOLO_FAMILIES and gc.SOLO_ROUTES == SOLO_ROUTES and not set(SOLO_FAMILIES) & set(gc.GATE_FAMILIES)
+    n = 0
+    for key in gc.cases_of(route):
+        g = gc.CASES[key]
+        for _, code, rt, form in gc.launches(key, (route,)):
+            for fam in SOLO_FAMILIES:
+                pr = gc.prepared(fam, key, route, form)
+                assert (pr is None) == (fam == 'solo_cin' and route == 's2_dsplit'), (fam, key, route)      # (the split-half stride-2 form refuses affine prologues)
+                if pr is None:
+                    continue
+                d, ref, tol = pr
+                live = gc.cc.live_channels(d)
+                assert bool((live.sum(1) == 1).all()) and torch.equal(live.nonzero()[:, 1], gc.cc.solo_perm(g.cin, g.cout)) and bool(live.any(0).all())
+                lo_sub, hi_sub = gc.cc.solo_kinds(d)
+                assert bool((lo_sub.sum(1) >= 2).all()) and bool((hi_sub.sum(1) >= 2).all()), (fam, key)
+                r, err = gc.emulated(fam, key, route, form)
+                print(f'{fam} {key} {route} {form}: emulation max|d| {err:.3e} = {r:.3f} of the gate')
+                assert r <= 0.5, (fam, key, route, form, r, err)
+                if route in gc.SPLIT_ROUTES:
+                    rd, _ = gc.ratio(gc.emulate(d, g, route, gc.cc.drop_small_lo), ref, tol)
+                    print(f'{fam} {key} {route} {form}: small lo halves dropped {rd:.1f} of the gate')
+                    assert rd >= 10.0, (fam, key, route, form, rd)
+                n += 1
+    assert n >= 3
+
+
 def gc_taps(gc, key):
     g = gc.CASES[key]
     return (0,) if g.taps == 1 else (0, 4, 8) if key in gc.BIG else tuple(range(9))

@@ -6,7 +6,7 @@ condition here is a condition on the reference.  Weights are packed with the exp
 which kernel form (d32, dsplit, w23_f32, w23_h4, w23_h8, w43_8, w43_16k32, w43_16k16, w43_up), and the union of the cases below reaches all nine.
 Nothing is larger than 48x48 pixels, batch 3 or 512 channels.
 
-Measured on an MI355X, the whole file 11.0 s (90 cases; no case above 0.5 s).  Largest |error| / gate per family
+Measured on an MI355X, the whole file 13.8 s (109 cases; no case above 0.5 s, the slowest 0.46 s: solo_cin_act on dsplit).  Largest |error| / gate per family
 and route, kernel | CPU emulation (test_family_within_the_gate prints every single ratio; onehot_pixels: the kernel's, d32 being the folded form):
                           d32             dsplit          w23_f32         w23_h4          w23_h8          w43_8           w43_16k32       w43_16k16       w43_up
     mixed_cout            0.0301 | 0.0246 0.1806 | 0.2101 0.0094 | 0.0101 0.1301 | 0.1301 0.0795 | 0.0795 0.1338 | 0.1338 0.0728 | 0.0728 0.0751 | 0.0751 0.0058 | 0.0064
@@ -16,9 +16,12 @@ and route, kernel | CPU emulation (test_family_within_the_gate prints every sing
     dc_plus_ripple        0.0109 | 0.0097 0.0015 | 0.0018 0.0043 | 0.0031 0.0015 | 0.0019 0.0082 | 0.0082 0.0022 | 0.0020 0.0011 | 0.0011 0.0013 | 0.0013 0.0017 | 0.0016
     swish_leaky_edges     0.4295 | 0.4295 0.2952 | 0.2952 0.3366 | 0.3366 0.2981 | 0.2981 0.2063 | 0.2063 0.2390 | 0.2390 0.1767 | 0.1767 0.2089 | 0.2089 -
     swish_leaky_edges_sft 0.2921 | 0.4235 0.2462 | 0.4148 0.2887 | 0.4238 0.2414 | 0.4038 0.2459 | 0.4160 0.2415 | 0.4018 0.2445 | 0.4108 0.2460 | 0.4119 -
+    solo_cin              0.3338 | 0.3738 0.4544 | 0.4544 0.1214 | 0.1409 0.3117 | 0.3117 0.2653 | 0.2653 0.2746 | 0.2746 0.2612 | 0.2612 0.2693 | 0.2694 -
+    solo_cin_act          0.4258 | 0.4258 0.4937 | 0.4937 0.1463 | 0.1352 0.2570 | 0.2570 0.2906 | 0.2906 0.2696 | 0.2696 0.2474 | 0.2474 0.2545 | 0.2545 0.0356 | 0.0314
     onehot_pixels         0.3916          0.3964          0.4667          0.4278          0.4920          0.3518          0.3503          0.2761          0.2917
 (equal pairs: the worst element is one whose error is a single rounding both evaluations make alike -- the residual add of swish_leaky_edges, the half
-rounding of a small channel's U in mixed_cout; the w23_h8 column is its bf16 form, whose gate is the operand format's 2^-8.  The swish / leaky families sit at
+rounding of a small channel's U in mixed_cout, the half rounding of a subnormal activation half in the solo families, whose gate enters it at the whole
+spacing; the w23_h8 column is its bf16 form, whose gate is the operand format's 2^-8.  The swish / leaky families sit at
 the epilogue's own rounding by construction: their operands are 2^10 larger than the convolution.  The SFT epilogue is an FMA chain in the kernels.
 Read the equal cells as what they are: they exercise the epilogue add (swish_leaky_edges, whole row) or the host-side packer's half rounding (the Winograd
 columns of mixed_cout), NOT the MFMA accumulation, and meet the >= 1e-3 condition trivially; the evidence on the accumulation path is in the cells that differ,
@@ -47,8 +50,23 @@ eight 3x3 tests of test_gpu_split.py that were run against each build (split_con
 Plainly: of eleven edits, four are caught by this file and by none of the old tests (e5, e6, e8, e9: subnormal lo halves flushed in each of the three packers, padding that lets a NaN through), errors confined to elements that are
 small next to the tensor's largest, or to non-finite inputs -- the gap the per-element gates were built for.  The seven gross edits (a product or an operand half left out, a wrong
 border, a misplaced scale, another chunk order) are caught by the old whole-tensor bounds as well; there this file adds only the localisation (which
-route, which family, which tap).  An edit that loses the lo halves of SMALL ACTIVATIONS only (tried on paper for cf_wf43.hip's V split) would pass both:
-with one gate per output element, a small input channel hides behind the large ones of the same sum.
+route, which family, which tap).
+The solo families (one input channel per output channel, channel scales over 32 binades; conv_check) were added for the edit the older families cannot
+see: the lo half of an activation zeroed where it is a subnormal half, |a| < 2^-3 under the range scale.  In every dense family a small input channel
+hides behind the large ones of the same sum -- tests/test_conv_families_host.py pins that on the CPU emulation (no older family's ratio at shape b moves
+by 0.005 of its gate; the solo families' rises to 25 .. 103 times theirs).  Four scratch builds with exactly that edit, one kernel each, all four built
+and run once; tests of this file that fail | of the eight 3x3 tests of test_gpu_split.py:
+  (s1) cf_split.hip split2 (the gather's split)                         5: the dsplit gates of solo_cin and solo_cin_act, tap_shift b / c / u1 | 1 (split_conv_against_fp64)
+         (in test_gpu_conv_geom.py: 11 -- the three solo gates of s2_dsplit / c1_dsplit, tap_shift on the seven split-half cases, mixed_cout on c1_dsplit)
+  (s2) cf_winograd.hip, the V split of the split-half form              2: the w23_h4 gates of solo_cin and solo_cin_act | 1 (split_conv_against_fp64)
+  (s3) cf_wsplit.hip, the V split                                       2: the w23_h8 gates of solo_cin and solo_cin_act | 2 (split_conv_against_fp64, split_conv_is_bitwise..)
+  (s4) cf_wf43.hip, the V split (the edit once "tried on paper")        6: the w43_8, w43_16k32 and w43_16k16 gates of solo_cin and solo_cin_act
+                                                                        | 2 (winograd_f43_forms_against_fp64, winograd_f43_with_512_input_channels)
+Plainly: every one of the four is now caught here, by the solo gates on exactly the route that was edited, and on the three Winograd kernels by nothing
+else in this file -- none of the seven older gate families, int_coded, onehot_pixels or (s2 - s4) tap_shift moves.  The old whole-tensor tests catch
+each of the four as well: most of their cases put O(1) values behind an affine or swish prologue, with no range scale, so a large share of ALL their operands lies below 2^-3
+and the edit is a gross one there (the split kernels' error is also held to 5x the fp32 kernels').  What they cannot see, and the solo gates can, is the same loss confined to the channels that are small next to the
+image's largest under a range scale (the host test's figures): there this file is the only check.
 """
 import pytest
 
@@ -58,7 +76,8 @@ pytestmark = pytest.mark.gpu
 
 ROUTES = ('d32', 'dsplit', 'w23_f32', 'w23_h4', 'w23_h8', 'w43_8', 'w43_16k32', 'w43_16k16', 'w43_up')
 GATE_FAMILIES = ('mixed_cout', 'mixed_cin', 'mixed_cin_act', 'cancel_pairs', 'dc_plus_ripple', 'swish_leaky_edges', 'swish_leaky_edges_sft')
-PROLOGUE_ONLY = ('mixed_cin', 'swish_leaky_edges', 'swish_leaky_edges_sft')       # families that ARE their prologue: the upsampling forms take none
+SOLO_FAMILIES = ('solo_cin', 'solo_cin_act')      # one input channel per output channel, under conv_check's solo gate
+PROLOGUE_ONLY = ('mixed_cin', 'swish_leaky_edges', 'swish_leaky_edges_sft', 'solo_cin')       # families that ARE their prologue: the upsampling forms take none
 SHAPE_KEYS = ('a', 'b', 'c', 'd', 'e', 'f', 'g', 'u1', 'u2')
 
 
@@ -69,7 +88,7 @@ def cc():
     from codeformer_amd import lib
     lib.load()
     m = load_script('tools/conv_check.py')
-    assert m.ROUTES == ROUTES and m.GATE_FAMILIES == GATE_FAMILIES and tuple(m.SHAPES) == SHAPE_KEYS
+    assert m.ROUTES == ROUTES and m.GATE_FAMILIES == GATE_FAMILIES and m.SOLO_FAMILIES == SOLO_FAMILIES and tuple(m.SHAPES) == SHAPE_KEYS
     return m
 
 
@@ -147,7 +166,7 @@ def test_tap_shift_moves_the_input_and_pads_each_border_with_zeros(cc, key):
 
 
 # ---- 3. the gate families --------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('family,route', [(f, r) for f in GATE_FAMILIES for r in ROUTES if not (r == 'w43_up' and f in PROLOGUE_ONLY)])
+@pytest.mark.parametrize('family,route', [(f, r) for f in GATE_FAMILIES + SOLO_FAMILIES for r in ROUTES if not (r == 'w43_up' and f in PROLOGUE_ONLY)])
 def test_family_within_the_gate(cc, family, route):
     """The per-element gate on every shape, code and split count that reaches the route; the measured / gate ratio is printed, may not exceed 1 and may
     not fall below 1e-3 of the emulation's (a gate that loose would check nothing)."""
@@ -163,6 +182,20 @@ def test_family_within_the_gate(cc, family, route):
     assert n > 0 and emu > 0.0
     assert worst >= 1e-3 * emu, (family, route, worst, emu)
     print(f'TABLE {family} {route} {worst:.4f} {emu:.4f}')
+
+
+@pytest.mark.parametrize('key', ('b', 'e'))
+def test_a_single_unit_tap_moves_a_solo_input_bitwise(cc, key):
+    """solo_cin_act's input (channel scales 2^-16 .. 2^16) against tap_shift's weight, one +-1 per output channel: d32 returns +- the moved input bit for
+    bit, the smallest channels included (cout 64 reads 64 of the 256 channels at e)."""
+    import torch
+    base = cc.family('solo_cin_act', key)
+    for tap in (0, 4, 8):
+        d = dict(base, w=cc.tap_weight(*cc.SHAPES[key][3:5], tap), b=torch.zeros_like(base['b']))
+        want = cc.reference(d)['out']
+        assert torch.equal(want, want.float().double()) and float(want.abs().min()) < 2.0 ** -20 < 2.0 ** 16 < float(want.abs().max())
+        got = cc.run(d, 0, 0, ('solo_tap', key, tap))
+        assert cc.bits_equal(got.cpu() + 0.0, want.float() + 0.0), (key, tap, int((got.cpu() != want.float()).sum()))
 
 
 # ---- 4. bitwise contracts and containment on the hard families ---------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ preconditions hold and that the reference is the index-by-index convolution, so 
 packed with the explicit code (0, or ops.SPLIT with stride2=True / a 1x1 weight); fp32 1x1 launches pass split_k=0.  Nothing is larger than 128x128x32
 in or 64x64x384 out.
 
-Measured on an MI355X, the whole file 7.0 s (160 cases; none above 0.4 s, the CPU references included; every case runs every gate family
+Measured on an MI355X, the whole file 7.9 s (167 cases; none above 0.4 s, the CPU references included; every case runs every gate family
 but mixed_cout at p1c, see conv_geom_check.families_of).  Largest |error| / gate per family and route,
 kernel | CPU emulation (test_family_within_the_gate prints every single ratio; onehot_pixels: the kernel's; -: the route lacks the family's prologue or epilogue):
                           s2_d32          s2_dsplit       c1_d32          c1_dsplit       ext_d32         ext_up          d32_32          head
@@ -17,7 +17,11 @@ kernel | CPU emulation (test_family_within_the_gate prints every single ratio; o
     dc_plus_ripple        0.0124 | 0.0119 0.0038 | 0.0041 0.0558 | 0.0565 0.0205 | 0.0180 0.0116 | 0.0082 0.0046 | 0.0043 0.0138 | 0.0126 0.0023 | 0.0007
     swish_leaky_edges     0.4234 | 0.4234 -               0.4886 | 0.4886 0.4792 | 0.4792 0.4050 | 0.4050 0.3811 | 0.3811 0.4387 | 0.4387 -
     swish_leaky_edges_sft 0.3096 | 0.4366 0.2474 | 0.4363 0.4254 | 0.4254 0.4003 | 0.4218 -               -               0.2386 | 0.3863 -
+    solo_cin              0.3512 | 0.3832 -               0.4747 | 0.4747 0.4995 | 0.4995 .               .               .               .
+    solo_cin_act          0.4072 | 0.4072 0.4547 | 0.4547 0.4981 | 0.4981 0.4998 | 0.4995 .               .               .               .
     onehot_pixels         0.4220          0.3679          0.4273          0.4157          0.4741          0.4193          0.2292          0.2243
+(.: the solo families run on the two split-half routes and their fp32 partners only.  Their c1 cells sit at one half by construction: a 1x1 with one input
+channel per output is ONE product, every rounding on its way is entered at a whole ulp and attains half of that -- see conv_geom_check.)
 (equal pairs: one rounding both evaluations make alike -- the residual add of swish_leaky_edges, the half rounding of a small channel's weight in
 mixed_cout on the split-half routes, and on ext_d32 the bias add of the 32-wide rung's smallest channel; they exercise the epilogue and the packer,
 not the accumulation, whose evidence is in the cells that differ, in int_coded, tap_shift and onehot_pixels.)
@@ -46,6 +50,9 @@ Plainly: six of the seven edits are gross and the old whole-tensor bounds catch 
 family).  One (e3: subnormal lo halves flushed in the packer, an error confined to channels small next to the tensor's largest) is caught by this file
 alone, as was the real defect above.  e1 does not move the containment sets: a clamp reads the border pixel where the reflection reads its neighbour,
 and both windows belong to the same outputs.
+  (s1) cf_split.hip split2: the lo half of an activation zeroed       11: the solo gates of s2_dsplit (solo_cin_act) and c1_dsplit (both), tap_shift on the seven split-half
+         where it is a subnormal half, |a| < 2^-3                      cases, mixed_cout on c1_dsplit | 0 of the two split-half tests above (stride2.., 1x1_streaming..)
+The solo families exist for this edit: see tests/test_gpu_conv_families.py, which lists it on all four split-half kernels.
 """
 import pytest
 
@@ -61,6 +68,8 @@ FORMS = {('s2_d32', '64-wide'), ('s2_d32', '128-wide'), ('s2_d32', 'ext'), ('s2_
 CASE_KEYS = ('s2a', 's2b', 's2c', 's2d', 's2z', 's2r', 'p1a', 'p1b', 'p1c', 'p1d', 'e1z', 'e1r', 'e2z', 'e2r', 'e3z', 'e3r', 'sl', 'epl', 'epa', 'epa2',
              'u1z', 'u1e', 'u2z', 'u2e', 'd32', 'hd')
 GATE_FAMILIES = ('mixed_cout', 'mixed_cin', 'mixed_cin_act', 'cancel_pairs', 'dc_plus_ripple', 'swish_leaky_edges', 'swish_leaky_edges_sft')
+SOLO_FAMILIES = ('solo_cin', 'solo_cin_act')      # one input channel per output channel: the split-half routes and their fp32 partners
+SOLO_ROUTES = ('s2_d32', 's2_dsplit', 'c1_d32', 'c1_dsplit')
 SFT_ROUTES = ('s2_d32', 's2_dsplit', 'c1_d32', 'c1_dsplit', 'd32_32')       # routes with the SFT epilogue (the EXT instantiations and the head lack it)
 NAN_BITS = 0x7fc00000
 
@@ -73,6 +82,7 @@ def gc():
     lib.load()
     m = load_script('tools/conv_geom_check.py')
     assert m.ROUTES == ROUTES and m.GATE_FAMILIES == GATE_FAMILIES and tuple(m.CASES) == CASE_KEYS
+    assert m.SOLO_FAMILIES == SOLO_FAMILIES and m.SOLO_ROUTES == SOLO_ROUTES
     return m
 
 
@@ -165,6 +175,23 @@ def test_family_within_the_gate(gc, family, route):
             assert r['ratio'] <= 1.0, (family, key, route, cname, form, r)
             worst, emu, n = max(worst, r['ratio']), max(emu, r['emu_ratio']), n + 1
     assert n > 0 and emu > 0.0
+    assert worst >= 1e-3 * emu, (family, route, worst, emu)
+    print(f'TABLE {family} {route} {worst:.4f} {emu:.4f}')
+
+
+@pytest.mark.parametrize('family,route', [(f, r) for f in SOLO_FAMILIES for r in SOLO_ROUTES if not (f == 'solo_cin' and r == 's2_dsplit')])
+def test_solo_family_within_the_gate(gc, family, route):
+    """One input channel per output channel over 32 binades of channel scales, on every case and form of the split-half routes and their fp32 partners,
+    under conv_geom_check's solo gate (c counts the one product chain that exists; the floor sums that channel alone, at the whole spacing)."""
+    worst, emu, n = 0.0, 0.0, 0
+    for key in gc.cases_of(route):
+        for cname, code, rt, form in gc.launches(key, (route,)):
+            r = gc.case(family, key, code, route, form)
+            assert r is not None, (family, key, route, form)
+            print(f'{family} {key} {route} {cname} {form}: max|d| {r["err"]:.3e} = {r["ratio"]:.4f} of the gate | emulation {r["emu_err"]:.3e} = {r["emu_ratio"]:.4f}')
+            assert r['ratio'] <= 1.0, (family, key, route, cname, form, r)
+            worst, emu, n = max(worst, r['ratio']), max(emu, r['emu_ratio']), n + 1
+    assert n >= 3 and emu > 0.0
     assert worst >= 1e-3 * emu, (family, route, worst, emu)
     print(f'TABLE {family} {route} {worst:.4f} {emu:.4f}')
 

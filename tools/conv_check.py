@@ -42,6 +42,16 @@ Families (CPU, fixed seeds; family(name, shape_key) -> dict x, w, b, sc, sh, res
                  output is a small remainder of a large S (median S / |pre| >= 100 asserted on the CPU) and the additions round.  Affine prologue, bias.
   dc_plus_ripple x = 2^8 + N(0, 1) against weights whose nine taps sum to ~0 per (n, c): the classic Winograd amplification case; the image border
                  (zero padding: the constant does not cancel there) and the interior patch borders are both in every shape.  Prologue none + act, residual.
+  solo_cin       output channel n reads exactly ONE input channel p(n): w[n, p(n)] is a dense random 3x3 tap set (not +-1: the weight's own lo halves take
+                 part, lo hi + hi lo + hi hi), every other weight an exact 0; input channel c carries 2^e(c), e linear over 2 SOLO_EXP = 32 binades.  In
+                 every dense family a small input channel hides behind the large ones of the same sum (S and c are set by all of them); here each
+                 channel is alone in its sum and meets its own gate.  Variant 'solo_cin': the scale through the affine prologue, e = -22 .. 10 (the top
+                 where mixed_cin has it: IEEE half ends at 65504 and an affine prologue has no range scale); 'solo_cin_act': in the tensor itself,
+                 e = -16 .. 16, prologue none with the per-image range scale `act`.  p (solo_perm) reads the smallest and the largest channel and at
+                 least one per 16-channel slab at every shape, cout < cin included; under the range scale the read channels include some whose lo
+                 halves are all subnormal with normal hi halves (|a| < 2^-3) and some whose hi halves are subnormal too (|a| < 2^-14) -- both
+                 asserted by the host test, per shape and image.  The bias is random at the scale of the channel it is added to; no epilogue operand.
+                 The gate differs in two places that follow from the zeros (below).
   swish_leaky_edges  inputs cycling through 0, -0, +-2^-10, +-1, +-6, +-20: affine (sc 1, sh 0) + swish with a residual, and LeakyReLU with an SFT
                  epilogue (variant 'swish_leaky_edges_sft'), the epilogue operands 2^10 larger than the convolution.
 
@@ -67,10 +77,23 @@ Gate, against fp64, PER ELEMENT (u = 2^-24):
       s = the image's range scale (1 with an affine prologue); on Winograd routes both sums in the transform domain, sum_c |V| and sum_c |U|, taken
       through |A^T| . |A|.  (The form of gemm_check.gate.)  0 for fp32 and bf16 operands.
   epilogue  bias 2 u |pre| (entered ALWAYS, also where b = 0 (tap_shift): harmless next to c u S, and exact elements meet any gate); residual 2 u |out|; SFT out = r0 + w (r0 r1 + pre): 2 u (|w r0 r1| + 2 |w (r0 r1 + pre)| + |out|): single roundings at a whole ulp.
+The solo families (SOLO_FAMILIES), two changes, both consequences of the exact zeros:
+  c      counts the products that exist.  A term whose weight is an exact zero is an exact zero product in every scheme (hi = lo = 0; U = G 0 G^T = 0), and
+         adding an exact zero never rounds: the chain over the channels has ONE term, so cin becomes 1 in every row above (d32 9, dsplit 27 + 12,
+         w23 1 + 7, split halves 3 + 12 + 7, w43 1 + 19, ...).  The transform constants and the split-K chunk additions (cin / 128: every chunk IS
+         added) stay as they are.
+  floor  sums the channels that have halves in the sum: sum |p(x)| / scale runs over the input channels with a non-zero weight for THAT output channel
+         (direct: the convolution of |p| with the 0 / 1 pattern of the weight; Winograd: sum over those channels of |V| through |A^T| . |A|, evaluated
+         exactly, no bound); sum |w| / s needs no change, a zero weight adds zero.  And with one channel alone in the sum the absolute 2^-25 of a
+         subnormal half is ATTAINED by a correct evaluation (in a dense sum it is a worst case over cin halves that never align), so it is entered at
+         the whole spacing 2^-24: the rule gemm_check.gate applies to single roundings (bias, residual), which keeps the emulation within half.
+  The fp32 routes have no floor term and take only the first change.
 The emulation (emulate(): torch float32 on the CPU; transforms as two passes of fp32 einsums, U from fp64 rounded once, halves split as
 gemm_check.split_halves does, three products lo hi + hi lo + hi hi, fp32 epilogue) is the condition on the gate: tests/test_conv_families_host.py asserts its
 error within 0.5 of the gate for every gate family, operand scheme and transform at every shape the GPU test uses (the folded forms are emulated on
-the upsampled image with the unfolded weight: the fold's additions are the + 3 of c).  No number here was fitted to
+the upsampled image with the unfolded weight: the fold's additions are the + 3 of c).  emulate(.., act_halves=) takes an edit of the activation's
+split: with drop_small_lo (the lo half zeroed where it is subnormal, |a| < 2^-3) the solo families' emulation exceeds their gate 25 .. 103 times at
+every shape and split-half scheme while no other family's ratio at shape b moves by 0.002 of its gate (the host test asserts >= 10 and <= 0.005).  No number here was fitted to
 what a kernel returns; the kernels' figures are in the docstring of tests/test_gpu_conv_families.py.
 """
 import functools
@@ -106,6 +129,11 @@ SHAPES = {'a': (1, 16, 16, 16, 64, None, False), 'b': (2, 16, 32, 32, 64, None, 
           'd': (3, 32, 48, 48, 128, None, False), 'e': (1, 16, 16, 256, 64, None, False), 'f': (1, 16, 16, 512, 128, 256, False),
           'g': (1, 48, 32, 192, 192, None, False), 'u1': (2, 16, 16, 32, 128, None, True), 'u2': (1, 16, 16, 64, 64, None, True)}
 GATE_FAMILIES = ('mixed_cout', 'mixed_cin', 'mixed_cin_act', 'cancel_pairs', 'dc_plus_ripple', 'swish_leaky_edges', 'swish_leaky_edges_sft')
+# one input channel per output channel: gate families too, under a gate that counts and sums the channels that HAVE a product.  A tuple of their own:
+# GATE_FAMILIES is the list of the dense families, which tests and tools/conv_geom_check.py pin as it is
+SOLO_FAMILIES = ('solo_cin', 'solo_cin_act')
+SOLO_EXP = 16
+LO_SUBNORMAL, HI_SUBNORMAL = 2.0 ** -3, 2.0 ** -14       # |a| below which the lo half / the hi half of an operand is a subnormal IEEE half
 IMPULSE_FAMILIES = ('onehot_pixels', 'tap_shift')
 
 # the transforms, as the kernels document them (cf_winograd.hip; cf_wf43.hip:16-19, B'^T = D B^T, G' = D^-1 G)
@@ -226,6 +254,24 @@ def tap_weight(cin, cout, tap, k=3):
     return w
 
 
+def solo_perm(cin, cout):
+    """p: output channel -> the one input channel it reads.  cout >= cin: n -> (5 n + 3) mod cin, a bijection on every run of cin outputs (5 is coprime
+    to every cin in use), so EVERY input channel is read; cout < cin: cout channels spread evenly from 0 to cin - 1, both ends included, less than 16
+    apart where cin <= 16 (cout - 1) + 1.  tap_perm promises neither where cout < cin."""
+    n = torch.arange(cout)
+    if cout >= cin:
+        assert math.gcd(5, cin) == 1
+        return (5 * n + 3) % cin
+    return torch.round(n.double() * ((cin - 1) / (cout - 1))).long()
+
+
+def solo_exponents(name, cin):
+    """e(c), linear from -SOLO_EXP to +SOLO_EXP; solo_cin: moved down by SOLO_EXP - CIN_EXP, so that the largest channel sits at 2^CIN_EXP as
+    mixed_cin's does -- an affine prologue has no range scale, and 2^16 x 1.5 x 4.5 is past the largest IEEE half."""
+    e = torch.round(-SOLO_EXP + torch.arange(cin).float() * (2.0 * SOLO_EXP / (cin - 1)))
+    return e - (SOLO_EXP - CIN_EXP) if name == 'solo_cin' else e
+
+
 def family_at(name, geom, seed, variant=0, k=3, out_hw=None, positions=None, key=None, bare_up=True):
     """The recipe of family() at any geometry: geom = (B, H, W of the input, cin, cout, upsample); k = 3 | 1 the kernel's side; out_hw the output
     size where it is neither the input's nor twice it (stride 2); positions(image) -> the one-hot pixels of an image (default: onehot_positions); bare_up: upsampling shapes take prologue none and no
@@ -267,6 +313,15 @@ def family_at(name, geom, seed, variant=0, k=3, out_hw=None, positions=None, key
             sc, sh = sc * torch.pow(2.0, e)[None, :], sh * torch.pow(2.0, e)[None, :]
         else:
             x, pro = x * torch.pow(2.0, e), PRO_NONE
+    elif name in SOLO_FAMILIES:
+        e, p = solo_exponents(name, cin), solo_perm(cin, cout)
+        w = torch.zeros(cout, cin, k, k)
+        w[torch.arange(cout), p] = rnd((cout, k, k), seed + 11, (2.0 / (k * k)) ** 0.5)
+        b = b * torch.pow(2.0, e)[p]                      # (at the scale of the one channel it is added to: a bias of 0.1 would hide a channel of 2^-16)
+        if name == 'solo_cin':
+            sc, sh = sc * torch.pow(2.0, e)[None, :], sh * torch.pow(2.0, e)[None, :]
+        else:
+            x, pro = x * torch.pow(2.0, e), PRO_NONE
     elif name == 'cancel_pairs':
         half = cin // 2
         x = rnd((B, H, W, half), seed + 8).repeat_interleave(2, dim=3)
@@ -288,7 +343,7 @@ def family_at(name, geom, seed, variant=0, k=3, out_hw=None, positions=None, key
         raise KeyError(name)
     if up and bare_up:
         pro, epi = PRO_NONE, EPI_NONE
-    return dict(x=x.contiguous(), w=w.contiguous(), b=b, sc=sc.contiguous(), sh=sh.contiguous(), res=res, ss=ss, pro=pro, epi=epi, sft_w=sft_w, up=up, key=key)
+    return dict(x=x.contiguous(), w=w.contiguous(), b=b, sc=sc.contiguous(), sh=sh.contiguous(), res=res, ss=ss, pro=pro, epi=epi, sft_w=sft_w, up=up, key=key, solo=name in SOLO_FAMILIES)
 
 
 @functools.lru_cache(maxsize=None)
@@ -391,16 +446,34 @@ def pack_scale_of(d, m, up=False):
     return ops.pack_scale(ops._f23_max(w) if m == 2 else ops._f43_max(w) if m == 4 else float(w.abs().max()) * (4.0 if up else 1.0))
 
 
-def coef(route, code, cin, split_k=0, up=False):
+def coef(route, code, cin, split_k=0, up=False, live=None):
+    """live: the number of input channels whose weight is not an exact zero, where that is fewer than cin (the solo families): the chains' length.
+    (The split-K chunk additions stay cin / 128: every chunk is added.)"""
     m, op = scheme_of(route, code)
+    n = cin if live is None else live
     if m == 0:
-        return (9 * cin if op == 'f32' else 27 * cin + 12) + (3 if up else 0)
+        return (9 * n if op == 'f32' else 27 * n + 12) + (3 if up else 0)
     t = 7 if m == 2 else 19
     if op == 'f32':
-        return cin + t + (cin // 128 if split_k else 0)
+        return n + t + (cin // 128 if split_k else 0)
     if op == 'half2':
-        return 3 * cin + 12 + t + (cin // 128 if split_k else 0)
-    return cin + t + 2.0 * (2.0 ** -11 if op == 'half' else 2.0 ** -8) / U
+        return 3 * n + 12 + t + (cin // 128 if split_k else 0)
+    return n + t + 2.0 * (2.0 ** -11 if op == 'half' else 2.0 ** -8) / U
+
+
+def live_channels(d):
+    """(cout, cin) bool: the input channels an output channel has a non-zero weight for."""
+    return (d['w'] != 0).flatten(2).any(2)
+
+
+def solo_kinds(d):
+    """(B, cin) bool x 2, of the conv's input as the kernels split it (fp32, through the prologue or under the range scale), among the channels some
+    output reads: channels whose EVERY lo half is a subnormal half (max |a| < 2^-3) while their hi halves are normal (median |a| >= 2^-14), and
+    channels whose every hi half is subnormal too (0 < max |a| < 2^-14)."""
+    s = act_scale_of(d).float()[:, None, None, None]
+    a = (d['x'] * d['sc'][:, None, None, :] + d['sh'][:, None, None, :] if d['pro'] == PRO_AFFINE else d['x'] * s).abs().flatten(1, 2)
+    mx, med, read = a.amax(1), a.median(1).values, live_channels(d).any(0)[None, :]
+    return (mx < LO_SUBNORMAL) & (med >= HI_SUBNORMAL) & read, (mx < HI_SUBNORMAL) & (mx > 0) & read
 
 
 @functools.lru_cache(maxsize=None)
@@ -408,11 +481,15 @@ def _abs_eval(name, key, variant, m):
     """(S, P / u-free prologue term, sum|p| term, sum|w| term) of a family at a shape for the transform m, fp64."""
     d = family(name, key, variant)
     p, ep = prologue64(d)
+    live = live_channels(d).double() if name in SOLO_FAMILIES else None       # the solo families: sum |p| over the channels that have halves in the sum
     if m == 0:
         ones_w, ones_p = torch.ones_like(d['w']), torch.ones_like(p)
-        return conv64(p.abs(), d['w'].abs()), conv64(ep, d['w'].abs()), conv64(p.abs(), ones_w)[..., :1], conv64(ones_p, d['w'].abs())
+        fv = conv64(p.abs(), ones_w)[..., :1] if live is None else conv64(p.abs(), live[:, :, None, None] * ones_w)
+        return conv64(p.abs(), d['w'].abs()), conv64(ep, d['w'].abs()), fv, conv64(ones_p, d['w'].abs())
     S, (fv, fu) = wino(p, d['w'], m, absolute=True)
     P, _ = wino(ep, d['w'], m, absolute=True)
+    if live is not None:          # sum over the live channels of |V|, per output channel, through |A^T| . |A|: exact, no bound
+        fv, _ = wino(p, d['w'], m, absolute=True, products=lambda Vm, Um: torch.matmul(Vm, live.t()))
     return S, P, fv, fu
 
 
@@ -428,10 +505,13 @@ def gate(name, key, route, code, split_k=0, variant=0):
     m, op = scheme_of(route, code)
     cin = d['w'].shape[1]
     S, P, fv, fu = _abs_eval(name, key, variant, m)
-    g = coef(route, code, cin, split_k, d['up']) * U * S + P + 2 * U * ref['pre'].abs()
+    solo = name in SOLO_FAMILIES
+    live = int(live_channels(d).sum(1).max()) if solo else None
+    assert live in (None, 1)
+    g = coef(route, code, cin, split_k, d['up'], live) * U * S + P + 2 * U * ref['pre'].abs()
     if op in ('half2', 'half'):
         s = act_scale_of(d)[:, None, None, None]
-        g = g + 2.0 ** -25 * (1.0 + 2.0 ** -10) * (fv / pack_scale_of(d, m, d['up']) + fu / s)
+        g = g + (2.0 ** -24 if solo else 2.0 ** -25) * (1.0 + 2.0 ** -10) * (fv / pack_scale_of(d, m, d['up']) + fu / s)
     if d['epi'] == EPI_RESIDUAL:
         g = g + 2 * U * ref['out'].abs()
     elif d['epi'] == EPI_SFT:
@@ -450,8 +530,18 @@ def _round16(t, op):
     return t.to(torch.float16 if op == 'half' else torch.bfloat16).float()
 
 
-def emulate(d, route, code):
-    """The route's arithmetic in torch float32 -> (B, Ho, Wo, cout) float32."""
+def drop_small_lo(a, ah, al):
+    """The edit the solo families exist for: the lo half of an activation zeroed wherever it is a subnormal half (|a| < 2^-3 under the range scale)."""
+    return ah, torch.where(a.abs() < LO_SUBNORMAL, torch.zeros_like(al), al)
+
+
+def drop_every_lo(a, ah, al):
+    return ah, torch.zeros_like(al)
+
+
+def emulate(d, route, code, act_halves=None):
+    """The route's arithmetic in torch float32 -> (B, Ho, Wo, cout) float32.  act_halves(a, hi, lo) -> (hi, lo): an edit of the activation's split
+    (split halves only; default none), for the host test that shows which family notices it."""
     m, op = scheme_of(route, code)
     f = torch.float32
     x, sc, sh = d['x'], d['sc'][:, None, None, :], d['sh'][:, None, None, :]
@@ -473,6 +563,8 @@ def emulate(d, route, code):
             return a @ b
         if op == 'half2':
             ah, al = _halves(a)
+            if act_halves is not None:
+                ah, al = act_halves(a, ah, al)
             bh, bl = _halves(b)
             return (al @ bh + ah @ bl) + ah @ bh
         return _round16(a, op) @ _round16(b, op)
@@ -589,9 +681,9 @@ def case(name, key, code, split_k, route, variant=0, emulate_too=True):
 
 if __name__ == '__main__':
     bad = 0
-    for fam in GATE_FAMILIES + ('onehot_pixels',):
+    for fam in GATE_FAMILIES + SOLO_FAMILIES + ('onehot_pixels',):
         for key in SHAPES:
-            if SHAPES[key][6] and fam in ('mixed_cin', 'swish_leaky_edges', 'swish_leaky_edges_sft'):
+            if SHAPES[key][6] and fam in ('mixed_cin', 'swish_leaky_edges', 'swish_leaky_edges_sft', 'solo_cin'):
                 continue          # (upsampling shapes take no prologue: these families are their prologue)
             for cname, code, sk, route, form in launches(key):
                 r = case(fam, key, code, sk, route)

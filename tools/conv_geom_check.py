@@ -54,6 +54,10 @@ Families: conv_check.family_at at the case's geometry (seed 3000 + 17 * the case
                  the others run with prologue none.  A recipe that needs more channels than the case has is dropped too (buildable(): mixed_cout at
                  cout 1, mixed_cin_act at c0 1, cancel_pairs at c0 1 and 3).
 
+  solo_cin, solo_cin_act   (SOLO_FAMILIES, on SOLO_ROUTES: the two split-half routes and their fp32 partners) conv_check's recipe: one input channel per output
+                 channel over 32 binades of channel scales, every other weight an exact zero.  s2_dsplit refuses the affine prologue that solo_cin is about.
+                 They are not in GATE_FAMILIES: the other routes have no split halves to lose.
+
 Gate, against fp64, PER ELEMENT, the form of conv_check.gate (u = 2^-24):    gate = c u S + P + floor + epilogue terms
   S      the definition's own convolution with |w| and |p(x)| on the padded image: a reflected or replicated pixel counts as often as it is read.
   c      taps cin for the fp32 chains (the head's FMA chain included), + 3 with folded taps; 3 taps cin + 12 for split halves -- at stride 2 the
@@ -66,6 +70,10 @@ Gate, against fp64, PER ELEMENT, the form of conv_check.gate (u = 2^-24):    gat
          LEAKY   out = pre > 0 ? pre : fl(0.2f pre): the map has slope <= 1, so g0 passes unchanged; one product: g0 + 2 u |out|
          AXPY    out = fl(fl(pre a) + res): |a| g0 + 2 u |a pre| + 2 u |out|
          AXPY2   t = fl(fl(pre a) + res), out = fl(fl(t a) + res2): a^2 g0 + 2 u (a^2 |pre| + |a t|) + 2 u |a t| + 2 u |out|
+  The solo families take conv_check's two changes: c counts the ONE channel whose product exists (taps instead of taps cin), and the floor sums |p(x)| over
+  that channel alone and enters the subnormal half's spacing whole, 2^-24.  At taps 1 in fp32 the whole sum is one product: its rounding, and the affine
+  prologue's two, are then single roundings that attain their u, and go in at a whole ulp each (c = 2, 2 P) -- found by the host test, whose emulation
+  stood at 0.96 (prologue none) and 0.60 (affine) of the gate without them.
 emulate() is the fp32 CPU emulation of each operand scheme on the padded image (stride 2: the plain weight on the padded image; the folded forms: the
 unfolded weight on the upsampled one); tests/test_conv_geom_host.py asserts it within 0.5 of the gate for every gate family, route and case.  No
 constant here was fitted to what a kernel returns.
@@ -102,6 +110,8 @@ ROUTES = ('s2_d32', 's2_dsplit', 'c1_d32', 'c1_dsplit', 'ext_d32', 'ext_up', 'd3
 END_ROUTES = ('head', 'nchw_in')       # the routes of END_CASES (with_nchw_ends() appends the new one to ROUTES)
 SPLIT_ROUTES = ('s2_dsplit', 'c1_dsplit')
 CODES = {'F32': 0, 'SPLIT': ops.SPLIT}
+SOLO_FAMILIES = cc.SOLO_FAMILIES        # one input channel per output channel: on the two split-half routes and their fp32 partners (SOLO_ROUTES)
+SOLO_ROUTES = ('s2_d32', 's2_dsplit', 'c1_d32', 'c1_dsplit')
 GATE_FAMILIES = cc.GATE_FAMILIES
 SLICE = dict(x=(80, 16), x2=(48, 0), out=(128, 32))      # (buffer width, first channel) of the sliced case
 
@@ -285,6 +295,8 @@ def onehot_positions(g, image=0):
 def buildable(name, g):
     """A recipe needs its channels: mixed_cout spreads exponents over >= 2 output channels, mixed_cin[_act] over >= 2 input channels, cancel_pairs
     pairs the input channels up."""
+    if name in SOLO_FAMILIES:
+        return g.cin >= 2 and g.cout >= 2
     return not ((name == 'mixed_cout' and g.cout < 2) or (name in ('mixed_cin', 'mixed_cin_act') and g.cin < 2) or (name == 'cancel_pairs' and g.cin % 2))
 
 
@@ -309,7 +321,7 @@ def prologues_of(route):
 
 
 # what a family is ABOUT: without that prologue / epilogue it is not run at all; any other prologue / epilogue a route lacks is simply left out
-POINT = {'mixed_cin': ('pro',), 'swish_leaky_edges': ('pro', 'epi'), 'swish_leaky_edges_sft': ('epi',), 'int_coded': ('pro',)}
+POINT = {'mixed_cin': ('pro',), 'solo_cin': ('pro',), 'swish_leaky_edges': ('pro', 'epi'), 'swish_leaky_edges_sft': ('epi',), 'int_coded': ('pro',)}
 
 
 def family_of(name, key, route, form, variant=0):
@@ -390,8 +402,12 @@ def reference(d, g):
     return dict(pre=pre, out=epilogue64(d, pre))
 
 
-def coef(route, g):
-    n = g.taps * g.cin
+def coef(route, g, live=None):
+    """live: the number of input channels with a non-zero weight, where that is fewer than cin (the solo families: 1) -- a product with an exact
+    zero is an exact zero in every scheme, and adding it never rounds."""
+    n = g.taps * (g.cin if live is None else live)
+    if n == 1 and route not in SPLIT_ROUTES:      # a solo 1x1 in fp32: the chain IS one product.  A single rounding attains its u, so it is entered at a whole
+        n = 2                                     # ulp, as the bias and residual roundings are (the rule of gemm_check.gate): the emulation then stays within half
     return (3 * n + 12 if route in SPLIT_ROUTES else n) + (3 if g.up else 0)
 
 
@@ -405,7 +421,10 @@ def _abs_eval(d, g):
     wa = d['w'].abs()
     S = conv64(padded(p.abs(), g), wa, g)
     P = conv64(padded(ep, g), wa, g) if bool((ep != 0).any()) else torch.zeros_like(S)
-    fv = conv64(padded(p.abs(), g), torch.ones_like(d['w'][:1]), g)
+    if d.get('solo'):          # sum |p| over the channels that have halves in this output channel's sum: per output channel
+        fv = conv64(padded(p.abs(), g), cc.live_channels(d)[:, :, None, None].float() * torch.ones_like(d['w']), g)
+    else:
+        fv = conv64(padded(p.abs(), g), torch.ones_like(d['w'][:1]), g)
     fu = conv64(padded(torch.ones_like(p[:1, :, :, :]), g), wa, g)
     return S, P, fv, fu
 
@@ -413,12 +432,18 @@ def _abs_eval(d, g):
 def gate_of(d, g, route, ref, form=None):
     """The tolerance per element (B, Ho, Wo, cout), fp64."""
     S, P, fv, fu = _abs_eval(d, g)
-    g0 = coef(route, g) * U * S + P + 2 * U * ref['pre'].abs()
+    solo = bool(d.get('solo'))
+    live = int(cc.live_channels(d).sum(1).max()) if solo else None
+    assert live in (None, 1)
+    if solo and g.taps * live == 1 and route not in SPLIT_ROUTES:
+        P = 2 * P      # one product is the whole sum: the affine prologue's two roundings (x sc, + sh), which prologue64 enters at the u each can attain, are
+        #                single roundings on the way of ONE term and go in at a whole ulp like the product itself (coef)
+    g0 = coef(route, g, live) * U * S + P + 2 * U * ref['pre'].abs()
     if form in ('few_cin 3', 'few_cin n'):      # the vector kernel STARTS its FMA chain at the bias: every partial sum carries it
         g0 = g0 + coef(route, g) * U * d['b'].double().abs()
     if route in SPLIT_ROUTES:
         s = act_scale_of(d)[:, None, None, None]
-        g0 = g0 + 2.0 ** -25 * (1.0 + 2.0 ** -10) * (fv / pack_scale_of(d, g) + fu / s)
+        g0 = g0 + (2.0 ** -24 if solo else 2.0 ** -25) * (1.0 + 2.0 ** -10) * (fv / pack_scale_of(d, g) + fu / s)
     r0, r1, e, out, pre = d['res'].double(), d['ss'].double(), d['epi'], ref['out'], ref['pre']
     if e == EPI_RESIDUAL:
         return g0 + 2 * U * out.abs()
@@ -448,7 +473,7 @@ def prepared(name, key, route, form, variant=0):
 
 
 # ---- fp32 emulation ------------------------------------------------------------------------------------------------------------------------------
-def emulate(d, g, route):
+def emulate(d, g, route, act_halves=None):
     """The route's arithmetic in torch float32 -> (B, Ho, Wo, cout) float32: fp32 products, or split halves lo hi + hi lo + hi hi under the pack-time
     and range scales; the convolution as ONE matrix product over the unfolded padded image."""
     f = torch.float32
@@ -469,6 +494,8 @@ def emulate(d, g, route):
     wm = (d['w'].reshape(d['w'].shape[0], -1).t() * scale).contiguous()
     if split:
         ah, al = _halves(cols.contiguous())
+        if act_halves is not None:            # (an edit of the activation's split: conv_check.drop_small_lo)
+            ah, al = act_halves(cols, ah, al)
         bh, bl = _halves(wm)
         v = (al @ bh + ah @ bl) + ah @ bh
     else:
@@ -621,8 +648,10 @@ if __name__ == '__main__':
         with_nchw_ends()
     bad = 0
     for key in CASES:
-        for fam in families_of(key) + ('onehot_pixels',):
+        for fam in families_of(key) + ('onehot_pixels',) + SOLO_FAMILIES:
             for cname, code, route, form in launches(key):
+                if fam in SOLO_FAMILIES and route not in SOLO_ROUTES:
+                    continue
                 r = case(fam, key, code, route, form)
                 if r is None:
                     continue
