@@ -491,7 +491,31 @@ __global__ void pixel_unshuffle_nhwc_kernel(const float* __restrict__ x, int c, 
   out[i] = v;
 }
 
+// pixel-shuffle, channels-last on both sides (nn.PixelShuffle behind a conv that stays NHWC); one thread per output float, channel fastest
+__global__ void pixel_shuffle_nhwc_kernel(const float* __restrict__ x, int c, int h, int w, int s, float* __restrict__ out, long total) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int k = (int)(i % c);
+  const long pix = i / c;
+  const int ox = (int)(pix % (w * s));
+  const int oy = (int)((pix / (w * s)) % (h * s));
+  const long b = pix / ((long)(w * s) * (h * s));
+  const int iy = oy / s, ix = ox / s;
+  out[i] = x[((b * h + iy) * (long)w + ix) * ((long)c * s * s) + (k * s + (oy - iy * s)) * s + (ox - ix * s)];
+}
+
 }  // namespace
+
+extern "C" int cf_pixel_shuffle_nhwc(const float* x, int batch, int c, int h, int w, int s, float* out, cf_stream_t stream) {
+  CF_REQUIRE(x && out && batch > 0 && c > 0 && h > 0 && w > 0 && s >= 1 && s <= 16, "cf_pixel_shuffle_nhwc: bad args (c=%d h=%d w=%d s=%d)", c, h, w, s);
+  CF_REQUIRE((long)h * s < (1L << 31) && (long)w * s < (1L << 31) && (long)c * s * s < (1L << 31), "cf_pixel_shuffle_nhwc: image too large");
+  const long total = (long)batch * h * s * w * s * c;
+  CF_REQUIRE((total + 255) / 256 < (1L << 31), "cf_pixel_shuffle_nhwc: tensor too large");
+  hipLaunchKernelGGL(pixel_shuffle_nhwc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, c, h, w, s, out,
+                     total);
+  CF_CHECK_LAUNCH("cf_pixel_shuffle_nhwc");
+  return CF_OK;
+}
 
 extern "C" int cf_pixel_unshuffle_nhwc(const float* x, int batch, int c, int h, int w, int s, int c_pad, float* out,
                                        cf_stream_t stream) {

@@ -91,6 +91,7 @@ SIGNATURES = {
     'cf_vq_argmin': (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     'cf_nchw_to_nhwc': (_I, [_P, _I, _I, _I, _P, _P]),
     'cf_pixel_unshuffle_nhwc': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    'cf_pixel_shuffle_nhwc': (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     'cf_nhwc_to_nchw': (_I, [_P, _I, _I, _I, _P, _P]),
     'cf_img_u8_to_tensor': (_I, [_P, _I, _I, _I, _P, _P]),
     'cf_tensor_to_img_u8': (_I, [_P, _I, _I, _I, _P, _P]),
@@ -102,6 +103,7 @@ SIGNATURES = {
     'cf_deform_conv2d_packed_elems': (_L, [_I, _I, _I, _I]),
     'cf_pack_deform_conv_weight': (_I, [_P, _I, _I, _I, _I, _P, _P]),
     'cf_deform_conv2d': (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 17 + [_P]),
+    'cf_flow_warp': (_I, [_P, _P, _P] + [_I] * 8 + [_P]),
     'cf_warp_affine_u8':(_I, [_P, _L, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'cf_warp_affine_f32': (_I, [_P, _I, _I, ctypes.POINTER(ctypes.c_double), _P, _I, _I, _I, _I, _P]),
     'cf_erode_f32': (_I, [_P, _P, _P, _I, _I, _I, _P]),

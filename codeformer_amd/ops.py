@@ -1033,6 +1033,23 @@ def pixel_unshuffle_nhwc(x, scale, c_pad=None):
     return y
 
 
+def pixel_shuffle_nhwc(x, scale):
+    """(B,H,W,C*s*s) channels-last -> (B,H*s,W*s,C) channels-last: nn.PixelShuffle(s) on a conv output that stays NHWC (NCHW indices:
+    out[b, c, h*s+i, w*s+j] = x[b, c*s*s + i*s + j, h, w]).  ValueError for a shape that does not fit, TypeError for anything but float32."""
+    scale = int(scale)
+    if x.dim() != 4 or scale < 1 or scale > 16 or x.shape[3] % (scale * scale):
+        raise ValueError(f'pixel_shuffle_nhwc: expected (B,H,W,C*{scale}*{scale}) with 1 <= scale <= 16, got shape {tuple(x.shape)}')
+    if x.dtype != torch.float32:
+        raise TypeError(f'pixel_shuffle_nhwc: x is {x.dtype}; the op is float32 only')
+    lib = L.load()
+    B, H, W, Cs = x.shape
+    C = Cs // (scale * scale)
+    x = x.detach().contiguous()
+    y = torch.empty(B, H * scale, W * scale, C, dtype=torch.float32, device=x.device)
+    L.check(lib.cf_pixel_shuffle_nhwc(L.ptr(x), B, C, H, W, scale, L.ptr(y), L.stream_ptr()), 'cf_pixel_shuffle_nhwc')
+    return y
+
+
 def to_nchw(x):
     """(B,H,W,C) -> (B,C,H,W)."""
     lib = L.load()
@@ -1226,6 +1243,53 @@ def deform_conv2d(x, offset, weight, mask=None, bias=None, stride=1, padding=0, 
     L.check(lib.cf_deform_conv2d(L.ptr(xin), L.ptr(offset), L.ptr(mask), L.ptr(w), L.ptr(bias), L.ptr(out), B, cin, H, W, cout, kh, kw,
                                  sh, sw, ph, pw, dh, dw, int(groups), int(deformable_groups), nhwc, int(route == 'mfma'), L.stream_ptr()),
             'cf_deform_conv2d')
+    return out
+
+
+# ---- optical-flow warp (cf_warp.hip; codeformer_amd/archs/arch_util.py is the basicsr.archs.arch_util surface on top) -----------------
+WARP_INTERP = {'bilinear': 0, 'nearest': 1}
+WARP_PADDING = {'zeros': 0, 'border': 1, 'reflection': 2}
+
+
+def flow_warp_check(x, flow, interp_mode, padding_mode):
+    """The shape, dtype and mode rules of flow_warp, for GPU and CPU tensors alike: ValueError for a shape or a mode string that does not
+    fit, TypeError for anything but float32.  Returns (interp, padding) as the kernel's codes."""
+    if not isinstance(interp_mode, str) or interp_mode not in WARP_INTERP:
+        raise ValueError(f"flow_warp: interp_mode {interp_mode!r} ('bilinear' or 'nearest')")
+    if not isinstance(padding_mode, str) or padding_mode not in WARP_PADDING:
+        raise ValueError(f"flow_warp: padding_mode {padding_mode!r} ('zeros', 'border' or 'reflection')")
+    if x.dim() != 4 or flow.dim() != 4:
+        raise ValueError('flow_warp: x is (B,C,H,W) and flow (B,H,W,2)')
+    B, C, H, W = x.shape
+    if tuple(flow.shape) != (B, H, W, 2) or min(B, C, H, W) < 1:
+        raise ValueError(f'flow_warp: flow shape {tuple(flow.shape)}, expected {(B, H, W, 2)} for x {tuple(x.shape)}')
+    if H >= 1 << 24 or W >= 1 << 24 or H * W >= 1 << 31:
+        raise ValueError(f'flow_warp: image too large ({H}x{W})')
+    for t, what in ((x, 'x'), (flow, 'flow')):
+        if t.dtype != torch.float32:
+            raise TypeError(f'flow_warp: {what} is {t.dtype}; the op is float32 only')
+    return WARP_INTERP[interp_mode], WARP_PADDING[padding_mode]
+
+
+def flow_warp(x, flow, interp_mode='bilinear', padding_mode='zeros', align_corners=True):
+    """Warp x (B,C,H,W) by the optical flow (B,H,W,2) = (dx, dy), float32: out[b, c, y, x] = the sample of x[b, c] at (x + dx, y + dy); the
+    definition stands in include/codeformer_hip.h (cf_flow_warp).  A torch.channels_last x with C % 4 == 0 is read in place and the result
+    is channels_last too; any other x is read as contiguous NCHW planes (after a copy where it is not contiguous)."""
+    interp, padding = flow_warp_check(x, flow, interp_mode, padding_mode)
+    lib = L.load()
+    B, C, H, W = x.shape
+    x, flow = x.detach(), flow.detach().contiguous()
+    nhwc = C % 4 == 0 and not x.is_contiguous() and _is_channels_last(x)
+    if nhwc:
+        out = torch.empty_like(x)     # (channels_last, like x)
+        nhwc = _is_channels_last(out)
+    if nhwc:
+        xin, dst = x.permute(0, 2, 3, 1), out.permute(0, 2, 3, 1)
+    else:
+        xin = x.contiguous()
+        out = dst = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
+    L.check(lib.cf_flow_warp(L.ptr(xin), L.ptr(flow), L.ptr(dst), B, C, H, W, interp, padding, int(bool(align_corners)), int(nhwc),
+                             L.stream_ptr()), 'cf_flow_warp')
     return out
 
 

@@ -412,6 +412,9 @@ int cf_nhwc_to_nchw(const float* x, int batch, int c, int hw, float* y, cf_strea
  * -> out [batch][h][w][c_pad], channel (ci*s + dy)*s + dx = x[ci][y*s+dy][x*s+dx], channels >= c*s*s zero (c_pad % 16 == 0).
  * s = 1 is a plain NCHW -> zero-padded NHWC conversion. */
 int cf_pixel_unshuffle_nhwc(const float* x, int batch, int c, int h, int w, int s, int c_pad, float* out, cf_stream_t stream);
+/* its inverse with channels-last on both sides (nn.PixelShuffle(s) behind a conv whose output stays NHWC; arch_util.py:95-114 Upsample):
+ * x [batch][h][w][c*s*s] -> out [batch][h*s][w*s][c], out[b][y*s+i][x*s+j][k] = x[b][y][x][(k*s + i)*s + j].  Pure data movement. */
+int cf_pixel_shuffle_nhwc(const float* x, int batch, int c, int h, int w, int s, float* out, cf_stream_t stream);
 
 /* ---- tensor boundary (basicsr/utils/img_util.py:9-35 img2tensor + normalize, :38-94 tensor2img) ---
  * u8 HWC BGR [batch][h][w][3] -> fp32 NCHW RGB in [-1,1] ((x/255 - 0.5)/0.5), and back
@@ -467,6 +470,31 @@ int cf_pack_deform_conv_weight(const float* w, int cout, int cin, int taps, int 
 int cf_deform_conv2d(const float* x, const float* offset, const float* mask, const float* weight, const float* bias, float* out,
                      int batch, int cin, int hin, int win, int cout, int kh, int kw, int stride_h, int stride_w, int pad_h,
                      int pad_w, int dil_h, int dil_w, int groups, int deform_groups, int x_nhwc, int route, cf_stream_t stream);
+
+/* ---- optical-flow warp (basicsr/archs/arch_util.py:117-148 flow_warp; the alignment op next to DCNv2Pack) ---------------------
+ * The reference adds the flow to a mesh grid, normalises by (n - 1) and calls torch's grid_sample, which un-normalises again; here the
+ * round trip is cancelled algebraically.  x fp32 [batch][c][h][w] (x_nhwc = 0) or channels-last [batch][h][w][c] (x_nhwc = 1: c % 4 == 0,
+ * x and out 16-byte aligned), flow fp32 [batch][h][w][2] = (dx, dy), out in the layout of x.  For output pixel (y, x), every step one
+ * fp32 operation, none contracted:
+ *   position    px = (float)x + dx,  py = (float)y + dy
+ *   coordinate  align_corners = 1:  ix = px * ((w-1) / max(w-1, 1))          (px itself; px * 0 when w == 1)
+ *               align_corners = 0:  ix = px * (w / max(w-1, 1)) - 0.5        (the reference normalises by w - 1 in both cases, and that
+ *               quirk is part of the function); the ratio is one fp32 division per launch.  iy likewise with h.
+ *   padding     0 zeros: nothing.   1 border: ix < 0 ? 0 : ix > w-1 ? w-1 : ix.
+ *               2 reflection about [lo, lo + span], (lo, span) = (0, w-1) with align_corners, (-0.5, w) without:  a = |ix - lo|,
+ *               r = fmod(a, span + span) (exact), ix = (r <= span ? r : (span + span) - r) + lo, then the border clamp (span == 0: the
+ *               clamp alone).  It is torch's reflection with the parity of the fold count taken from the exact remainder.
+ *   bilinear    in range when ix > -1 && iy > -1 && ix < w && iy < h; x0 = floor(ix), lw = ix - x0, hw = 1 - lw (lh, hh likewise); the
+ *               corners top-left, top-right, bottom-left, bottom-right weigh hh*hw, hh*lw, lh*hw, lh*lw; a corner outside the image
+ *               contributes +0 and is never read;  out = ((t0 + t1) + t2) + t3, t_i = weight_i * value_i, in that order.
+ *   nearest     (rint(ix), rint(iy)), half to even; the pixel there, 0 when it lies outside the image.
+ * Non-finite positions: every in-range test runs on the fp32 coordinate before any float -> int conversion, and no address is formed
+ * from an unchecked value.  A NaN position samples nothing and gives 0 in EVERY padding mode -- a deliberate choice: torch's result
+ * there is undefined.  +-inf follows the padding rule as written: 0 under zeros, the edge pixel under border, 0 under reflection (the
+ * remainder of an infinite value is NaN); on an axis of one pixel with align_corners the coordinate is inf * 0 = NaN, hence 0.
+ * h, w < 2^24 and h * w < 2^31.  Every argument is checked before anything is launched. */
+int cf_flow_warp(const float* x, const float* flow, float* out, int batch, int c, int h, int w, int interp, int padding, int align_corners,
+                 int x_nhwc, cf_stream_t stream);
 
 /* ---- alignment warp and paste-back of the whole-image / video path ----------------------------------------------------------
  * Replaces the OpenCV calls of facelib/utils/face_restoration_helper.py: cv2.warpAffine of align_warp_face (:343-344) and of
