@@ -1,0 +1,12 @@
+from copy import deepcopy
+
+from codeformer_amd.utils.registry import METRIC_REGISTRY
+from .psnr_ssim import calculate_psnr, calculate_ssim
+
+__all__ = ['calculate_psnr', 'calculate_ssim']
+
+
+def calculate_metric(data, opt):
+    """The metric named by opt['type'] (a METRIC_REGISTRY entry), called with data and the other options as keywords."""
+    opt = deepcopy(opt)
+    return METRIC_REGISTRY.get(opt.pop('type'))(**data, **opt)

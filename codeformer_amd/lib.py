@@ -104,6 +104,9 @@ SIGNATURES = {
     'cf_pack_deform_conv_weight': (_I, [_P, _I, _I, _I, _I, _P, _P]),
     'cf_deform_conv2d': (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 17 + [_P]),
     'cf_flow_warp': (_I, [_P, _P, _P] + [_I] * 8 + [_P]),
+    'cf_metric_parts': (_I, [_I, _I, _I]),
+    'cf_psnr': (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_L), ctypes.POINTER(_L), _I, _I, _P, _P, _P, _P]),
+    'cf_ssim': (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_L), ctypes.POINTER(_L), _I, _I, _P, _P, _P]),
     'cf_warp_affine_u8':(_I, [_P, _L, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'cf_warp_affine_f32': (_I, [_P, _I, _I, ctypes.POINTER(ctypes.c_double), _P, _I, _I, _I, _I, _P]),
     'cf_erode_f32': (_I, [_P, _P, _P, _I, _I, _I, _P]),

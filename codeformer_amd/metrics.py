@@ -1,0 +1,198 @@
+"""PSNR and SSIM of images and image batches (the reference's basicsr/metrics/psnr_ssim.py:9-128 and metric_util.py:6-45).
+
+Two paths, one definition (it also stands at "quality metrics" in include/codeformer_hip.h):
+  host    numpy arrays and CPU tensors: the reference's arithmetic in float64, written out without cv2.
+  device  CUDA (ROCm) tensors, uint8 or float32: the HIP kernels of csrc/cf_metrics.hip through ops.psnr / ops.ssim.  Crop and order are
+          expressed through strides, nothing is copied, and there is no other path for a GPU tensor.
+
+Preparation of both images: reorder_image ((h,w) -> (h,w,1); 'CHW' -> HWC), crop_border pixels off every side, and with test_y_channel a
+3-channel image is BGR and becomes one channel in the reference's float32 rounding (to_y_channel below); everything after that is float64.
+PSNR: sse = sum (a-b)^2 over pixels and channels, mse = sse / N, inf when mse == 0, else 20 log10(255 / sqrt(mse)).  (The reference's Y path
+falls into float32 because its to_y_channel returns float32; here it stays in float64, which moves the result by less than 1e-5 dB.)
+SSIM: the window g[i] = exp(-(i-5)^2 / (2 1.5^2)) / sum = cv2.getGaussianKernel(11, 1.5), applied along the rows and then the columns, valid
+region only (the reference's [5:-5, 5:-5]); C1 = (0.01 255)^2, C2 = (0.03 255)^2; the mean of
+((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)) per channel, then the mean over channels.
+Deviation: an image smaller than 11x11 after the crop raises ValueError (the reference returns the NaN of an empty mean).
+
+calculate_psnr / calculate_ssim keep the reference's positional signature and return a Python float; psnr_batch / ssim_batch are new,
+device-only, and return a (B,) float64 tensor on the device without a synchronisation.
+"""
+import numpy as np
+import torch
+
+from .utils.registry import METRIC_REGISTRY
+
+__all__ = ['calculate_psnr', 'calculate_ssim', 'psnr_batch', 'ssim_batch', 'reorder_image', 'to_y_channel']
+
+ORDERS = ('HWC', 'CHW')
+C1 = (0.01 * 255)**2
+C2 = (0.03 * 255)**2
+
+
+def _check_order(input_order):
+    if input_order not in ORDERS:
+        raise ValueError(f'Wrong input_order {input_order}. Supported input_orders are "HWC" and "CHW"')
+
+
+def reorder_image(img, input_order='HWC'):
+    """(h,w) -> (h,w,1); (c,h,w) with 'CHW' -> (h,w,c); (h,w,c) as it is."""
+    _check_order(input_order)
+    if len(img.shape) == 2:
+        img = img[..., None]
+    if input_order == 'CHW':
+        img = img.transpose(1, 2, 0)
+    return img
+
+
+def to_y_channel(img):
+    """The Y of YCbCr (BT.601) of a BGR image with values in [0, 255], float32 and not rounded to integers; a 1-channel image only takes
+    the float32 round trip.  Every step is one operation: f = float32(v) / float32(255); d = ((f_b 24.966 + f_g 128.553) + f_r 65.481) + 16
+    in float64; Y = float32(float32(d / 255) * float32(255))."""
+    f = img.astype(np.float32) / np.float32(255.)
+    if f.ndim == 3 and f.shape[2] == 3:
+        d = f.astype(np.float64)
+        d = ((d[..., 0] * 24.966 + d[..., 1] * 128.553) + d[..., 2] * 65.481) + 16.0
+        f = (d / 255.).astype(np.float32)[..., None]
+    return f * np.float32(255.)
+
+
+def _prepare(img, crop_border, input_order, test_y_channel):
+    img = reorder_image(img, input_order=input_order).astype(np.float64)
+    if crop_border != 0:
+        img = img[crop_border:-crop_border, crop_border:-crop_border, ...]
+    if test_y_channel:
+        img = to_y_channel(img).astype(np.float64)
+    return img
+
+
+def _psnr_of_sse(sse, count):
+    mse = sse / count
+    if mse == 0:
+        return float('inf')
+    return float(20. * np.log10(255. / np.sqrt(mse)))
+
+
+def gaussian_window():
+    g = np.exp(-(np.arange(11, dtype=np.float64) - 5.)**2 / (2 * 1.5**2))
+    return g / g.sum()
+
+
+def _filter_valid(img, g):
+    """The separable window over the valid region of a (h,w) float64 plane: along the rows, then along the columns, taps in ascending order."""
+    h, w = img.shape
+    rows = np.zeros((h, w - 10))
+    for k in range(11):
+        rows += g[k] * img[:, k:k + w - 10]
+    out = np.zeros((h - 10, w - 10))
+    for k in range(11):
+        out += g[k] * rows[k:k + h - 10]
+    return out
+
+
+def _ssim_plane(img1, img2):
+    g = gaussian_window()
+    mu1, mu2 = _filter_valid(img1, g), _filter_valid(img2, g)
+    mu1_sq, mu2_sq, mu1_mu2 = mu1**2, mu2**2, mu1 * mu2
+    sigma1_sq = _filter_valid(img1**2, g) - mu1_sq
+    sigma2_sq = _filter_valid(img2**2, g) - mu2_sq
+    sigma12 = _filter_valid(img1 * img2, g) - mu1_mu2
+    ssim_map = ((2 * mu1_mu2 + C1) * (2 * sigma12 + C2)) / ((mu1_sq + mu2_sq + C1) * (sigma1_sq + sigma2_sq + C2))
+    return ssim_map.mean()
+
+
+def _host_pair(img1, img2):
+    """numpy arrays of both images when the host path applies (arrays, CPU tensors); None for two device tensors."""
+    t1, t2 = torch.is_tensor(img1), torch.is_tensor(img2)
+    if t1 and t2 and (img1.is_cuda or img2.is_cuda):
+        if img1.device != img2.device:
+            raise ValueError(f'the images lie on different devices ({img1.device}, {img2.device})')
+        return None
+    if (t1 and img1.is_cuda) or (t2 and img2.is_cuda):
+        raise ValueError('one image is a device tensor and the other is not')
+    return tuple(t.detach().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (img1, img2))
+
+
+def _device_view(t, crop_border, input_order):
+    """(1,H,W,C) or (B,H,W,C) view of a device tensor: the order through a permutation, the crop through a slice -- strides only."""
+    if t.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f'device metrics take uint8 or float32 tensors, got {t.dtype}')
+    t = t.detach()
+    if t.dim() == 2:
+        t = t[None, :, :, None]
+    elif t.dim() == 3:
+        t = (t.permute(1, 2, 0) if input_order == 'CHW' else t)[None]
+    elif t.dim() == 4:
+        t = t.permute(0, 2, 3, 1) if input_order == 'CHW' else t
+    else:
+        raise ValueError(f'an image is (h,w), (h,w,c) or (c,h,w) and a batch 4-D, got {tuple(t.shape)}')
+    c = int(crop_border)
+    if c != 0:
+        t = t[:, c:-c, c:-c]
+    if min(t.shape) < 1:
+        raise ValueError(f'nothing is left of the image after crop_border {crop_border}')
+    return t
+
+
+@METRIC_REGISTRY.register()
+def calculate_psnr(img1, img2, crop_border, input_order='HWC', test_y_channel=False):
+    """PSNR of two images with values in [0, 255]: numpy arrays / CPU tensors on the host, uint8 or float32 CUDA tensors ((h,w), (h,w,c) or
+    (c,h,w)) through the HIP kernel.  crop_border pixels on every side take no part; test_y_channel scores the Y channel of a BGR image.
+    A Python float.  The device path reads back the squared-error sum and applies the host path's expression: for uint8 colour inputs the
+    sum is exact and the result has the host path's bits."""
+    assert img1.shape == img2.shape, (f'Image shapes are differnet: {img1.shape}, {img2.shape}.')
+    _check_order(input_order)
+    pair = _host_pair(img1, img2)
+    if pair is None:
+        from . import ops
+        a, b = (_device_view(t, crop_border, input_order) for t in (img1, img2))
+        if img1.dim() == 4:
+            raise ValueError('calculate_psnr takes one image pair (psnr_batch takes batches)')
+        sse, _ = ops.psnr(a, b, test_y_channel)
+        _, H, W, C = a.shape
+        return _psnr_of_sse(float(sse.item()), H * W * (1 if test_y_channel else C))
+    img1, img2 = (_prepare(i, crop_border, input_order, test_y_channel) for i in pair)
+    d = img1 - img2
+    return _psnr_of_sse(float(np.sum(d * d)), d.size)
+
+
+@METRIC_REGISTRY.register()
+def calculate_ssim(img1, img2, crop_border, input_order='HWC', test_y_channel=False):
+    """SSIM of two images with values in [0, 255] (per channel, then averaged); the arguments of calculate_psnr.  A Python float."""
+    assert img1.shape == img2.shape, (f'Image shapes are differnet: {img1.shape}, {img2.shape}.')
+    _check_order(input_order)
+    pair = _host_pair(img1, img2)
+    if pair is None:
+        from . import ops
+        a, b = (_device_view(t, crop_border, input_order) for t in (img1, img2))
+        if img1.dim() == 4:
+            raise ValueError('calculate_ssim takes one image pair (ssim_batch takes batches)')
+        return float(ops.ssim(a, b, test_y_channel).item())
+    img1, img2 = (_prepare(i, crop_border, input_order, test_y_channel) for i in pair)
+    if img1.shape[0] < 11 or img1.shape[1] < 11:
+        raise ValueError(f'the image ({img1.shape[0]}x{img1.shape[1]} after the crop) is smaller than the 11x11 window')
+    return float(np.array([_ssim_plane(img1[..., i], img2[..., i]) for i in range(img1.shape[2])]).mean())
+
+
+def _batch_views(a, b, crop_border, input_order):
+    _check_order(input_order)
+    if not (torch.is_tensor(a) and torch.is_tensor(b) and a.is_cuda and b.is_cuda):
+        raise ValueError('psnr_batch / ssim_batch take CUDA (ROCm) tensors; calculate_psnr / calculate_ssim score host images')
+    if a.device != b.device:
+        raise ValueError(f'the batches lie on different devices ({a.device}, {b.device})')
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f'two 4-D batches of one shape are needed, got {tuple(a.shape)} and {tuple(b.shape)}')
+    return _device_view(a, crop_border, input_order), _device_view(b, crop_border, input_order)
+
+
+def psnr_batch(a, b, crop_border=0, input_order='HWC', test_y_channel=False):
+    """PSNR of every image pair of two device batches -- (B,H,W,C) for 'HWC', (B,C,H,W) for 'CHW', uint8 or float32 with values in
+    [0, 255], any strides -- as a (B,) float64 tensor on the device, without a synchronisation.  (B,512,512,3) uint8 BGR is what
+    CodeFormer.restore_u8 returns."""
+    from . import ops
+    return ops.psnr(*_batch_views(a, b, crop_border, input_order), test_y_channel)[1]
+
+
+def ssim_batch(a, b, crop_border=0, input_order='HWC', test_y_channel=False):
+    """SSIM of every image pair of two device batches; the arguments and the result of psnr_batch."""
+    from . import ops
+    return ops.ssim(*_batch_views(a, b, crop_border, input_order), test_y_channel)

@@ -1443,3 +1443,59 @@ def scale_clear_border_(x, border, scale):
     B, H, W = x.shape
     L.check(lib.cf_scale_clear_border_f32(L.ptr(x), B, H, W, int(border), float(scale), L.stream_ptr()), 'cf_scale_clear_border_f32')
     return x
+
+
+# ---- quality metrics (cf_metrics.hip) -- see codeformer_amd/metrics.py for the public surface -----------------------------------------
+METRIC_DTYPES = {torch.uint8: 0, torch.float32: 1}
+
+
+def _metric_call(a, b, y_channel, ssim_):
+    """The checks and scratch shared by psnr / ssim.  a, b: (B,H,W,C) VIEWS (any strides: a crop, a permuted CHW tensor, a slice)."""
+    if not (a.is_cuda and b.is_cuda):
+        raise ValueError('codeformer_amd ops need CUDA (ROCm) tensors')
+    if a.device != b.device:
+        raise ValueError(f'metrics: the images lie on different devices ({a.device}, {b.device})')
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f'metrics: two (B,H,W,C) views of one shape are needed, got {tuple(a.shape)} and {tuple(b.shape)}')
+    if a.dtype not in METRIC_DTYPES or b.dtype != a.dtype:
+        raise TypeError(f'metrics: both images must be uint8 or both float32, got {a.dtype} and {b.dtype}')
+    B, H, W, C = a.shape
+    if C not in (1, 3) or min(B, H, W) < 1:
+        raise ValueError(f'metrics: shape {tuple(a.shape)} (B,H,W,C) needs C in (1, 3) and no empty dimension')
+    if ssim_ and (H < 11 or W < 11):
+        raise ValueError(f'ssim: the image ({H}x{W}) is smaller than the 11x11 window')
+    for t in (a, b):
+        if sum((n - 1) * s for n, s in zip(t.shape, t.stride())) >= 1 << 31:
+            raise ValueError('metrics: the largest element offset of an image reaches 2^31')
+    lib = L.ensure_device(a.device)
+    planes = 1 if y_channel else C
+    nparts = lib.cf_metric_parts(H, W, planes)
+    if nparts < 0:
+        raise RuntimeError(f'cf_metric_parts failed: {L.last_error()}')
+    parts = torch.empty(B * nparts, dtype=torch.float64, device=a.device)
+    strides = [(ctypes.c_int64 * 4)(*t.stride()) for t in (a, b)]
+    return lib, parts, strides, METRIC_DTYPES[a.dtype]
+
+
+def psnr(a, b, y_channel=False):
+    """(sse, psnr): two (B,) float64 tensors -- the squared-error sum of every image pair of the (B,H,W,C) views a, b (uint8 or float32,
+    values in [0, 255]) and its PSNR; the definition stands at cf_psnr in include/codeformer_hip.h.  No copy, no synchronisation."""
+    lib, parts, (sa, sb), dt = _metric_call(a, b, y_channel, False)
+    B, H, W, C = a.shape
+    with torch.cuda.device(a.device):
+        out = torch.empty(2, B, dtype=torch.float64, device=a.device)
+        L.check(lib.cf_psnr(a.data_ptr(), b.data_ptr(), B, H, W, C, sa, sb, dt, int(bool(y_channel)), L.ptr(parts, dtype=torch.float64),
+                            out[0].data_ptr(), out[1].data_ptr(), L.stream_ptr()), 'cf_psnr')
+    return out[0], out[1]
+
+
+def ssim(a, b, y_channel=False):
+    """(B,) float64: the SSIM of every image pair of the (B,H,W,C) views a, b (cf_ssim in include/codeformer_hip.h).  No copy, no
+    synchronisation."""
+    lib, parts, (sa, sb), dt = _metric_call(a, b, y_channel, True)
+    B, H, W, C = a.shape
+    with torch.cuda.device(a.device):
+        out = torch.empty(B, dtype=torch.float64, device=a.device)
+        L.check(lib.cf_ssim(a.data_ptr(), b.data_ptr(), B, H, W, C, sa, sb, dt, int(bool(y_channel)), L.ptr(parts, dtype=torch.float64),
+                            L.ptr(out, dtype=torch.float64), L.stream_ptr()), 'cf_ssim')
+    return out

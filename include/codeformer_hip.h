@@ -496,6 +496,33 @@ int cf_deform_conv2d(const float* x, const float* offset, const float* mask, con
 int cf_flow_warp(const float* x, const float* flow, float* out, int batch, int c, int h, int w, int interp, int padding, int align_corners,
                  int x_nhwc, cf_stream_t stream);
 
+/* ---- quality metrics: PSNR and SSIM of image batches (basicsr/metrics/psnr_ssim.py:9-128, metric_util.py:6-45) ------------------
+ * Added without a version bump: the three exports are additive and CF_ABI_VERSION stays 22.
+ * a and b are two images of the same shape, uint8 (dtype 0) or float32 (dtype 1) with values in [0, 255], `batch` of them, h x w pixels,
+ * channels 1 or 3.  Element (n, y, x, ch) of image a lies at a[n*stride_a[0] + y*stride_a[1] + x*stride_a[2] + ch*stride_a[3]] (element
+ * strides in HOST memory, 4 each, non-negative): HWC, CHW, a border crop and a slice of a larger tensor are all the same call, with no copy.
+ * Values: without y_channel the element itself, in fp64.  With y_channel a 3-channel image is BGR and becomes ONE plane
+ *   f = float32(v) / float32(255) per channel;  d = ((f_b*24.966 + f_g*128.553) + f_r*65.481) + 16.0 in fp64, each operation rounded on its
+ *   own and in this order;  Y = float32(float32(d / 255.0) * float32(255))
+ * (bgr2ycbcr(y_only) of basicsr/utils/matlab_functions.py as to_y_channel calls it), and a 1-channel image float32(float32(v)/255 * 255).
+ * Everything after that is fp64.  planes = 1 with y_channel, else channels.
+ *   cf_psnr   sse[n] = sum (a - b)^2 over pixels and planes; psnr[n] (may be NULL) = inf when sse == 0, else 20 log10(255 / sqrt(sse / N)),
+ *             N = h*w*planes.  For uint8 inputs without y_channel sse is exact.
+ *   cf_ssim   window g[i] = exp(-(i-5)^2 / (2 * 1.5^2)) / sum, applied along the rows and then along the columns, valid region only
+ *             ((h-10) x (w-10) outputs: h, w >= 11); C1 = (0.01*255)^2, C2 = (0.03*255)^2; with mu = g*a etc.
+ *             map = ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)), s1 = g*a^2 - mu1^2, s2 likewise, s12 = g*ab - mu1 mu2;
+ *             ssim[n] = the mean over planes of the mean of the plane's map.  fp64 throughout.
+ * Reductions are deterministic and batch-invariant: every workgroup writes one fp64 partial to a slot of `parts` that depends only on
+ * (image, plane, tile), a second launch adds an image's partials in a fixed order, the tiling depends on (h, w) only and there are no
+ * floating-point atomics.  parts: batch * cf_metric_parts(h, w, planes) doubles of scratch (what either call needs at most; h, w below 11
+ * count the squared-error strips alone).  The largest element offset of an image must stay below 2^31.
+ * Every argument is checked before anything is launched. */
+int cf_metric_parts(int h, int w, int channels); /* -1: bad arguments */
+int cf_psnr(const void* a, const void* b, int batch, int h, int w, int channels, const int64_t* stride_a, const int64_t* stride_b, int dtype,
+            int y_channel, double* parts, double* sse, double* psnr, cf_stream_t stream);
+int cf_ssim(const void* a, const void* b, int batch, int h, int w, int channels, const int64_t* stride_a, const int64_t* stride_b, int dtype,
+            int y_channel, double* parts, double* ssim, cf_stream_t stream);
+
 /* ---- alignment warp and paste-back of the whole-image / video path ----------------------------------------------------------
  * Replaces the OpenCV calls of facelib/utils/face_restoration_helper.py: cv2.warpAffine of align_warp_face (:343-344) and of
  * paste_faces_to_input_image (:400, :428, :479), cv2.erode (:430-431, :447), cv2.GaussianBlur (:449), np.sum (:433), the soft-mask

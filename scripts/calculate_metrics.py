@@ -1,0 +1,83 @@
+"""PSNR and SSIM of a directory of restored images against their ground truth.
+
+  python scripts/calculate_metrics.py --restored DIR --gt DIR [--crop_border N] [--test_y_channel] [--batch 16] [--json OUT]
+
+PNGs are paired by file name and read as uint8 BGR (img_util.imread_bgr).  On a GPU, images of one size are scored in device batches
+(metrics.psnr_batch / ssim_batch: the HIP kernels); without one the host definition runs image by image.  One line per file, then the
+means.  A file without a partner in the other directory and a pair of different sizes are errors that name the file.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from basicsr.metrics import calculate_psnr, calculate_ssim  # noqa: E402
+from basicsr.metrics.psnr_ssim import psnr_batch, ssim_batch  # noqa: E402
+from basicsr.utils.img_util import imread_bgr  # noqa: E402
+
+
+def _pngs(d):
+    if not os.path.isdir(d):
+        raise SystemExit(f'error: {d} is not a directory')
+    return sorted(f for f in os.listdir(d) if f.lower().endswith('.png'))
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    p.add_argument('--restored', required=True)
+    p.add_argument('--gt', required=True)
+    p.add_argument('--crop_border', type=int, default=0)
+    p.add_argument('--test_y_channel', action='store_true')
+    p.add_argument('--batch', type=int, default=16, help='images per device batch')
+    p.add_argument('--json', default=None, help='also write the per-file values and the means here')
+    args = p.parse_args(argv)
+    names, gt = _pngs(args.restored), set(_pngs(args.gt))
+    for n in names:
+        if n not in gt:
+            raise SystemExit(f'error: {n} has no ground truth in {args.gt}')
+    for n in sorted(gt - set(names)):
+        raise SystemExit(f'error: {n} has no restored image in {args.restored}')
+    if not names:
+        raise SystemExit(f'error: no PNG files in {args.restored}')
+    pairs = []
+    for n in names:
+        a, b = imread_bgr(os.path.join(args.restored, n)), imread_bgr(os.path.join(args.gt, n))
+        if a.shape != b.shape:
+            raise SystemExit(f'error: {n}: restored is {a.shape[1]}x{a.shape[0]}, ground truth {b.shape[1]}x{b.shape[0]}')
+        pairs.append((n, a, b))
+    opt = dict(crop_border=args.crop_border, input_order='HWC', test_y_channel=args.test_y_channel)
+    result = {}
+    if torch.cuda.is_available():
+        by_size = {}
+        for item in pairs:
+            by_size.setdefault(item[1].shape, []).append(item)
+        for group in by_size.values():
+            for i in range(0, len(group), max(1, args.batch)):
+                chunk = group[i:i + max(1, args.batch)]
+                a = torch.from_numpy(np.stack([c[1] for c in chunk])).cuda()
+                b = torch.from_numpy(np.stack([c[2] for c in chunk])).cuda()
+                ps, ss = psnr_batch(a, b, **opt).tolist(), ssim_batch(a, b, **opt).tolist()
+                for (n, _, _), pv, sv in zip(chunk, ps, ss):
+                    result[n] = {'psnr': pv, 'ssim': sv}
+    else:
+        for n, a, b in pairs:
+            result[n] = {'psnr': calculate_psnr(a, b, **opt), 'ssim': calculate_ssim(a, b, **opt)}
+    for n in names:
+        print(f'{n}\tPSNR {result[n]["psnr"]:.6f} dB\tSSIM {result[n]["ssim"]:.6f}')
+    mean = {k: float(np.mean([result[n][k] for n in names])) for k in ('psnr', 'ssim')}
+    print(f'mean of {len(names)}\tPSNR {mean["psnr"]:.6f} dB\tSSIM {mean["ssim"]:.6f}')
+    if args.json:
+        with open(args.json, 'w') as fh:
+            json.dump({'files': result, 'mean': mean, 'crop_border': args.crop_border, 'test_y_channel': args.test_y_channel}, fh, indent=1)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
