@@ -10,3 +10,8 @@ def calculate_metric(data, opt):
     """The metric named by opt['type'] (a METRIC_REGISTRY entry), called with data and the other options as keywords."""
     opt = deepcopy(opt)
     return METRIC_REGISTRY.get(opt.pop('type'))(**data, **opt)
+
+
+from codeformer_amd.metrics import calculate_identity, identity_batch, identity_input, load_arcface  # noqa: E402
+
+__all__ += ['calculate_identity', 'identity_batch', 'identity_input', 'load_arcface']

@@ -115,9 +115,12 @@ __device__ __forceinline__ float swishf(float y) { return y * (1.0f / (1.0f + ex
 // load, the vector epilogue rounds once (RNE) after the GroupNorm partials were taken.  Only the instantiations the bf16 mode runs from
 // 64x64 pixels up exist (direct bf16 3x3 with 64 output channels, folded upsample, fp32 1x1 on images); every other one is untouched.
 template <int TAPS, int STRIDE, int WM, int WN, int MI, int NI, bool IN_NCHW, bool BF16 = false, bool EXT = false, bool F16 = false,
-          bool SK = false, bool BIO = false>
+          bool SK = false, bool BIO = false, bool PRELU = false>
 __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) {
   using C = Cfg<TAPS, STRIDE, WM, WN, MI, NI>;
+  // PRELU: the general instantiations that carry the two PReLU epilogues and nothing else.  They are kernels of their own, so every other
+  // instantiation is the code it was before those epilogues existed.
+  static_assert(!PRELU || (EXT && TAPS == 9 && !BF16 && !F16), "PReLU epilogues: general fp32 3x3 instantiations");
   static_assert(!BIO || (!IN_NCHW && !EXT && !SK && !F16 && STRIDE == 1), "bf16 tensors: dense NHWC stride-1 instantiations only");
   static_assert(!SK || (TAPS == 1 && !EXT && !BF16 && !F16), "split-K: 1x1 / Linear fp32 instantiations");
   constexpr bool LP = BF16 || F16;  // 16-bit MFMA operands
@@ -716,7 +719,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
           if (CF_LIVE(p) && (EPI == CF_EPI_RESIDUAL || EPI == CF_EPI_SFT)) r0[p] = cf_load4_bf16(a.res, offs[p]);
           if (CF_LIVE(p) && EPI == CF_EPI_SFT) r1[p] = cf_load4_bf16(a.sft_scale, offs[p]);
         } else {
-        if (CF_LIVE(p) && (EPI == CF_EPI_RESIDUAL || EPI == CF_EPI_SFT || EPI == CF_EPI_AXPY || EPI == CF_EPI_AXPY2))
+        if (CF_LIVE(p) && (EPI == CF_EPI_RESIDUAL || EPI == CF_EPI_SFT || EPI == CF_EPI_AXPY || EPI == CF_EPI_AXPY2 || EPI == CF_EPI_RES_PRELU))
           r0[p] = *reinterpret_cast<const f32x4*>(a.res + offs[p]);
         if (CF_LIVE(p) && (EPI == CF_EPI_SFT || EPI == CF_EPI_AXPY2)) r1[p] = *reinterpret_cast<const f32x4*>(a.sft_scale + offs[p]);
         }
@@ -758,6 +761,14 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
             for (int e = 0; e < 4; ++e) {
               v[e] = __fadd_rn(__fmul_rn(v[e], a.sft_w), x[e]);
               if (EPI == CF_EPI_AXPY2) v[e] = __fadd_rn(__fmul_rn(v[e], a.sft_w), xx[e]);
+            }
+          } else if (EPI == CF_EPI_PRELU || EPI == CF_EPI_RES_PRELU) {
+            // nn.PReLU with one learned slope of any sign or size (arcface_arch.py:73,87,98): a select, never max(x, a * x)
+            const f32x4 rr = r0[p];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float t = EPI == CF_EPI_RES_PRELU ? __fadd_rn(v[e], rr[e]) : v[e];
+              v[e] = t > 0.f ? t : __fmul_rn(a.sft_w, t);
             }
           }
           if constexpr (BIO) cf_store4_bf16(a.out, o, v);   // (rounded here, once; the statistics below see the fp32 values)
@@ -852,7 +863,10 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const ArgsOf<EXT, SK> a) 
       }
     }
   };
-  if constexpr (EXT) {  // host guarantees NHWC output with cout % 4 == 0
+  if constexpr (PRELU) {  // host guarantees one of the two codes, NHWC output with cout % 4 == 0
+    if (a.epilogue == CF_EPI_RES_PRELU) epilogue_vec(std::integral_constant<int, CF_EPI_RES_PRELU>{});
+    else epilogue_vec(std::integral_constant<int, CF_EPI_PRELU>{});
+  } else if constexpr (EXT) {  // host guarantees NHWC output with cout % 4 == 0
     switch (a.epilogue) {
       case CF_EPI_RESIDUAL: epilogue_vec(std::integral_constant<int, CF_EPI_RESIDUAL>{}); break;
       case CF_EPI_LEAKY: epilogue_vec(std::integral_constant<int, CF_EPI_LEAKY>{}); break;
@@ -1130,7 +1144,7 @@ int conv1x1_mtiles(const ConvArgsExt& a, int bm) {
   return 0;
 }
 
-template <int TAPS, int STRIDE, int WM, int WN, int MI, int NI, bool IN_NCHW, bool BF16 = false, bool EXT = false, bool F16 = false, bool BIO = false>
+template <int TAPS, int STRIDE, int WM, int WN, int MI, int NI, bool IN_NCHW, bool BF16 = false, bool EXT = false, bool F16 = false, bool BIO = false, bool PRELU = false>
 int launch(const ConvArgsExt& a, hipStream_t stream, int* parts_query) {
   using C = Cfg<TAPS, STRIDE, WM, WN, MI, NI>;
   ArgsOf<EXT> k = a;  // (slices the stride fields off for the CodeFormer instantiations)
@@ -1156,7 +1170,7 @@ int launch(const ConvArgsExt& a, hipStream_t stream, int* parts_query) {
     return CF_OK;
   }
   k.ntn = a.cout_pad / C::BN;
-  constexpr auto kern = igemm_kernel<TAPS, STRIDE, WM, WN, MI, NI, IN_NCHW, BF16, EXT, F16, false, BIO>;
+  constexpr auto kern = igemm_kernel<TAPS, STRIDE, WM, WN, MI, NI, IN_NCHW, BF16, EXT, F16, false, BIO, PRELU>;
   constexpr size_t lds = C::LDS_FLOATS * sizeof(float);
   CF_LDS_ATTR(kern, lds);  // (cf_device_init sets the dynamic-LDS attribute on each device)
   hipLaunchKernelGGL(kern, dim3(mtiles * k.ntn), dim3(256), lds, stream, k);
@@ -1232,10 +1246,10 @@ static int conv_validate(const cf_conv_desc* d, const int* pq, ConvFacts& f) {
                    d->cout_pad % (d->bf16_mfma == CF_OPERAND_F16 ? 32 : 64) == 0 && d->cout % 4 == 0,
                "cf_conv2d: bf16_mfma covers 3x3 stride-1 NHWC convs with channels %% 32 == 0 (c0=%d c1=%d cout_pad=%d)", d->c0,
                d->c1, d->cout_pad);
-  CF_REQUIRE(d->prologue >= 0 && d->prologue <= 3 && d->epilogue >= 0 && d->epilogue <= CF_EPI_AXPY2, "cf_conv2d: bad pro/epilogue");
+  CF_REQUIRE(d->prologue >= 0 && d->prologue <= 3 && d->epilogue >= 0 && d->epilogue <= CF_EPI_RES_PRELU, "cf_conv2d: bad pro/epilogue");
   if (d->prologue == CF_PRO_AFFINE || d->prologue == CF_PRO_AFFINE_SWISH)
     CF_REQUIRE(d->pro_scale && d->pro_shift, "cf_conv2d: affine prologue without scale/shift tables");
-  if (d->epilogue == CF_EPI_RESIDUAL || d->epilogue == CF_EPI_SFT || d->epilogue == CF_EPI_AXPY || d->epilogue == CF_EPI_AXPY2)
+  if (d->epilogue == CF_EPI_RESIDUAL || d->epilogue == CF_EPI_SFT || d->epilogue == CF_EPI_AXPY || d->epilogue == CF_EPI_AXPY2 || d->epilogue == CF_EPI_RES_PRELU)
     CF_REQUIRE(d->res, "cf_conv2d: epilogue needs res");
   if (d->epilogue == CF_EPI_SFT) CF_REQUIRE(d->sft_scale, "cf_conv2d: SFT epilogue needs sft_scale");
   if (d->epilogue == CF_EPI_AXPY2) CF_REQUIRE(d->sft_scale, "cf_conv2d: AXPY2 epilogue needs res2 (sft_scale)");
@@ -1261,10 +1275,14 @@ static int conv_validate(const cf_conv_desc* d, const int* pq, ConvFacts& f) {
                    !d->out_nchw && d->bf16_mfma != CF_OPERAND_BF16 && !d->stats_out &&
                    !(pq && d->stats_cpg) && d->cout % 4 == 0 && d->epilogue != CF_EPI_SFT && d->epilogue != CF_EPI_GELU,
                "cf_conv2d: strided slices / leaky|axpy epilogues / off-grid sizes (%dx%d) need a 3x3 stride-1 fp32 / f16-operand NHWC conv with "
-               "cout %% 4 == 0, no statistics, epilogue in {none, residual, leaky, axpy, axpy2}", d->hout, d->wout);
+               "cout %% 4 == 0, no statistics, epilogue in {none, residual, leaky, axpy, axpy2, prelu, res_prelu}", d->hout, d->wout);
     CF_REQUIRE(ld0 % 4 == 0 && ld1 % 4 == 0 && ldo % 4 == 0, "cf_conv2d: channel strides must be multiples of 4 floats");
+    CF_REQUIRE(d->epilogue < CF_EPI_PRELU || (d->bf16_mfma == CF_OPERAND_F32 && !d->upsample),
+               "cf_conv2d: the PReLU epilogues are built for plain 3x3 convs with fp32 operands (operand %d, upsample %d)", d->bf16_mfma, d->upsample);
   } else {
     CF_REQUIRE(!few_cout || ld0 == d->c0, "cf_conv2d: the NCHW <=4-channel output conv reads a dense input");
+    CF_REQUIRE(d->epilogue < CF_EPI_PRELU, "cf_conv2d: the PReLU epilogues belong to the general fp32 / f16-operand 3x3 instantiations (winograd %d, operand %d)",
+               d->winograd, d->bf16_mfma);
   }
   CF_REQUIRE(!(d->out_nchw && (d->taps != 9 || d->epilogue != CF_EPI_NONE)), "cf_conv2d: out_nchw needs 3x3, no epilogue");
   CF_REQUIRE(d->cout_pad >= d->cout && d->cout_pad % 32 == 0, "cf_conv2d: cout_pad %d invalid for cout %d", d->cout_pad,
@@ -1377,6 +1395,14 @@ static int launch_few_cout(ConvArgsExt& a, const cf_conv_desc* d, hipStream_t st
 static int launch_direct(ConvArgsExt& a, const cf_conv_desc* d, const ConvFacts& f, hipStream_t stream, int* pq) {
   const int cp = d->cout_pad;
   const bool f16 = d->bf16_mfma == CF_OPERAND_F16, bf16 = d->bf16_mfma == CF_OPERAND_BF16;
+  if (f.ext && d->epilogue >= CF_EPI_PRELU) {  // the PReLU instantiations (fp32 operands, plain 3x3: checked); 64-wide channel tiles on small
+    // images as in the dense kernels (`narrow`: per-image shape only), otherwise the tiles of the general rungs below
+    if (d->stride == 2) return launch<9, 2, 2, 2, 2, 2, false, false, true, false, false, true>(a, stream, pq);  // cout_pad % 128 == 0 (checked)
+    if (f.narrow) return launch<9, 1, 2, 2, 2, 1, false, false, true, false, false, true>(a, stream, pq);
+    if (cp % 128 == 0) return launch<9, 1, 2, 2, 2, 2, false, false, true, false, false, true>(a, stream, pq);
+    if (cp % 64 == 0) return launch<9, 1, 4, 1, 2, 2, false, false, true, false, false, true>(a, stream, pq);
+    return launch<9, 1, 4, 1, 2, 1, false, false, true, false, false, true>(a, stream, pq);  // cout_pad % 32 == 0 (checked)
+  }
   if (f.ext) {  // the general instantiations; their rungs follow no common ladder
     if (d->stride == 2) return launch<9, 2, 2, 2, 2, 2, false, false, true>(a, stream, pq);  // fp32, cout_pad % 128 == 0 (checked)
     if (d->upsample) {

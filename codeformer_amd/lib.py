@@ -16,7 +16,7 @@ c_float_p = ctypes.c_void_p  # device pointers are passed as integers
 
 ABI_VERSION = 22
 PRO_NONE, PRO_AFFINE, PRO_AFFINE_SWISH, PRO_LEAKY = 0, 1, 2, 3
-EPI_NONE, EPI_RESIDUAL, EPI_SFT, EPI_GELU, EPI_LEAKY, EPI_AXPY, EPI_AXPY2 = 0, 1, 2, 3, 4, 5, 6
+EPI_NONE, EPI_RESIDUAL, EPI_SFT, EPI_GELU, EPI_LEAKY, EPI_AXPY, EPI_AXPY2, EPI_PRELU, EPI_RES_PRELU = 0, 1, 2, 3, 4, 5, 6, 7, 8
 PAD_ZERO, PAD_REFLECT, PAD_EDGE = 0, 1, 2
 
 
@@ -107,6 +107,15 @@ SIGNATURES = {
     'cf_metric_parts': (_I, [_I, _I, _I]),
     'cf_psnr': (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_L), ctypes.POINTER(_L), _I, _I, _P, _P, _P, _P]),
     'cf_ssim': (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_L), ctypes.POINTER(_L), _I, _I, _P, _P, _P]),
+    'cf_prelu_maxpool2': (_I, [_P, _I, _I, _I, _I, _F, _P, _P]),
+    'cf_se_pool_parts': (_I, [_I]),
+    'cf_se_pool': (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    'cf_se_gate': (_I, [_P, _P, _P, _F, _P, _P, _I, _I, _I, _P, _P]),
+    'cf_se_scale_res_prelu': (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P]),
+    'cf_fc_rows_workspace_elems': (_L, [_I, _I, _I]),
+    'cf_fc_rows': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    'cf_identity_input': (_I, [_P, _I, _I, _I, ctypes.POINTER(_L), _I, _I, _P, _P]),
+    'cf_cosine_rows': (_I, [_P, _P, _I, _I, _P, _P]),
     'cf_warp_affine_u8':(_I, [_P, _L, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'cf_warp_affine_f32': (_I, [_P, _I, _I, ctypes.POINTER(ctypes.c_double), _P, _I, _I, _I, _I, _P]),
     'cf_erode_f32': (_I, [_P, _P, _P, _I, _I, _I, _P]),

@@ -16,13 +16,21 @@ Deviation: an image smaller than 11x11 after the crop raises ValueError (the ref
 
 calculate_psnr / calculate_ssim keep the reference's positional signature and return a Python float; psnr_batch / ssim_batch are new,
 device-only, and return a (B,) float64 tensor on the device without a synchronisation.
+
+Identity preservation, the third full-reference score of face restoration: the cosine similarity of the ArcFace embeddings
+(archs/arcface_arch.py ResNetArcFace) of the restored face and the ground truth.  identity_input is the image front end, stated as a
+definition ("ArcFace / identity metric" in include/codeformer_hip.h): RGB in [-1, 1], gray = 0.2989 R + 0.5870 G + 0.1140 B, then a bilinear
+resize to 128 x 128 with half-pixel centres, edge clamp and no antialiasing -- gray first, resize second, every step one float32 operation,
+so the host definition (torch ops on the CPU) and the kernel give the same bits.  identity_batch / calculate_identity / load_arcface
+follow; no trained ArcFace checkpoint ships with or was run through this code.
 """
 import numpy as np
 import torch
 
 from .utils.registry import METRIC_REGISTRY
 
-__all__ = ['calculate_psnr', 'calculate_ssim', 'psnr_batch', 'ssim_batch', 'reorder_image', 'to_y_channel']
+__all__ = ['calculate_psnr', 'calculate_ssim', 'psnr_batch', 'ssim_batch', 'reorder_image', 'to_y_channel', 'identity_input', 'identity_batch',
+           'calculate_identity', 'load_arcface']
 
 ORDERS = ('HWC', 'CHW')
 C1 = (0.01 * 255)**2
@@ -196,3 +204,122 @@ def ssim_batch(a, b, crop_border=0, input_order='HWC', test_y_channel=False):
     """SSIM of every image pair of two device batches; the arguments and the result of psnr_batch."""
     from . import ops
     return ops.ssim(*_batch_views(a, b, crop_border, input_order), test_y_channel)
+
+
+# ---- identity preservation ----------------------------------------------------------------------------------------------------------------
+ID_SIZE = 128
+GRAY = (0.2989, 0.5870, 0.1140)
+
+
+def _identity_view(img, order):
+    """(B,H,W,3) view of a tensor: uint8 BGR or float32 RGB in [0, 1], one image or a batch, 'HWC' or 'CHW' -- strides only."""
+    _check_order(order)
+    if img.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f'identity_input takes uint8 (BGR) or float32 (RGB in [0, 1]) images, got {img.dtype}')
+    t = img.detach()
+    if t.dim() == 3:
+        t = t[None]
+    if t.dim() != 4:
+        raise ValueError(f'an image is (h,w,3) or (3,h,w) and a batch 4-D, got {tuple(img.shape)}')
+    if order == 'CHW':
+        t = t.permute(0, 2, 3, 1)
+    if t.shape[3] != 3 or min(t.shape) < 1:
+        raise ValueError(f'identity_input needs 3-channel images, got {tuple(img.shape)} with order {order}')
+    return t
+
+
+def _axis_host(n):
+    """Source indices and weights of the 128 output positions along an axis of n pixels: src = (o + 0.5) * (n / 128) - 0.5, clamped at 0."""
+    o = torch.arange(ID_SIZE, dtype=torch.float32)
+    scale = torch.tensor(float(n), dtype=torch.float32) / torch.tensor(float(ID_SIZE), dtype=torch.float32)
+    src = (o + 0.5) * scale
+    src = (src - 0.5).clamp_min(0.)
+    f = torch.floor(src)
+    lo = src - f
+    i0 = f.long().clamp(0, n - 1)
+    return i0, (i0 + 1).clamp_max(n - 1), lo, 1.0 - lo
+
+
+def identity_gray_host(t):
+    """(B,H,W,3) CPU view -> (B,H,W) float32 gray of the RGB image in [-1, 1]."""
+    f = t.to(torch.float32) / torch.tensor(255., dtype=torch.float32) if t.dtype == torch.uint8 else t
+    v = f * 2.0
+    v = v - 1.0
+    r, g, b = (v[..., 2], v[..., 1], v[..., 0]) if t.dtype == torch.uint8 else (v[..., 0], v[..., 1], v[..., 2])
+    return (GRAY[0] * r + GRAY[1] * g) + GRAY[2] * b
+
+
+def _identity_input_host(t):
+    gray = identity_gray_host(t)
+    y0, y1, ly, hy = _axis_host(t.shape[1])
+    x0, x1, lx, hx = _axis_host(t.shape[2])
+    top, bot = gray[:, y0], gray[:, y1]
+    top = hx * top[:, :, x0] + lx * top[:, :, x1]
+    bot = hx * bot[:, :, x0] + lx * bot[:, :, x1]
+    return (hy[:, None] * top + ly[:, None] * bot)[:, None].contiguous()
+
+
+def identity_input(img, order='HWC'):
+    """The input of the identity network, (B,1,128,128) float32, from uint8 BGR images ((B,H,W,3): what CodeFormer.restore_u8 returns) or
+    float32 RGB images in [0, 1] ((B,H,W,3), or (B,3,H,W) with order 'CHW'); one image gives B = 1.  CUDA tensors go through one HIP launch
+    that reads the image through its strides (a crop or a slice needs no copy); numpy arrays and CPU tensors take the host definition, whose
+    bits the kernel reproduces."""
+    if not torch.is_tensor(img):
+        img = torch.from_numpy(np.ascontiguousarray(img))
+    t = _identity_view(img, order)
+    if t.is_cuda:
+        from . import ops
+        return ops.identity_input(t, bgr=t.dtype == torch.uint8)
+    return _identity_input_host(t)
+
+
+def _cosine_host(x, y):
+    x, y = x.double(), y.double()
+    den = (x.norm(dim=1) * y.norm(dim=1)).clamp_min(1e-8)
+    return (x * y).sum(dim=1) / den
+
+
+def identity_batch(a, b, net, order='HWC'):
+    """Identity preservation of every image pair of two batches: cosine(net(identity_input(a)), net(identity_input(b))) as a (B,) float64
+    tensor on the inputs' device, the cosine x.y / max(|x| |y|, 1e-8) taken in float64 from the float32 embeddings.  On the device nothing
+    is copied to the host and nothing synchronises; both batches pass the network in one call (row r of a batch is bitwise the call on r alone)."""
+    xa, xb = identity_input(a, order), identity_input(b, order)
+    if xa.shape != xb.shape or xa.device != xb.device:
+        raise ValueError(f'two batches of one size on one device are needed, got {tuple(xa.shape)} on {xa.device} and {tuple(xb.shape)} on {xb.device}')
+    n = xa.shape[0]
+    with torch.no_grad():
+        e = net(torch.cat([xa, xb], 0))
+    if e.is_cuda:
+        from . import ops
+        return ops.cosine_rows(e[:n], e[n:])
+    return _cosine_host(e[:n], e[n:])
+
+
+@METRIC_REGISTRY.register()
+def calculate_identity(img1, img2, net, input_order='HWC'):
+    """Identity preservation of one image pair ((h,w,3) or (3,h,w); uint8 BGR or float32 RGB in [0, 1]) under the embedding network `net`
+    (load_arcface).  numpy arrays and CPU tensors take the host path, CUDA tensors the HIP path.  A Python float."""
+    for i in (img1, img2):
+        if len(i.shape) != 3:
+            raise ValueError('calculate_identity takes one image pair (identity_batch takes batches)')
+    return float(identity_batch(img1, img2, net, input_order)[0].item())
+
+
+def load_arcface(path=None, device=None):
+    """ResNetArcFace('IRBlock', [2, 2, 2, 2], use_se=False) in eval mode -- the configuration identity scoring uses -- with the checkpoint at
+    `path` loaded if one is given ('params_ema' / 'params' wrappers and a leading 'module.' of the keys are removed).  Nothing is
+    downloaded: a missing file raises FileNotFoundError.  Without a path the weights are the seeded-by-the-caller random initialisation."""
+    import os
+    from .archs.arcface_arch import ResNetArcFace
+    net = ResNetArcFace('IRBlock', [2, 2, 2, 2], use_se=False)
+    if path is not None:
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f'ArcFace checkpoint {path} not found (nothing is downloaded)')
+        state = torch.load(path, map_location='cpu', weights_only=True)
+        for k in ('params_ema', 'params'):
+            if isinstance(state, dict) and k in state:
+                state = state[k]
+                break
+        net.load_state_dict({(k[7:] if k.startswith('module.') else k): v for k, v in state.items()}, strict=True)
+    net.eval()
+    return net.to(device) if device is not None else net

@@ -12,7 +12,7 @@ import weakref
 import torch
 
 from . import lib as L
-from .lib import (EPI_AXPY, EPI_AXPY2, EPI_GELU, EPI_LEAKY, EPI_NONE, EPI_RESIDUAL, EPI_SFT, PRO_AFFINE, PRO_AFFINE_SWISH,
+from .lib import (EPI_AXPY, EPI_AXPY2, EPI_GELU, EPI_LEAKY, EPI_NONE, EPI_PRELU, EPI_RES_PRELU, EPI_RESIDUAL, EPI_SFT, PRO_AFFINE, PRO_AFFINE_SWISH,
                   PAD_EDGE, PAD_REFLECT, PAD_ZERO, PRO_LEAKY, PRO_NONE)
 
 GN_GROUPS = 32
@@ -651,7 +651,7 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     check of this function has passed: a call refused with ValueError / TypeError leaves the state alone.  Statistics attached here
     carry the stamp of `out`; outside inference_mode a later in-place write by the caller (y.mul_(), y.copy_()) retires them, under
     inference_mode such a write cannot be seen.
-    EPI_LEAKY / EPI_AXPY / EPI_AXPY2 use sft_w as alpha (see cf_epilogue in the header).
+    EPI_AXPY / EPI_AXPY2 / EPI_PRELU / EPI_RES_PRELU use sft_w as alpha (see cf_epilogue in the header; EPI_LEAKY's slope is the constant 0.2).
     sft_w with EPI_SFT: a float, or a contiguous float32 tensor of B values on x's device -- one weight per image (cf_conv2d_sft_w); image b
     is then bitwise the launch on that image alone with sft_w = float(sft_w[b]).
     pad_mode: PAD_ZERO, PAD_REFLECT (ReflectionPad2d(1) + unpadded 3x3) or PAD_EDGE (with upsample: reflection padding of the
@@ -1498,4 +1498,106 @@ def ssim(a, b, y_channel=False):
         out = torch.empty(B, dtype=torch.float64, device=a.device)
         L.check(lib.cf_ssim(a.data_ptr(), b.data_ptr(), B, H, W, C, sa, sb, dt, int(bool(y_channel)), L.ptr(parts, dtype=torch.float64),
                             L.ptr(out, dtype=torch.float64), L.stream_ptr()), 'cf_ssim')
+    return out
+
+
+# ---- ResNetArcFace and the identity metric (cf_arcface.hip) -- definitions at "ArcFace / identity metric" in include/codeformer_hip.h ------
+def _nhwc_dense(x, what):
+    _f32(x)
+    if x.dim() != 4 or not x.is_contiguous() or x.shape[3] % 4:
+        raise ValueError(f'{what}: expected a dense float32 (B,H,W,C) tensor with C % 4 == 0, got {tuple(x.shape)}')
+    return x.shape
+
+
+def prelu_maxpool2(x, alpha):
+    """MaxPool2d(2, 2) of prelu(x, alpha): (B,2h,2w,C) -> (B,h,w,C), PReLU first (they do not commute for alpha < 0)."""
+    B, H, W, C = _nhwc_dense(x, 'prelu_maxpool2')
+    if H % 2 or W % 2:
+        raise ValueError(f'prelu_maxpool2: even height and width, got {H}x{W}')
+    out = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
+    L.check(L.load().cf_prelu_maxpool2(L.ptr(x), B, H // 2, W // 2, C, float(alpha), L.ptr(out), L.stream_ptr()), 'cf_prelu_maxpool2')
+    return out
+
+
+def se_pool(x):
+    """(B,H,W,C) -> the (B,C) mean over the pixels, in one fixed order per image."""
+    B, H, W, C = _nhwc_dense(x, 'se_pool')
+    lib = L.load()
+    parts = torch.empty(B * lib.cf_se_pool_parts(H * W) * C, dtype=torch.float32, device=x.device)
+    out = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    L.check(lib.cf_se_pool(L.ptr(x), B, H * W, C, L.ptr(parts), L.ptr(out), L.stream_ptr()), 'cf_se_pool')
+    return out
+
+
+def se_gate(pooled, w1, b1, alpha, w2, b2):
+    """sigmoid(Linear(prelu(Linear(pooled)))) on (B,C) rows; w1 (r,C), w2 (C,r) in torch's Linear layout."""
+    B, C = _f32(pooled).shape
+    r = w1.shape[0]
+    if tuple(w1.shape) != (r, C) or tuple(w2.shape) != (C, r) or tuple(b1.shape) != (r,) or tuple(b2.shape) != (C,):
+        raise ValueError(f'se_gate: weights {tuple(w1.shape)}, {tuple(w2.shape)} do not fit {C} channels')
+    out = torch.empty((B, C), dtype=torch.float32, device=pooled.device)
+    L.check(L.load().cf_se_gate(L.ptr(pooled), L.ptr(w1), L.ptr(b1), float(alpha), L.ptr(w2), L.ptr(b2), B, C, r, L.ptr(out), L.stream_ptr()), 'cf_se_gate')
+    return out
+
+
+def se_scale_res_prelu(x, y, res, alpha):
+    """prelu(x * y[b][c] + res, alpha): x, res (B,H,W,C), y (B,C); res None: prelu(x * y[b][c], alpha), no add."""
+    B, H, W, C = _nhwc_dense(x, 'se_scale_res_prelu')
+    if (res is not None and tuple(res.shape) != tuple(x.shape)) or tuple(y.shape) != (B, C):
+        raise ValueError(f'se_scale_res_prelu: x {tuple(x.shape)}, y {tuple(y.shape)}, res {None if res is None else tuple(res.shape)}')
+    out = torch.empty_like(x)
+    L.check(L.load().cf_se_scale_res_prelu(L.ptr(x), L.ptr(y), L.ptr(res), B, H * W, C, float(alpha), L.ptr(out), L.stream_ptr()), 'cf_se_scale_res_prelu')
+    return out
+
+
+FC_ROWS = 16   # rows per cf_fc_rows launch
+
+
+def pack_fc_rows(weight):
+    """(N,K) Linear weight -> the [K/4][N][4] layout cf_fc_rows reads (a lane owns an output column)."""
+    N, K = _f32(weight).shape
+    if K % 256 or N % 4:
+        raise ValueError(f'pack_fc_rows: K % 256 == 0 and N % 4 == 0, got {(N, K)}')
+    return weight.detach().reshape(N, K // 4, 4).permute(1, 0, 2).contiguous()
+
+
+def fc_rows(x, wp, bias=None):
+    """x (M,K) @ W^T + bias for a handful of rows, W packed by pack_fc_rows; row m never depends on the other rows (more than FC_ROWS rows
+    are that many launches, each reading the weight once)."""
+    M, K = _f32(x).shape
+    N = wp.shape[1]
+    if tuple(wp.shape) != (K // 4, N, 4) or not x.is_contiguous():
+        raise ValueError(f'fc_rows: x {tuple(x.shape)} (dense) does not fit the packed weight {tuple(wp.shape)}')
+    lib = L.load()
+    out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    for m0 in range(0, M, FC_ROWS):
+        m = min(FC_ROWS, M - m0)
+        ws = torch.empty(lib.cf_fc_rows_workspace_elems(m, N, K), dtype=torch.float32, device=x.device)
+        L.check(lib.cf_fc_rows(L.ptr(x[m0:m0 + m]), L.ptr(wp), L.ptr(bias), m, N, K, L.ptr(ws), L.ptr(out[m0:m0 + m]), L.stream_ptr()), 'cf_fc_rows')
+    return out
+
+
+def identity_input(view, bgr):
+    """(B,H,W,3) VIEW (any non-negative strides), uint8 or float32 in [0, 1] -> (B,1,128,128) float32: RGB in [-1, 1], gray, bilinear resize."""
+    if view.dim() != 4 or view.shape[3] != 3 or min(view.shape) < 1 or view.dtype not in METRIC_DTYPES:
+        raise ValueError(f'identity_input: a uint8 or float32 (B,H,W,3) view is needed, got {view.dtype} {tuple(view.shape)}')
+    if min(view.stride()) < 0 or sum((n - 1) * s for n, s in zip(view.shape, view.stride())) >= 1 << 31:
+        raise ValueError('identity_input: strides must be non-negative and the largest element offset below 2^31')
+    lib = L.ensure_device(view.device)
+    B, H, W, _ = view.shape
+    with torch.cuda.device(view.device):
+        out = torch.empty((B, 1, 128, 128), dtype=torch.float32, device=view.device)
+        L.check(lib.cf_identity_input(view.data_ptr(), B, H, W, (ctypes.c_int64 * 4)(*view.stride()), METRIC_DTYPES[view.dtype], int(bool(bgr)),
+                                      L.ptr(out), L.stream_ptr()), 'cf_identity_input')
+    return out
+
+
+def cosine_rows(x, y):
+    """(B,) float64: x_r . y_r / max(|x_r| |y_r|, 1e-8) of the float32 rows of x and y, in float64."""
+    if x.dim() != 2 or tuple(x.shape) != tuple(y.shape) or x.device != y.device:
+        raise ValueError(f'cosine_rows: two (B,N) tensors of one shape on one device, got {tuple(x.shape)} and {tuple(y.shape)}')
+    lib = L.ensure_device(x.device)
+    with torch.cuda.device(x.device):
+        out = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+        L.check(lib.cf_cosine_rows(L.ptr(_f32(x)), L.ptr(_f32(y)), x.shape[0], x.shape[1], L.ptr(out, dtype=torch.float64), L.stream_ptr()), 'cf_cosine_rows')
     return out

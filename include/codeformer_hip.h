@@ -78,6 +78,13 @@ enum cf_epilogue {
   CF_EPI_AXPY = 5,      /* (acc + bias) * alpha + res        (x5 * 0.2 + x, rrdbnet_arch.py:39)          */
   CF_EPI_AXPY2 = 6,     /* ((acc + bias) * alpha + res) * alpha + res2 ; res2 = sft_scale
                            (last conv of an RRDB: both residuals of rrdbnet_arch.py:39 and :62 in one pass) */
+  /* nn.PReLU with ONE learned slope (ResNetArcFace, basicsr/archs/arcface_arch.py:73,87,98); alpha = sft_w, any real value (negative, zero,
+     above 1): prelu(x, alpha) = x > 0 ? x : alpha * x -- a select, not max(x, alpha * x).  CF_EPI_LEAKY above is NOT this with alpha = 0.2
+     passed in: its slope 0.2 is a constant of the kernel and sft_w is ignored there.  Enum values added without a version bump (no struct
+     change); instantiations of their own beside the general ones of CF_EPI_LEAKY .. CF_EPI_AXPY2 -- which therefore keep their code --: plain 3x3,
+     fp32 operands, stride 1, or stride 2 with pad_lo = 1 / cout_pad % 128 == 0; strided slices and off-grid sizes as there. */
+  CF_EPI_PRELU = 7,     /* prelu(acc + bias, alpha)                        */
+  CF_EPI_RES_PRELU = 8, /* prelu((acc + bias) + res, alpha)   (IRBlock: out += residual; prelu, :97-98) */
 };
 
 /* MFMA operand format (cf_conv_desc.bf16_mfma; the field keeps its ABI-v3 name) */
@@ -522,6 +529,46 @@ int cf_psnr(const void* a, const void* b, int batch, int h, int w, int channels,
             int y_channel, double* parts, double* sse, double* psnr, cf_stream_t stream);
 int cf_ssim(const void* a, const void* b, int batch, int h, int w, int channels, const int64_t* stride_a, const int64_t* stride_b, int dtype,
             int y_channel, double* parts, double* ssim, cf_stream_t stream);
+
+/* ---- ArcFace / identity metric (basicsr/archs/arcface_arch.py ResNetArcFace; the identity score of face restoration) -------------------
+ * Added without a version bump: the exports are additive and CF_ABI_VERSION stays 22.  fp32, channels-last, every pointer 16-byte aligned
+ * where a kernel reads float4 (checked).  Every reduction has one fixed order given by the per-image shape: bitwise repeatable, and image /
+ * row b of a batch is bitwise the call on it alone.  Every argument is checked before anything is launched.
+ *   cf_prelu_maxpool2      x [batch][2h][2w][c] -> out [batch][h][w][c], c % 4 == 0: out = max over the 2x2 window of prelu(x, alpha), PReLU
+ *                          FIRST (for alpha < 0 it is not monotone and the two do not commute; arcface_arch.py:232-233); a NaN wins the max.
+ *   cf_se_pool             x [batch][hw][c] -> out [batch][c] = mean over the pixels (SEBlock's AdaptiveAvgPool2d(1), :159,166): fp32 partial
+ *                          sums per (image, 64 channels, 256 pixels) in `parts` (batch * cf_se_pool_parts(hw) * c floats), added in block order,
+ *                          one division by (float)hw.
+ *   cf_se_gate             pooled [batch][c] -> out [batch][c] = sigmoid(w2 prelu(w1 p + b1, alpha) + b2), w1 [r][c], w2 [c][r] (torch's Linear
+ *                          layout; :160-162), sigmoid(s) = 1 / (1 + expf(-s)); one workgroup per image; c <= 4096, r <= 256.
+ *   cf_se_scale_res_prelu  out = prelu(x * y[b][c] + res, alpha), x / res / out [batch][hw][c], y [batch][c]; multiply and add rounded
+ *                          separately (:168, :97-98).  res == NULL: no add, out = prelu(x * y[b][c], alpha) (SEBlock alone with alpha = 1).
+ *   cf_fc_rows             out [m][n] = x [m][k] W^T + bias for 1 <= m <= 16 rows (fc5 of ResNetArcFace: k = 32768, n = 512 -- a 64 MiB weight
+ *                          read once, a GEMV family).  wp is W [n][k] laid out [k/4][n][4] (a lane owns an output column and reads 16
+ *                          contiguous bytes per 4 k); k % 256 == 0, n % 4 == 0.  K is cut into chunks of 256 across workgroups; a chunk is
+ *                          four quarters of 64, each an fmaf chain in ascending k from zero, added in order; the chunk sums meet in ws
+ *                          (cf_fc_rows_workspace_elems floats) and a second launch adds them -- chunks c = j mod 8 in ascending order for
+ *                          j = 0 .. 7, those eight in order -- then the bias.  One order for every m.
+ *   cf_identity_input      image -> [batch][1][128][128] fp32, the input of the identity network.  img: uint8 (dtype 0; f = (float)v / 255.0f)
+ *                          or float32 in [0, 1] (dtype 1), 3 channels, element (n, y, x, ch) at img[n*stride[0] + y*stride[1] + x*stride[2] +
+ *                          ch*stride[3]] (element strides in HOST memory, non-negative; largest offset below 2^31); bgr = 1: channel 0 is blue.
+ *                          Every step one fp32 operation, none contracted:  v = f * 2 - 1 per channel;  gray = (0.2989 R + 0.5870 G) + 0.1140 B;
+ *                          along an axis of n pixels, output index o:  src = (o + 0.5) * (n / 128) - 0.5 (the ratio one fp32 division per
+ *                          launch), src = max(src, 0), i0 = floor(src), i1 = min(i0 + 1, n - 1), l = src - i0, h = 1 - l;
+ *                          out = hy * (hx * g00 + lx * g01) + ly * (hx * g10 + lx * g11)  -- bilinear with half-pixel centres, edge clamp, no
+ *                          antialiasing; gray first, resize second.  Indices are clamped to the image before any address is formed.
+ *   cf_cosine_rows         out[r] = x_r . y_r / max(|x_r| |y_r|, 1e-8) in fp64 from fp32 rows [rows][n]; one wave per row (lane partials in
+ *                          stride order, then a butterfly); a zero row gives 0. */
+int cf_prelu_maxpool2(const float* x, int batch, int h, int w, int c, float alpha, float* out, cf_stream_t stream);
+int cf_se_pool_parts(int hw); /* -1: bad argument */
+int cf_se_pool(const float* x, int batch, int hw, int c, float* parts, float* out, cf_stream_t stream);
+int cf_se_gate(const float* pooled, const float* w1, const float* b1, float alpha, const float* w2, const float* b2, int batch, int c, int r,
+               float* out, cf_stream_t stream);
+int cf_se_scale_res_prelu(const float* x, const float* y, const float* res, int batch, int hw, int c, float alpha, float* out, cf_stream_t stream);
+int64_t cf_fc_rows_workspace_elems(int m, int n, int k); /* -1: bad arguments */
+int cf_fc_rows(const float* x, const float* wp, const float* bias, int m, int n, int k, float* ws, float* out, cf_stream_t stream);
+int cf_identity_input(const void* img, int batch, int h, int w, const int64_t* stride, int dtype, int bgr, float* out, cf_stream_t stream);
+int cf_cosine_rows(const float* x, const float* y, int rows, int n, double* out, cf_stream_t stream);
 
 /* ---- alignment warp and paste-back of the whole-image / video path ----------------------------------------------------------
  * Replaces the OpenCV calls of facelib/utils/face_restoration_helper.py: cv2.warpAffine of align_warp_face (:343-344) and of

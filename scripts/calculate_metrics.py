@@ -1,10 +1,15 @@
-"""PSNR and SSIM of a directory of restored images against their ground truth.
+"""PSNR and SSIM (and, with --identity, identity preservation) of a directory of restored images against their ground truth.
 
   python scripts/calculate_metrics.py --restored DIR --gt DIR [--crop_border N] [--test_y_channel] [--batch 16] [--json OUT]
+                                      [--identity (--arcface_weights PATH | --random_init_seed N)]
 
 PNGs are paired by file name and read as uint8 BGR (img_util.imread_bgr).  On a GPU, images of one size are scored in device batches
 (metrics.psnr_batch / ssim_batch: the HIP kernels); without one the host definition runs image by image.  One line per file, then the
 means.  A file without a partner in the other directory and a pair of different sizes are errors that name the file.
+--identity adds the cosine similarity of the ArcFace embeddings of both images (metrics.identity_batch, scored in the same device batches;
+whole images, crop_border does not apply).  The network's weights come from --arcface_weights (a ResNetArcFace 'IRBlock' [2,2,2,2]
+checkpoint; nothing is downloaded), or, for plumbing only, from a random initialisation seeded by --random_init_seed: such a column means
+nothing about identity.
 """
 import argparse
 import json
@@ -18,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from basicsr.metrics import calculate_psnr, calculate_ssim  # noqa: E402
+from basicsr.metrics import calculate_identity, calculate_psnr, calculate_ssim, identity_batch, load_arcface  # noqa: E402
 from basicsr.metrics.psnr_ssim import psnr_batch, ssim_batch  # noqa: E402
 from basicsr.utils.img_util import imread_bgr  # noqa: E402
 
@@ -37,7 +42,17 @@ def main(argv=None):
     p.add_argument('--test_y_channel', action='store_true')
     p.add_argument('--batch', type=int, default=16, help='images per device batch')
     p.add_argument('--json', default=None, help='also write the per-file values and the means here')
+    p.add_argument('--identity', action='store_true', help='add the ArcFace identity column')
+    p.add_argument('--arcface_weights', default=None, help='ResNetArcFace checkpoint for --identity')
+    p.add_argument('--random_init_seed', type=int, default=None, help='--identity on a seeded random initialisation (plumbing only)')
     args = p.parse_args(argv)
+    net = None
+    if args.identity:
+        if (args.arcface_weights is None) == (args.random_init_seed is None):
+            raise SystemExit('error: --identity needs exactly one of --arcface_weights PATH and --random_init_seed N')
+        if args.random_init_seed is not None:
+            torch.manual_seed(args.random_init_seed)
+        net = load_arcface(args.arcface_weights, 'cuda' if torch.cuda.is_available() else None)
     names, gt = _pngs(args.restored), set(_pngs(args.gt))
     for n in names:
         if n not in gt:
@@ -64,15 +79,20 @@ def main(argv=None):
                 a = torch.from_numpy(np.stack([c[1] for c in chunk])).cuda()
                 b = torch.from_numpy(np.stack([c[2] for c in chunk])).cuda()
                 ps, ss = psnr_batch(a, b, **opt).tolist(), ssim_batch(a, b, **opt).tolist()
-                for (n, _, _), pv, sv in zip(chunk, ps, ss):
-                    result[n] = {'psnr': pv, 'ssim': sv}
+                ids = identity_batch(a, b, net).tolist() if net is not None else [None] * len(chunk)
+                for (n, _, _), pv, sv, iv in zip(chunk, ps, ss, ids):
+                    result[n] = {'psnr': pv, 'ssim': sv, **({} if iv is None else {'identity': iv})}
     else:
         for n, a, b in pairs:
             result[n] = {'psnr': calculate_psnr(a, b, **opt), 'ssim': calculate_ssim(a, b, **opt)}
+            if net is not None:
+                result[n]['identity'] = calculate_identity(a, b, net)
+    keys = ('psnr', 'ssim') + (('identity',) if net is not None else ())
+    ident = (lambda v: f'\tIDENTITY {v["identity"]:.6f}') if net is not None else (lambda v: '')
     for n in names:
-        print(f'{n}\tPSNR {result[n]["psnr"]:.6f} dB\tSSIM {result[n]["ssim"]:.6f}')
-    mean = {k: float(np.mean([result[n][k] for n in names])) for k in ('psnr', 'ssim')}
-    print(f'mean of {len(names)}\tPSNR {mean["psnr"]:.6f} dB\tSSIM {mean["ssim"]:.6f}')
+        print(f'{n}\tPSNR {result[n]["psnr"]:.6f} dB\tSSIM {result[n]["ssim"]:.6f}' + ident(result[n]))
+    mean = {k: float(np.mean([result[n][k] for n in names])) for k in keys}
+    print(f'mean of {len(names)}\tPSNR {mean["psnr"]:.6f} dB\tSSIM {mean["ssim"]:.6f}' + ident(mean))
     if args.json:
         with open(args.json, 'w') as fh:
             json.dump({'files': result, 'mean': mean, 'crop_border': args.crop_border, 'test_y_channel': args.test_y_channel}, fh, indent=1)
