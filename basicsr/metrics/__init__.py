@@ -15,3 +15,6 @@ def calculate_metric(data, opt):
 from codeformer_amd.metrics import calculate_identity, identity_batch, identity_input, load_arcface  # noqa: E402
 
 __all__ += ['calculate_identity', 'identity_batch', 'identity_input', 'load_arcface']
+from codeformer_amd.metrics import calculate_perceptual, load_lpips_vgg, load_vgg, lpips_batch, perceptual_batch  # noqa: E402
+
+__all__ += ['calculate_perceptual', 'perceptual_batch', 'load_vgg', 'lpips_batch', 'load_lpips_vgg']

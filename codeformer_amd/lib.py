@@ -116,6 +116,15 @@ SIGNATURES = {
     'cf_fc_rows': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     'cf_identity_input': (_I, [_P, _I, _I, _I, ctypes.POINTER(_L), _I, _I, _P, _P]),
     'cf_cosine_rows': (_I, [_P, _P, _I, _I, _P, _P]),
+    'cf_vgg_input': (_I, [_P, _I, _I, _I, ctypes.POINTER(_L), _I, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _I, _P, _P]),
+    'cf_relu': (_I, [_P, _L, _P, _P]),
+    'cf_relu_maxpool2': (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    'cf_gram_workspace_elems': (_L, [_I, _I, _I]),
+    'cf_gram': (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    'cf_feat_dist_parts': (_I, [_L]),
+    'cf_feat_dist': (_I, [_P, _P, _I, _L, _P, _P, _P]),
+    'cf_lpips_parts': (_I, [_I]),
+    'cf_lpips_head': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     'cf_warp_affine_u8':(_I, [_P, _L, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'cf_warp_affine_f32': (_I, [_P, _I, _I, ctypes.POINTER(ctypes.c_double), _P, _I, _I, _I, _I, _P]),
     'cf_erode_f32': (_I, [_P, _P, _P, _I, _I, _I, _P]),

@@ -23,6 +23,10 @@ definition ("ArcFace / identity metric" in include/codeformer_hip.h): RGB in [-1
 resize to 128 x 128 with half-pixel centres, edge clamp and no antialiasing -- gray first, resize second, every step one float32 operation,
 so the host definition (torch ops on the CPU) and the kernel give the same bits.  identity_batch / calculate_identity / load_arcface
 follow; no trained ArcFace checkpoint ships with or was run through this code.
+
+A perceptual score: perceptual_batch / calculate_perceptual give, per image pair, sum_k w_k criterion(f_k(a), f_k(b)) over the VGG layers of a
+losses.PerceptualLoss (load_vgg builds one), or the same on the Gram matrices (style).  No trained VGG checkpoint ships with or was run
+through this code either.
 """
 import numpy as np
 import torch
@@ -30,7 +34,7 @@ import torch
 from .utils.registry import METRIC_REGISTRY
 
 __all__ = ['calculate_psnr', 'calculate_ssim', 'psnr_batch', 'ssim_batch', 'reorder_image', 'to_y_channel', 'identity_input', 'identity_batch',
-           'calculate_identity', 'load_arcface']
+           'calculate_identity', 'load_arcface', 'perceptual_batch', 'calculate_perceptual', 'load_vgg', 'lpips_batch', 'load_lpips_vgg']
 
 ORDERS = ('HWC', 'CHW')
 C1 = (0.01 * 255)**2
@@ -211,11 +215,11 @@ ID_SIZE = 128
 GRAY = (0.2989, 0.5870, 0.1140)
 
 
-def _identity_view(img, order):
+def _identity_view(img, order, what='identity_input'):
     """(B,H,W,3) view of a tensor: uint8 BGR or float32 RGB in [0, 1], one image or a batch, 'HWC' or 'CHW' -- strides only."""
     _check_order(order)
     if img.dtype not in (torch.uint8, torch.float32):
-        raise TypeError(f'identity_input takes uint8 (BGR) or float32 (RGB in [0, 1]) images, got {img.dtype}')
+        raise TypeError(f'{what} takes uint8 (BGR) or float32 (RGB in [0, 1]) images, got {img.dtype}')
     t = img.detach()
     if t.dim() == 3:
         t = t[None]
@@ -224,7 +228,7 @@ def _identity_view(img, order):
     if order == 'CHW':
         t = t.permute(0, 2, 3, 1)
     if t.shape[3] != 3 or min(t.shape) < 1:
-        raise ValueError(f'identity_input needs 3-channel images, got {tuple(img.shape)} with order {order}')
+        raise ValueError(f'{what} needs 3-channel images, got {tuple(img.shape)} with order {order}')
     return t
 
 
@@ -323,3 +327,115 @@ def load_arcface(path=None, device=None):
         net.load_state_dict({(k[7:] if k.startswith('module.') else k): v for k, v in state.items()}, strict=True)
     net.eval()
     return net.to(device) if device is not None else net
+
+
+# ---- perceptual / style score -------------------------------------------------------------------------------------------------------------
+def perceptual_batch(a, b, net, order='HWC', criterion='l1', style=False):
+    """The perceptual distance of every image pair of two batches under `net`, a losses.PerceptualLoss (load_vgg): per image
+    sum_k w_k mean|f_k(a) - f_k(b)| over its layer_weights ('mse': the mean square, 'fro': the Frobenius norm, every image as a batch of
+    one), with style=True the same on the Gram matrices F F^T / (c h w).  Its vgg_type and norm flags apply; perceptual_weight and
+    style_weight do not.  Inputs as for identity_batch: uint8 BGR (B,H,W,3) -- what CodeFormer.restore_u8 returns -- or float32 RGB in
+    [0, 1], 'HWC' or 'CHW', read through their strides.  A (B,) float64 tensor on the inputs' device; on the device both batches pass the
+    network in one call (row r is bitwise the call on r alone), nothing is copied to the host and nothing synchronises."""
+    from .losses import CRITERIA, gram_host, reduce_dist
+    if criterion not in CRITERIA:
+        raise NotImplementedError(f'{criterion} criterion has not been supported.')
+    ta, tb = (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t)) for t in (a, b))
+    va, vb = _identity_view(ta, order, 'perceptual_batch'), _identity_view(tb, order, 'perceptual_batch')
+    if va.shape != vb.shape or va.device != vb.device or va.dtype != vb.dtype:
+        raise ValueError(f'two batches of one size and type on one device are needed, got {va.dtype} {tuple(va.shape)} on {va.device} and {vb.dtype} {tuple(vb.shape)} on {vb.device}')
+    bgr = va.dtype == torch.uint8
+    if va.is_cuda:
+        from . import ops
+        ops.L.ensure_device(va.device)
+        with torch.no_grad(), torch.cuda.device(va.device):
+            return net.score(net.features([va, vb], bgr), style=style, criterion=criterion, per_image=True)
+    with torch.no_grad():
+        n = va.shape[0]
+        x = torch.cat([va, vb], 0)
+        x = x.to(torch.float32) / torch.tensor(255., dtype=torch.float32) if bgr else x
+        x = (x.flip(3) if bgr else x).permute(0, 3, 1, 2)
+        total = torch.zeros(n, dtype=torch.float64)
+        for k, f in net.vgg.forward_host(x).items():
+            t = gram_host(f) if style else f
+            d = (t[:n] - t[n:]).double().reshape(n, -1)
+            total = total + reduce_dist(torch.stack([d.abs().sum(1), (d * d).sum(1)], 1), d.shape[1], criterion, True) * float(net.layer_weights[k])
+        return total
+
+
+@METRIC_REGISTRY.register()
+def calculate_perceptual(img1, img2, net, input_order='HWC', criterion='l1', style=False):
+    """The perceptual distance of one image pair ((h,w,3) or (3,h,w); uint8 BGR or float32 RGB in [0, 1]) under `net` (load_vgg).  numpy
+    arrays and CPU tensors take the host path, CUDA tensors the HIP path.  A Python float."""
+    for i in (img1, img2):
+        if len(i.shape) != 3:
+            raise ValueError('calculate_perceptual takes one image pair (perceptual_batch takes batches)')
+    return float(perceptual_batch(img1, img2, net, input_order, criterion, style)[0].item())
+
+
+VGG_LAYER_WEIGHTS = {'conv1_2': 0.1, 'conv2_2': 0.1, 'conv3_4': 1., 'conv4_4': 1., 'conv5_4': 1.}   # the weights of the reference's training options
+
+
+def load_vgg(path=None, vgg_type='vgg19', layer_weights=None, use_input_norm=True, range_norm=False, device=None):
+    """A losses.PerceptualLoss on `vgg_type` for perceptual_batch, with the torchvision state dict at `path` loaded if one is given
+    (`features.<i>.*` by position; `classifier.*` and layers past the last requested one are ignored).  Nothing is downloaded: a missing
+    file raises FileNotFoundError.  Without a path the weights are the seeded-by-the-caller random initialisation (or
+    vgg_arch.VGG_PRETRAIN_PATH, where that file exists)."""
+    import os
+    from .archs.vgg_arch import FeaturesOnly
+    from .losses import PerceptualLoss
+    net = PerceptualLoss(dict(layer_weights or VGG_LAYER_WEIGHTS), vgg_type=vgg_type, use_input_norm=use_input_norm, range_norm=range_norm)
+    if path is not None:
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f'VGG checkpoint {path} not found (nothing is downloaded)')
+        full = FeaturesOnly(vgg_type)
+        full.load_state_dict(torch.load(path, map_location='cpu', weights_only=True))
+        with torch.no_grad():
+            for dst, src in zip(net.vgg.names, full.features):
+                if dst in net.vgg.vgg_net._modules and list(src.state_dict()):
+                    net.vgg.vgg_net._modules[dst].load_state_dict(src.state_dict())
+    net.eval()
+    return net.to(device) if device is not None else net
+
+
+# ---- the LPIPS form, by its published definition ---------------------------------------------------------------------------------------------
+# The reference trains with LPIPSLoss, a wrapper of the external `lpips` package; that package is not installed, so no fixture of it can exist
+# and this is the definition of Zhang et al. 2018 restated: vgg16 taps relu1_2 .. relu5_3 of an image in [-1, 1] behind the scaling layer
+# (x - shift) / scale, features divided per pixel by sqrt(sum_c f^2) + 1e-10, squared differences weighted by non-negative `lin` vectors,
+# averaged over the pixels, summed over the layers.  No LPIPS weights (neither the VGG nor the lin layers) ship with or were run through this code.
+LPIPS_TAPS = ('relu1_2', 'relu2_2', 'relu3_3', 'relu4_3', 'relu5_3')
+LPIPS_SHIFT = (-.030, -.088, -.188)
+LPIPS_SCALE = (.458, .448, .450)
+
+
+def load_lpips_vgg(device=None):
+    """A vgg16 VGGFeatureExtractor on LPIPS_TAPS whose input normalisation is the LPIPS scaling layer (mean = shift, std = scale; inputs in
+    [-1, 1]); weights as for VGGFeatureExtractor (seeded by the caller when no checkpoint file exists).  Nothing is downloaded."""
+    from .archs.vgg_arch import VGGFeatureExtractor
+    net = VGGFeatureExtractor(list(LPIPS_TAPS), vgg_type='vgg16', use_input_norm=True, range_norm=False)
+    with torch.no_grad():
+        net.mean.copy_(torch.tensor(LPIPS_SHIFT).view(1, 3, 1, 1))
+        net.std.copy_(torch.tensor(LPIPS_SCALE).view(1, 3, 1, 1))
+    return net.to(device) if device is not None else net
+
+
+def lpips_batch(a, b, net, lin, order='HWC'):
+    """The LPIPS distance of every image pair of two device batches of float32 RGB images in [-1, 1] ((B,H,W,3), or (B,3,H,W) with 'CHW';
+    strides only) under `net` (load_lpips_vgg) and `lin`: one non-negative float32 weight vector per tap of `net`, in tap order.  A (B,)
+    float64 tensor on the device: sum over the taps of cf_lpips_head; no copy to the host, no synchronisation.  Device only."""
+    va, vb = _identity_view(a, order, 'lpips_batch'), _identity_view(b, order, 'lpips_batch')
+    if not va.is_cuda or va.dtype != torch.float32 or vb.dtype != torch.float32:
+        raise ValueError('lpips_batch takes float32 CUDA (ROCm) tensors with values in [-1, 1]')
+    if va.shape != vb.shape or va.device != vb.device:
+        raise ValueError(f'two batches of one size on one device are needed, got {tuple(va.shape)} on {va.device} and {tuple(vb.shape)} on {vb.device}')
+    if len(lin) != len(net.layer_name_list):
+        raise ValueError(f'lin: one weight vector per tap ({len(net.layer_name_list)}), got {len(lin)}')
+    from . import ops
+    ops.L.ensure_device(va.device)
+    n = va.shape[0]
+    with torch.no_grad(), torch.cuda.device(va.device):
+        feats = net.features_from_views([va, vb])
+        total = 0
+        for (k, f), w in zip(feats.items(), lin):
+            total = total + ops.lpips_head(f[:n], f[n:], w)
+    return total

@@ -1601,3 +1601,123 @@ def cosine_rows(x, y):
         out = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
         L.check(lib.cf_cosine_rows(L.ptr(_f32(x)), L.ptr(_f32(y)), x.shape[0], x.shape[1], L.ptr(out, dtype=torch.float64), L.stream_ptr()), 'cf_cosine_rows')
     return out
+
+
+# ---- VGGFeatureExtractor and the perceptual / style score (cf_vgg.hip) -- definitions at "VGG / perceptual" in include/codeformer_hip.h ------
+VGG_IN_CPAD = 16    # channels of vgg_input's output: one K slab of the general 3x3 kernel (pack_weight pads conv1_1's three to the same)
+GRAM_CHUNK = 1024   # CF_GRAM_CHUNK
+FEAT_CHUNK = 16384  # CF_FEAT_CHUNK
+
+
+def vgg_input(view, bgr, range_norm=False, mean=None, std=None, c_pad=VGG_IN_CPAD, out=None):
+    """(B,H,W,3) VIEW (any non-negative strides), uint8 (v / 255) or float32 -> dense (B,H,W,c_pad) float32, channels R, G, B then zeros:
+    (x + 1) / 2 with range_norm, then (x - mean[c]) / std[c] when mean / std (three Python floats each) are given.  out: a dense
+    destination (a batch slice of a larger buffer)."""
+    if view.dim() != 4 or view.shape[3] != 3 or min(view.shape) < 1 or view.dtype not in METRIC_DTYPES:
+        raise ValueError(f'vgg_input: a uint8 or float32 (B,H,W,3) view is needed, got {view.dtype} {tuple(view.shape)}')
+    if min(view.stride()) < 0 or sum((n - 1) * s for n, s in zip(view.shape, view.stride())) >= 1 << 31:
+        raise ValueError('vgg_input: strides must be non-negative and the largest element offset below 2^31')
+    if (mean is None) != (std is None) or (mean is not None and (len(mean) != 3 or len(std) != 3)):
+        raise ValueError('vgg_input: mean and std are three floats each, or both None')
+    if c_pad < 4 or c_pad > 64 or c_pad % 4:
+        raise ValueError(f'vgg_input: c_pad {c_pad} (4 .. 64, a multiple of 4)')
+    lib = L.ensure_device(view.device)
+    B, H, W, _ = view.shape
+    f3 = ctypes.c_float * 3
+    if out is not None:
+        if tuple(out.shape) != (B, H, W, c_pad) or out.dtype != torch.float32 or out.device != view.device or not out.is_contiguous():
+            raise ValueError(f'vgg_input: out must be a dense float32 {(B, H, W, c_pad)} tensor on {view.device}')
+        _drop_state(out)
+    with torch.cuda.device(view.device):
+        if out is None:
+            out = torch.empty((B, H, W, c_pad), dtype=torch.float32, device=view.device)
+        L.check(lib.cf_vgg_input(view.data_ptr(), B, H, W, (ctypes.c_int64 * 4)(*view.stride()), METRIC_DTYPES[view.dtype], int(bool(bgr)),
+                                 int(bool(range_norm)), int(mean is not None), None if mean is None else f3(*mean), None if std is None else f3(*std),
+                                 int(c_pad), L.ptr(out), L.stream_ptr()), 'cf_vgg_input')
+    return out
+
+
+def relu(x, inplace=False):
+    """x > 0 ? x : +0 on a dense float32 tensor with a multiple of 4 elements (NaN stays NaN); inplace: x is overwritten and returned."""
+    _f32(x)
+    if not x.is_contiguous() or x.numel() % 4 or x.numel() == 0:
+        raise ValueError(f'relu: expected a dense tensor with a multiple of 4 elements, got {tuple(x.shape)}')
+    out = x if inplace else torch.empty_like(x)
+    if inplace:
+        _drop_state(x)
+    L.check(L.load().cf_relu(L.ptr(x), x.numel(), L.ptr(out), L.stream_ptr()), 'cf_relu')
+    return out
+
+
+def relu_maxpool2(x, full=False):
+    """MaxPool2d(2, 2) of relu(x): (B,H,W,C) -> (B,H//2,W//2,C), an odd last row / column dropped; a NaN wins the max.
+    full=True: (pooled, relu(x) at full size) from the one launch; full='inplace': the full-size ReLU overwrites x."""
+    B, H, W, C = _nhwc_dense(x, 'relu_maxpool2')
+    if H < 2 or W < 2:
+        raise ValueError(f'relu_maxpool2: the pool would take {H}x{W} to zero')
+    out = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
+    fl = None
+    if full == 'inplace':
+        fl = x
+        _drop_state(x)
+    elif full:
+        fl = torch.empty_like(x)
+    L.check(L.load().cf_relu_maxpool2(L.ptr(x), B, H, W, C, L.ptr(out), L.ptr(fl), L.stream_ptr()), 'cf_relu_maxpool2')
+    return (out, fl) if full else out
+
+
+def gram(f):
+    """(B,H,W,C) or (B,HW,C) dense float32 features -> (B,C,C): F^T F / (float)(C * HW) per image on the fp32 MFMA, C % 64 == 0, C <= 512.
+    Bitwise symmetric, bitwise repeatable, image b bitwise the call on it alone."""
+    _f32(f)
+    if f.dim() not in (3, 4) or not f.is_contiguous() or min(f.shape) < 1:
+        raise ValueError(f'gram: expected dense (B,H,W,C) or (B,HW,C) features, got {tuple(f.shape)}')
+    B, C = f.shape[0], f.shape[-1]
+    hw = f.numel() // (B * C)
+    if C % 64 or C > 512 or B > 65535:
+        raise ValueError(f'gram: C % 64 == 0, C <= 512 and B <= 65535, got B {B}, C {C}')
+    lib = L.load()
+    n = lib.cf_gram_workspace_elems(B, hw, C)
+    if n < 0:
+        raise ValueError(f'gram: unsupported shape {tuple(f.shape)}')
+    ws = torch.empty(n, dtype=torch.float32, device=f.device)
+    g = torch.empty((B, C, C), dtype=torch.float32, device=f.device)
+    L.check(lib.cf_gram(L.ptr(f), B, hw, C, L.ptr(ws), L.ptr(g), L.stream_ptr()), 'cf_gram')
+    return g
+
+
+def feat_dist(a, b):
+    """(B,2) float64: per image (sum |a - b|, sum (a - b)^2) of two dense float32 tensors of one shape (B, ...); each difference is one
+    float32 subtraction, widened before use; partial sums per chunk of FEAT_CHUNK elements, added in one fixed order (cf_feat_dist in the header)."""
+    _f32(a), _f32(b)
+    if tuple(a.shape) != tuple(b.shape) or a.dim() < 2 or a.device != b.device or not (a.is_contiguous() and b.is_contiguous()) or a.numel() == 0:
+        raise ValueError(f'feat_dist: two dense tensors of one shape (B, ...) on one device, got {tuple(a.shape)} and {tuple(b.shape)}')
+    B = a.shape[0]
+    n = a.numel() // B
+    if B > 65535:
+        raise ValueError(f'feat_dist: at most 65535 images, got {B}')
+    lib = L.load()
+    nparts = lib.cf_feat_dist_parts(n)
+    if nparts < 0:
+        raise ValueError(f'feat_dist: unsupported size {n}')
+    parts = torch.empty(B * nparts * 2, dtype=torch.float64, device=a.device)
+    out = torch.empty((B, 2), dtype=torch.float64, device=a.device)
+    L.check(lib.cf_feat_dist(L.ptr(a), L.ptr(b), B, n, L.ptr(parts, dtype=torch.float64), L.ptr(out, dtype=torch.float64), L.stream_ptr()), 'cf_feat_dist')
+    return out
+
+
+def lpips_head(fa, fb, lin):
+    """(B,) float64: one layer of the LPIPS distance of dense channels-last float32 features fa, fb (B,H,W,C) or (B,HW,C), C % 4 == 0, C <= 512,
+    under the non-negative channel weights lin (C,): the pixel mean of sum_c lin[c] (fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10))^2."""
+    _f32(fa), _f32(fb), _f32(lin)
+    if tuple(fa.shape) != tuple(fb.shape) or fa.dim() not in (3, 4) or fa.device != fb.device or not (fa.is_contiguous() and fb.is_contiguous()) or fa.numel() == 0:
+        raise ValueError(f'lpips_head: two dense feature tensors of one shape on one device, got {tuple(fa.shape)} and {tuple(fb.shape)}')
+    B, C = fa.shape[0], fa.shape[-1]
+    hw = fa.numel() // (B * C)
+    if C % 4 or C > 512 or B > 65535 or tuple(lin.shape) != (C,) or lin.device != fa.device or not lin.is_contiguous():
+        raise ValueError(f'lpips_head: C % 4 == 0, C <= 512, B <= 65535 and lin of shape ({C},) on {fa.device}, got B {B}, C {C}, lin {tuple(lin.shape)}')
+    lib = L.load()
+    parts = torch.empty(B * lib.cf_lpips_parts(hw), dtype=torch.float64, device=fa.device)
+    out = torch.empty(B, dtype=torch.float64, device=fa.device)
+    L.check(lib.cf_lpips_head(L.ptr(fa), L.ptr(fb), L.ptr(lin), B, hw, C, L.ptr(parts, dtype=torch.float64), L.ptr(out, dtype=torch.float64), L.stream_ptr()), 'cf_lpips_head')
+    return out

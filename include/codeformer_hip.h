@@ -570,6 +570,51 @@ int cf_fc_rows(const float* x, const float* wp, const float* bias, int m, int n,
 int cf_identity_input(const void* img, int batch, int h, int w, const int64_t* stride, int dtype, int bgr, float* out, cf_stream_t stream);
 int cf_cosine_rows(const float* x, const float* y, int rows, int n, double* out, cf_stream_t stream);
 
+/* ---- VGG / perceptual (basicsr/archs/vgg_arch.py VGGFeatureExtractor; basicsr/losses/losses.py PerceptualLoss) --------------------------
+ * Additive exports, CF_ABI_VERSION stays 22.  fp32, channels-last; every reduction has one fixed order given by the per-image shape:
+ * bitwise repeatable, image b of a batch is bitwise the call on it alone, no float atomics.  Every argument is checked before a launch.
+ *   cf_vgg_input      image -> out [batch][h][w][c_pad] fp32, channels 3 .. c_pad - 1 zero (c_pad % 4 == 0, 4 <= c_pad <= 64: the K slab of the
+ *                     first conv).  img / stride / dtype / bgr as cf_identity_input (uint8: f = (float)v / 255.0f; bgr = 1: channel 0 is
+ *                     blue; output channel order is R, G, B).  Every step one fp32 operation, none contracted, as vgg_arch.py:150-153:
+ *                     range_norm: f = (f + 1) / 2;  use_norm: f = (f - mean[c]) / std[c], mean / std three floats each in HOST memory.
+ *   cf_relu           out = x > 0 ? x : +0 on n floats (n % 4 == 0), out == x allowed (in place).  NaN stays NaN, -inf gives 0.
+ *   cf_relu_maxpool2  x [batch][h][w][c] -> out [batch][h/2][w/2][c], c % 4 == 0, h, w >= 2: max over the 2x2 window at stride 2 of relu(x);
+ *                     an odd last row / column is dropped (nn.MaxPool2d(2, 2)); a NaN wins the max.  full != NULL: also writes relu(x) at
+ *                     full resolution [batch][h][w][c] (full == x allowed: every element is read and written by the same thread).
+ *   cf_gram           F [batch][hw][c] -> G [batch][c][c], G[b][i][j] = (sum_p F[b][p][i] F[b][p][j]) / (float)(c * hw), c % 64 == 0, c <= 512,
+ *                     hw >= 1, on v_mfma_f32_32x32x2_f32 (IEEE-fp32 operands).  p is cut into chunks of CF_GRAM_CHUNK = 1024 pixels (the last
+ *                     one zero-filled); a chunk's 64 x 64 tile is accumulated in ascending p with short chains: 16 pixels from zero on the
+ *                     MFMA, those sums in order in groups of 8, the group sums in order; only tiles with j0 >= i0 are computed.  Chunk
+ *                     products lie in ws (cf_gram_workspace_elems floats); a second launch adds them in ascending chunk order (groups of 16
+ *                     chunks from zero, the group sums in order), divides once and writes G[i][j] and G[j][i] from the same value
+ *                     (i <= j): G is bitwise symmetric.
+ *   cf_feat_dist      a, b [batch][n] fp32 -> out [batch][2] fp64 = (sum |a - b|, sum (a - b)^2): the difference is one fp32 subtraction,
+ *                     widened to fp64 before it is used.  One partial pair per (image, chunk of CF_FEAT_CHUNK = 16384 elements) in parts
+ *                     (batch * cf_feat_dist_parts(n) * 2 doubles): a chunk is groups of 4 consecutive elements, thread t of 256 adds the
+ *                     groups t, t + 256, .. in ascending order (elements 4t .. 4t + 3, 4t + 1024 .., each group in ascending order), then
+ *                     the xor tree of each wave and the four waves in order.  The partials of an image are then added in ONE FIXED order,
+ *                     which is not the ascending one: one wave per image, lane l adds chunks l, l + 64, .. in ascending order, then the
+ *                     xor tree over the 64 lanes.
+ *   cf_lpips_head     one layer of the LPIPS distance by its published definition (Zhang et al. 2018): a, b [batch][hw][c] fp32 (c % 4 == 0,
+ *                     c <= 512), lin [c] -> out [batch] fp64 = mean over the pixels of  sum_c lin[c] (a_c / (sqrt(sum_c a_c^2) + 1e-10) -
+ *                     b_c / (sqrt(sum_c b_c^2) + 1e-10))^2.  Per pixel everything is fp32, one operation per step, none contracted; channel
+ *                     sums: a lane's elements in ascending order, then the xor tree of one wave.  Pixel values are widened to fp64; one
+ *                     partial per (image, 256 pixels) in parts (batch * cf_lpips_parts(hw) doubles): wave w of a workgroup adds the pixels
+ *                     w, w + 4, .. in ascending order, the four waves in order; the partials of an image are added as cf_feat_dist adds
+ *                     its own (lane-strided, then the xor tree: fixed, not ascending), then one division by (double)hw. */
+#define CF_GRAM_CHUNK 1024
+#define CF_FEAT_CHUNK 16384
+int cf_vgg_input(const void* img, int batch, int h, int w, const int64_t* stride, int dtype, int bgr, int range_norm, int use_norm,
+                 const float* mean, const float* std, int c_pad, float* out, cf_stream_t stream);
+int cf_relu(const float* x, int64_t n, float* out, cf_stream_t stream);
+int cf_relu_maxpool2(const float* x, int batch, int h, int w, int c, float* out, float* full, cf_stream_t stream);
+int64_t cf_gram_workspace_elems(int batch, int hw, int c); /* -1: bad arguments */
+int cf_gram(const float* f, int batch, int hw, int c, float* ws, float* g, cf_stream_t stream);
+int cf_feat_dist_parts(int64_t n); /* -1: bad argument */
+int cf_feat_dist(const float* a, const float* b, int batch, int64_t n, double* parts, double* out, cf_stream_t stream);
+int cf_lpips_parts(int hw); /* -1: bad argument */
+int cf_lpips_head(const float* a, const float* b, const float* lin, int batch, int hw, int c, double* parts, double* out, cf_stream_t stream);
+
 /* ---- alignment warp and paste-back of the whole-image / video path ----------------------------------------------------------
  * Replaces the OpenCV calls of facelib/utils/face_restoration_helper.py: cv2.warpAffine of align_warp_face (:343-344) and of
  * paste_faces_to_input_image (:400, :428, :479), cv2.erode (:430-431, :447), cv2.GaussianBlur (:449), np.sum (:433), the soft-mask

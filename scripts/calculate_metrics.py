@@ -1,7 +1,8 @@
-"""PSNR and SSIM (and, with --identity, identity preservation) of a directory of restored images against their ground truth.
+"""PSNR and SSIM (and, with --identity, identity preservation; with --perceptual, a VGG feature distance) of a directory of restored images against their ground truth.
 
   python scripts/calculate_metrics.py --restored DIR --gt DIR [--crop_border N] [--test_y_channel] [--batch 16] [--json OUT]
                                       [--identity (--arcface_weights PATH | --random_init_seed N)]
+                                      [--perceptual [--vgg_weights PATH] [--vgg_layers NAME=W ...]]
 
 PNGs are paired by file name and read as uint8 BGR (img_util.imread_bgr).  On a GPU, images of one size are scored in device batches
 (metrics.psnr_batch / ssim_batch: the HIP kernels); without one the host definition runs image by image.  One line per file, then the
@@ -10,6 +11,10 @@ means.  A file without a partner in the other directory and a pair of different 
 whole images, crop_border does not apply).  The network's weights come from --arcface_weights (a ResNetArcFace 'IRBlock' [2,2,2,2]
 checkpoint; nothing is downloaded), or, for plumbing only, from a random initialisation seeded by --random_init_seed: such a column means
 nothing about identity.
+--perceptual adds the L1 distance of the vgg19 features of both images (metrics.perceptual_batch; whole images), over the layers and
+weights of --vgg_layers (default conv1_2=0.1 conv2_2=0.1 conv3_4=1 conv4_4=1 conv5_4=1).  The weights come from --vgg_weights (a torchvision
+vgg19 state dict; nothing is downloaded); without it the network keeps a random initialisation (seeded by --random_init_seed, else 0), and the
+column is plumbing only.
 """
 import argparse
 import json
@@ -23,7 +28,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from basicsr.metrics import calculate_identity, calculate_psnr, calculate_ssim, identity_batch, load_arcface  # noqa: E402
+from basicsr.metrics import (calculate_identity, calculate_perceptual, calculate_psnr, calculate_ssim, identity_batch, load_arcface, load_vgg,  # noqa: E402
+                             perceptual_batch)
 from basicsr.metrics.psnr_ssim import psnr_batch, ssim_batch  # noqa: E402
 from basicsr.utils.img_util import imread_bgr  # noqa: E402
 
@@ -45,8 +51,19 @@ def main(argv=None):
     p.add_argument('--identity', action='store_true', help='add the ArcFace identity column')
     p.add_argument('--arcface_weights', default=None, help='ResNetArcFace checkpoint for --identity')
     p.add_argument('--random_init_seed', type=int, default=None, help='--identity on a seeded random initialisation (plumbing only)')
+    p.add_argument('--perceptual', action='store_true', help='add the VGG perceptual-distance column')
+    p.add_argument('--vgg_weights', default=None, help='torchvision vgg19 state dict for --perceptual')
+    p.add_argument('--vgg_layers', nargs='+', default=None, metavar='NAME=W', help='layers and weights of --perceptual')
     args = p.parse_args(argv)
-    net = None
+    net = vgg = None
+    if args.perceptual:
+        try:
+            layers = None if args.vgg_layers is None else {k: float(v) for k, v in (item.split('=', 1) for item in args.vgg_layers)}
+        except ValueError:
+            raise SystemExit('error: --vgg_layers takes NAME=WEIGHT items, e.g. conv5_4=1')
+        if args.vgg_weights is None:
+            torch.manual_seed(0 if args.random_init_seed is None else args.random_init_seed)
+        vgg = load_vgg(args.vgg_weights, layer_weights=layers, device='cuda' if torch.cuda.is_available() else None)
     if args.identity:
         if (args.arcface_weights is None) == (args.random_init_seed is None):
             raise SystemExit('error: --identity needs exactly one of --arcface_weights PATH and --random_init_seed N')
@@ -80,15 +97,18 @@ def main(argv=None):
                 b = torch.from_numpy(np.stack([c[2] for c in chunk])).cuda()
                 ps, ss = psnr_batch(a, b, **opt).tolist(), ssim_batch(a, b, **opt).tolist()
                 ids = identity_batch(a, b, net).tolist() if net is not None else [None] * len(chunk)
-                for (n, _, _), pv, sv, iv in zip(chunk, ps, ss, ids):
-                    result[n] = {'psnr': pv, 'ssim': sv, **({} if iv is None else {'identity': iv})}
+                pcs = perceptual_batch(a, b, vgg).tolist() if vgg is not None else [None] * len(chunk)
+                for (n, _, _), pv, sv, iv, cv in zip(chunk, ps, ss, ids, pcs):
+                    result[n] = {'psnr': pv, 'ssim': sv, **({} if iv is None else {'identity': iv}), **({} if cv is None else {'perceptual': cv})}
     else:
         for n, a, b in pairs:
             result[n] = {'psnr': calculate_psnr(a, b, **opt), 'ssim': calculate_ssim(a, b, **opt)}
             if net is not None:
                 result[n]['identity'] = calculate_identity(a, b, net)
-    keys = ('psnr', 'ssim') + (('identity',) if net is not None else ())
-    ident = (lambda v: f'\tIDENTITY {v["identity"]:.6f}') if net is not None else (lambda v: '')
+            if vgg is not None:
+                result[n]['perceptual'] = calculate_perceptual(a, b, vgg)
+    keys = ('psnr', 'ssim') + (('identity',) if net is not None else ()) + (('perceptual',) if vgg is not None else ())
+    ident = lambda v: (f'\tIDENTITY {v["identity"]:.6f}' if net is not None else '') + (f'\tPERCEPTUAL {v["perceptual"]:.6f}' if vgg is not None else '')  # noqa: E731
     for n in names:
         print(f'{n}\tPSNR {result[n]["psnr"]:.6f} dB\tSSIM {result[n]["ssim"]:.6f}' + ident(result[n]))
     mean = {k: float(np.mean([result[n][k] for n in names])) for k in keys}
