@@ -236,3 +236,117 @@ def test_script_identity_column(tmp_path, capsys):
         a, b = (torch.from_numpy(imgs[k, i]).to(next(net.parameters()).device) for k in (0, 1))
         assert abs(rec['files'][f'{i}.png']['identity'] - M.calculate_identity(a, b, net)) <= 1e-12
     assert abs(rec['mean']['identity'] - np.mean([rec['files'][f'{i}.png']['identity'] for i in range(2)])) <= 1e-15
+
+
+# ---- the per-element bounds of tools/arcface_check.py: every one a statement about the float64 reference ------------------------------------
+@pytest.fixture(scope='module')
+def ac():
+    from _tools import load_script
+    return load_script('tools/arcface_check.py')
+
+
+def _ratio(got, ref, bound):
+    return float((np.abs(got.astype(np.float64) - ref) / (bound + 1e-300)).max())
+
+
+def test_fc_rows_emulation_within_half_of_the_bound_and_int_coded_exact(ac):
+    assert ac.FC_SHAPES == ((1, 4, 256), (16, 68, 2304), (17, 128, 1024)) and ac.FC_FIN == 8 and ac.fc_coef(2304) == 64 + 3 + 2 + 7
+    for shape in ac.FC_SHAPES:
+        for fam in ac.FC_FAMILIES:
+            x, w, b = ac.fc_family(fam, shape)
+            ref, emu = ac.fc_ref(x, w, b), ac.fc_emulate(x, w, b)
+            r = _ratio(emu, ref, ac.fc_bound(x, w, b))
+            print(f'fc_rows {fam} {shape}: emulation {r:.4f} of the bound')
+            assert r <= 0.5, (fam, shape, r)
+            if fam == 'int_coded':      # whole units of 2^-5, every partial sum below 2^24 of them: float32 is exact
+                S = (np.abs(x.astype(np.float64)) @ np.abs(w.astype(np.float64)).T + np.abs(b)) * 32
+                assert float(S.max()) < 2 ** 24 and np.array_equal(ref * 32, np.round(ref * 32)) and np.array_equal(emu.astype(np.float64), ref)
+            if fam == 'cancel_pairs':   # ill-conditioned: the sum is far below its terms
+                S = np.abs(x.astype(np.float64)) @ np.abs(w.astype(np.float64)).T
+                assert float(np.median(S / np.abs(ref))) >= 100
+            if fam == 'row_scales' and shape[0] > 1:
+                assert b is None and float(np.abs(x[-1]).max() / np.abs(x[0]).max()) > 2.0 ** 36
+        ks = ac.fc_onehot_ks(shape[2])
+        assert {0, 63, 64, 127, 128, 191, 192, 255, shape[2] - 1} <= set(ks) and (shape[2] == 256 or {256, shape[2] - 256, shape[2] - 257} <= set(ks))
+        x, w, b = ac.fc_family('normal', shape)
+        hot = np.zeros((len(ks), shape[2]), np.float32)
+        hot[np.arange(len(ks)), ks] = 1.0
+        assert np.array_equal(ac.fc_emulate(hot, w, b), (w[:, ks].T + b[None]).astype(np.float32))
+
+
+@pytest.mark.parametrize('slope', R.SLOPES)
+def test_se_gate_emulation_within_half_of_the_bound(ac, slope):
+    assert ac.SE_GATE_SHAPES == ((2, 68, 3), (1, 320, 20), (1, 4096, 256), (2, 128, 8)) and ac.SLOPES == R.SLOPES
+    for shape in ac.SE_GATE_SHAPES:
+        args = ac.gate_inputs(shape, slope)
+        p, w1, b1, w2, b2 = args
+        ref = ac.gate_ref(p, w1, b1, slope, w2, b2)
+        emu, s32 = ac.gate_emulate(p, w1, b1, slope, w2, b2)
+        fig = ac.sigmoid_figure(s32)
+        r = _ratio(emu, ref['out'], ac.gate_bound(p, w1, b1, slope, w2, b2, ref, fig))
+        print(f'se_gate {shape} slope {slope}: emulation {r:.4f} of the bound; sigmoid figure {fig:.3f} u')
+        assert r <= 0.5 and fig <= 4.0, (shape, slope, r, fig)
+        assert float(ref['s'].max()) > 35 and float(ref['s'].min()) < -35 and np.all(np.isfinite(emu)) and emu.min() >= 0 and emu.max() <= 1
+
+
+def test_se_pool_emulation_within_half_of_the_bound_and_int_coded_exact(ac):
+    assert ac.SE_POOL_SHAPES == ((1, 1, 1, 4), (1, 16, 16, 68), (2, 17, 19, 132))
+    for shape in ac.SE_POOL_SHAPES:
+        hw = shape[1] * shape[2]
+        for fam in ac.SE_POOL_FAMILIES:
+            x = ac.pool_family(fam, shape)
+            ref, emu = ac.pool_ref(x), ac.pool_emulate(x)
+            r = _ratio(emu, ref, ac.pool_bound(x))
+            print(f'se_pool {fam} {shape}: emulation {r:.4f} of the bound')
+            assert r <= 0.5, (fam, shape, r)
+            if fam == 'int_coded' and hw & (hw - 1) == 0:
+                assert np.array_equal(emu.astype(np.float64), ref) and float(np.abs(x).max()) * hw < 2 ** 24
+            if fam == 'cancel' and hw > 1:      # the mean is the ripple: far below |x|
+                assert float(np.abs(ref).max()) < 1e-3 and float(np.abs(x).mean()) > 0.5
+            if fam == 'mixed' and shape[3] > 4:
+                assert float(np.abs(ref[:, -1]).max() / np.abs(ref[:, 0]).max()) > 2.0 ** 30
+
+
+def test_cosine_rows_emulation_within_half_of_the_bound(ac):
+    for n in (1, 63, 65):
+        for rows in (1, 4, 5):
+            for norm in (1.0, 1e-20, 1e18):
+                x, y = ac.cosine_rows_family(rows, n, norm)
+                ref = ac.cosine_ref(x, y)
+                r = _ratio(ac.cosine_emulate(x, y), ref, ac.cosine_bound(x, y))
+                assert r <= 0.5, (n, rows, norm, r)
+                if norm == 1e-20:   # the floor decides
+                    assert np.allclose(ref, (x.astype(np.float64) * y).sum(1) / 1e-8, rtol=1e-15) and float(np.abs(ref).max()) < 1e-30
+
+
+@pytest.mark.parametrize('shape', [(1, 1, 1, 3), (1, 2, 3, 3), (1, 127, 129, 3), (1, 300, 5, 3)])
+@pytest.mark.parametrize('dtype', ['uint8', 'float32'])
+def test_identity_input_host_definition_per_image_bound(ac, shape, dtype):
+    """The host definition against the float64 bilinear resize of the gray image under arcface_check.identity_bound."""
+    rng = np.random.default_rng(sum(shape))
+    img = torch.from_numpy(rng.integers(0, 256, shape).astype(np.uint8) if dtype == 'uint8' else rng.random(shape).astype(np.float32))
+    out = M.identity_input(img)
+    gray = M.identity_gray_host(img).double()
+    ref = F.interpolate(gray[:, None], size=(128, 128), mode='bilinear', align_corners=False)
+    bound = ac.identity_bound(gray.numpy())
+    err = float((out.double() - ref).abs().max())
+    print(f'identity_input {shape} {dtype}: |host - float64 resize| {err:.3e}, bound {float(bound[0]):.3e}')
+    assert err <= float(bound[0]) and ac.identity_weights_exact(shape[1]) and ac.identity_weights_exact(shape[2]) and ac.identity_weights_exact(32767)
+    if shape[1:3] == (1, 1):
+        assert torch.equal(out, M.identity_gray_host(img)[:, None].expand(1, 1, 128, 128))
+
+
+@pytest.mark.parametrize('cin,cout,H,W,B', [(32, 32, 9, 5, 1), (64, 64, 8, 8, 2), (128, 128, 25, 41, 1)])
+@pytest.mark.parametrize('slope', (-0.5, 1.5))
+def test_block_emulation_within_half_of_the_composed_bound(ac, cin, cout, H, W, B, slope):
+    """arcface_check.block_ref: the float32 CPU evaluation of the folded dataflow against the float64 one on the same float32-rounded parameters;
+    in float64 that dataflow is the module up to the fold's rounding."""
+    blk = R.fill_state(A.IRBlock(cin, cout, use_se=False), 400 + cin + H, slope=slope).eval()
+    x = torch.from_numpy(np.random.default_rng(cin + W).normal(0., 1., (B, cin, H, W)).astype(np.float32))
+    with torch.no_grad():
+        ref, bound = ac.block_ref(blk, x)
+        r = float(((ac.block_emulate(blk, x).double() - ref).abs() / bound).max())
+        mod = blk.double()(x.double())
+    print(f'IRBlock({cin}, {cout}) {H}x{W} slope {slope}: emulation {r:.4f} of the bound')
+    assert r <= 0.5 and bool((bound > 0).all())
+    assert float((mod - ref).abs().max()) <= 1e-4 * float(ref.abs().max())      # (float32-rounded folded weights against the module in float64)

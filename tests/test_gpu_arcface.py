@@ -6,6 +6,35 @@ reference is the reference module's own CPU forward (whole network: recorded in 
 summation order over K up to 32768.  Every measured ratio is printed before it is asserted.  Everything else is bitwise.
 
 Measured on an MI355X (ratio e(device) / e(float32 reference)): see profiles/NOTES.md, "ArcFace".
+
+Per element (the second half of this file).  The yardstick is blind to elements small next to the tensor's largest, so every kernel of
+cf_arcface.hip is also held, element by element, to a bound derived from the order its comment states -- tools/arcface_check.py has the recipes,
+the float64 references, the bounds and a NumPy float32 emulation of each order; tests/test_arcface_host.py shows on the CPU that the emulation
+stays within 0.5 of every bound and that the exact families are exact.  Largest |error| / bound on an MI355X (every ratio is printed, `RATIO ...`):
+  fc_rows  (1, 4, 256), (16, 68, 2304), (17, 128, 1024)     int_coded 0 (bitwise float64), one-hot rows bitwise fl(w[n, k] + b[n]) on both sides of every
+           quarter and chunk boundary, cancel_pairs 0.0008, row_scales 0.0068, normal 0.0071
+  se_gate  (2, 68, 3) 0.0258, (1, 320, 20) 0.0005, (1, 4096, 256) < 5e-5, (2, 128, 8) 0.0028, four slopes each; pre-activations of +-40 give exactly 1 and
+           < 1e-14, never NaN.  Measured sigmoid figure (torch's CPU float32 sigmoid against float64 on the same pre-activations): 1.46 .. 1.90 u sigmoid(s)
+  se_pool  normal 0.0519, cancel 0.0159, mixed 0.0568, int_coded 0.0039 (bitwise where H W is a power of two)
+  cosine_rows  n 1, 63, 65 x rows 1, 4, 5 x norms 1, 1e-20, 1e+18: 0.0405
+  prelu_maxpool2, se_scale_res_prelu, identity_input: bitwise (torch's CPU ops / the host definition)
+  IRBlock without SE on the forms the network never reaches (reference: the folded dataflow in float64 on the float32-rounded folded parameters):
+           128 -> 128 at 25x41 (`128`) 0.0025, 32 -> 32 at 9x5 (`32`) 0.0066, 64 -> 64 at 8x8 with batch 17 / 33 (the 32- and 64-row bn0 tables) 0.0040;
+           every one of the 17 / 33 rows bitwise the row alone.  IRBlock(64, 96) has no 32-wide form: ops._cout_pad(96) is 128.
+  The bounds are worst cases over every rounding and stand far above a random walk: the emulation sits at the same small ratios (the host test prints
+  them), and each test asserts the kernel's ratio not below 1e-3 of the emulation's.
+Whole file: 91 tests in 4.2 s (46 in 4.1 s before); the slowest new test is se_gate at (1, 4096, 256), 0.06 s.  Nothing failed on the first run.
+
+Scratch builds with one in-range edit each (not committed; addresses, barriers and launch geometry untouched), each run once through this file and
+the tests of tests/test_gpu_conv_prelu.py.  New tests of this file that fail | old ones (the yardstick tests above):
+  (p1) cf_igemm.hip PReLU epilogue as max(t, a t)                 4: the reach blocks at slope 1.5 | r18, the five blocks at slope 1.5
+  (p2) cf_igemm.hip RES_PRELU adds the residual after the select  8: every reach block | r18, 12 block cases
+  (p3) cf_igemm.hip the padding takes the affine prologue's shift 8: every reach block | both networks, all 20 block cases
+  (a4) fc_rows finish starts its chains at c = j + FC_FIN         3: fc_rows_per_element, every shape | fc_rows[128], [132] (K = 1024 is four chunks: all dropped), both networks
+  (a5) se_gate layer 1 stops at c & ~63                           4: se_gate_per_element (2, 68, 3), every slope | 0 (C = 128 everywhere else)
+  (a6) prelu_maxpool2 without the `t != t` clause                 1: prelu_maxpool2_non_finite_values.. | 0
+Plainly: p1 - p3 and a4 are gross and the old yardstick tests catch them too, at the shapes and slopes they run; a5 and a6 are caught by the new
+tests alone.  (tests/test_gpu_conv_prelu.py lists what p1 - p3 do to the per-element conv tests.)
 """
 import copy
 
@@ -245,3 +274,210 @@ def test_identity_batch_invariances(lib, nets):
     # both embeddings of a pair carry a relative error of at most MARGIN * 1.3e-6 (the network gate above), and a cosine moves by at most
     # the sum of the two: 2 * 8 * 1.3e-6, doubled for the host's own float32 error
     assert float((ab.cpu() - host).abs().max()) <= 4e-5
+
+
+# ---- the kernels of cf_arcface.hip per element (tools/arcface_check.py: recipes, float64 references, derived bounds) ---------------------
+@pytest.fixture(scope='module')
+def ac():
+    from _tools import load_script
+    return load_script('tools/arcface_check.py')
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _gate(what, got, ref, bound):
+    """Print the largest |error| / bound, assert it at most 1; -> the ratio."""
+    r = float((np.abs(got.astype(np.float64) - ref) / (bound + 1e-300)).max())
+    print(f'\nRATIO {what}: {r:.4f} of the bound')
+    assert np.all(np.isfinite(got)) and r <= 1.0, (what, r)
+    return r
+
+
+def _fc(lib, x, w, b):
+    return _np(lib.ops.fc_rows(_t(x), lib.ops.pack_fc_rows(_t(w)), None if b is None else _t(b)))
+
+
+@pytest.mark.parametrize('shape', [(1, 4, 256), (16, 68, 2304), (17, 128, 1024)])
+def test_fc_rows_per_element(lib, ac, shape):
+    """One chunk and a column block that is almost wholly the clamp; nine chunks (the finish's second pass), M at the launch limit, a ragged last
+    block; two launches.  int_coded and the one-hot rows bitwise, every family within c u sum |w||x| + 2 u |out| per element."""
+    M, N, K = shape
+    for fam in ac.FC_FAMILIES:
+        x, w, b = ac.fc_family(fam, shape)
+        got, ref = _fc(lib, x, w, b), ac.fc_ref(x, w, b)
+        r = _gate(f'fc_rows {fam} {shape}', got, ref, ac.fc_bound(x, w, b))
+        e = float((np.abs(ac.fc_emulate(x, w, b).astype(np.float64) - ref) / ac.fc_bound(x, w, b)).max())
+        assert r >= 1e-3 * e, (fam, shape, r, e)
+        if fam == 'int_coded':
+            assert np.array_equal(got.astype(np.float64), ref)
+    x, w, b = ac.fc_family('normal', shape)
+    ks = ac.fc_onehot_ks(K)
+    wp, bd = lib.ops.pack_fc_rows(_t(w)), _t(b)
+    for i in range(0, len(ks), M):      # M rows per call, as the shape says
+        sel = ks[i:i + M]
+        hot = np.zeros((len(sel), K), np.float32)
+        hot[np.arange(len(sel)), sel] = 1.0
+        got = _np(lib.ops.fc_rows(_t(hot), wp, bd))
+        assert np.array_equal(_bits(torch.from_numpy(got)), _bits(torch.from_numpy((w[:, sel].T + b[None]).astype(np.float32)))), (shape, sel)
+    if M > 1:   # rows bitwise independent of the batch and of M
+        full = lib.ops.fc_rows(_t(x), wp, bd)
+        for rows in ((0, 1), (M // 2, M // 2 + 3), (M - 1, M)):
+            assert np.array_equal(_bits(lib.ops.fc_rows(_t(x[rows[0]:rows[1]]), wp, bd)), _bits(full[rows[0]:rows[1]])), rows
+
+
+def test_fc_rows_workspace_query_refuses(lib):
+    from codeformer_amd import lib as L
+    q = L.load().cf_fc_rows_workspace_elems
+    assert q(16, 68, 2304) == 9 * 16 * 68 and q(1, 4, 256) == 4
+    for m, n, k in ((0, 64, 256), (17, 64, 256), (4, 64, 255), (4, 64, 128)):
+        assert q(m, n, k) == -1, (m, n, k)
+
+
+@pytest.mark.parametrize('slope', R.SLOPES)
+@pytest.mark.parametrize('shape', [(2, 68, 3), (1, 320, 20), (1, 4096, 256), (2, 128, 8)])
+def test_se_gate_per_element(lib, ac, shape, slope):
+    """C off 64 and 256, r off 4, the limits 4096 / 256; pre-activations of +-40 in every seventh channel: the gate is finite, in [0, 1], within the bound."""
+    p, w1, b1, w2, b2 = ac.gate_inputs(shape, slope)
+    got = _np(lib.ops.se_gate(*(_t(v) for v in (p, w1, b1)), slope, _t(w2), _t(b2)))
+    ref = ac.gate_ref(p, w1, b1, slope, w2, b2)
+    emu, s32 = ac.gate_emulate(p, w1, b1, slope, w2, b2)
+    fig = ac.sigmoid_figure(s32)
+    bound = ac.gate_bound(p, w1, b1, slope, w2, b2, ref, fig)
+    r = _gate(f'se_gate {shape} slope {slope} (sigmoid figure {fig:.3f} u)', got, ref['out'], bound)
+    e = float((np.abs(emu.astype(np.float64) - ref['out']) / bound).max())
+    assert r >= 1e-3 * e, (shape, slope, r, e)
+    assert got.min() >= 0.0 and got.max() <= 1.0 and float(ref['s'].max()) > 35 and float(ref['s'].min()) < -35
+    hi, lo = ref['s'] > 35, ref['s'] < -35
+    assert np.all(got[hi] == 1.0) and np.all(got[lo] < 1e-14)
+
+
+def test_se_gate_refuses_sizes_past_its_limits(lib):
+    z = lambda *s: torch.zeros(*s, device='cuda')   # noqa: E731
+    with pytest.raises(RuntimeError, match='cf_se_gate: bad dims'):
+        lib.ops.se_gate(z(1, 4097), z(4, 4097), z(4), 0.25, z(4097, 4), z(4097))
+    with pytest.raises(RuntimeError, match='cf_se_gate: bad dims'):
+        lib.ops.se_gate(z(1, 64), z(257, 64), z(257), 0.25, z(64, 257), z(64))
+
+
+@pytest.mark.parametrize('shape', [(1, 1, 1, 4), (1, 16, 16, 68), (2, 17, 19, 132)])
+def test_se_pool_per_element(lib, ac, shape):
+    """(31 + nrb + 2) u sum |x| / HW per channel: a bound that stands on cancelling and mixed-scale input, where H W ulp(|mean|) cannot be stated."""
+    hw = shape[1] * shape[2]
+    for fam in ac.SE_POOL_FAMILIES:
+        x = ac.pool_family(fam, shape)
+        got, ref = _np(lib.ops.se_pool(_t(x))), ac.pool_ref(x)
+        r = _gate(f'se_pool {fam} {shape}', got, ref, ac.pool_bound(x))
+        e = float((np.abs(ac.pool_emulate(x).astype(np.float64) - ref) / (ac.pool_bound(x) + 1e-300)).max())
+        assert r >= 1e-3 * e, (fam, shape, r, e)
+        if fam == 'int_coded' and hw & (hw - 1) == 0:
+            assert np.array_equal(got.astype(np.float64), ref)
+
+
+def test_prelu_maxpool2_non_finite_values_ties_and_signed_zeros(lib):
+    """(2, 4, 6, 8): a NaN in each of the four window positions wins and stays in its window; -inf under a negative slope becomes +inf and wins; four
+    equal values; -0.0 against +0.0: the bits of torch's CPU max_pool2d(prelu(x))."""
+    rng = np.random.default_rng(31)
+    base = torch.from_numpy(rng.normal(0., 1., (2, 4, 6, 8)).astype(np.float32))
+
+    def both(x, slope):
+        nchw = x.permute(0, 3, 1, 2)
+        ref = F.max_pool2d(F.prelu(nchw, torch.tensor([slope])), 2, 2).permute(0, 2, 3, 1).contiguous()
+        return lib.ops.prelu_maxpool2(x.cuda(), slope).cpu(), ref
+    for slope in (0.25, -0.5):
+        clean, ref = both(base, slope)
+        assert np.array_equal(_bits(clean), _bits(ref))
+        for dy, dx in ((0, 0), (0, 1), (1, 0), (1, 1)):
+            x = base.clone()
+            x[1, 2 + dy, 2 + dx, 3] = float('nan')
+            got, ref = both(x, slope)
+            assert bool(torch.isnan(got[1, 1, 1, 3])) and bool(torch.isnan(ref[1, 1, 1, 3]))
+            got[1, 1, 1, 3] = clean[1, 1, 1, 3]
+            assert np.array_equal(_bits(got), _bits(clean)), (slope, dy, dx)
+        x = base.clone()
+        x[0, 0, 0, 0], x[0, 1, 3, 1], x[1, 3, 5, 7] = float('inf'), float('-inf'), float('-inf')
+        x[0, 2:4, 0:2, 5] = 0.75                                     # four equal values
+        x[1, 0, 0, 2], x[1, 0, 1, 2], x[1, 1, 0, 2], x[1, 1, 1, 2] = -0.0, 0.0, -0.0, -0.0      # signed zeros, either order
+        x[1, 0, 2, 2], x[1, 0, 3, 2], x[1, 1, 2, 2], x[1, 1, 3, 2] = 0.0, -0.0, -0.0, -0.0
+        got, ref = both(x, slope)
+        assert np.array_equal(_bits(got), _bits(ref)), slope
+        assert float(got[0, 0, 0, 0]) == float('inf') and float(got[0, 1, 0, 5]) == 0.75
+        assert (float(got[0, 0, 1, 1]) == float('inf')) == (slope < 0) and (float(got[1, 1, 2, 7]) == float('inf')) == (slope < 0)
+        assert bool(torch.isfinite(got).sum() == got.numel() - (3 if slope < 0 else 1))
+    got, ref = both(x, 0.0)                                          # slope 0: 0 * (-inf) is NaN, and it wins
+    assert bool(torch.isnan(got[0, 0, 1, 1])) and np.array_equal(_bits(got), _bits(ref))
+
+
+def test_se_scale_res_prelu_without_residual_and_with_a_gate_per_image(lib):
+    rng = np.random.default_rng(41)
+    x = torch.from_numpy(rng.normal(0., 1., (3, 5, 7, 12)).astype(np.float32))      # H W C / 4 = 105 float4 per image: no multiple of the block
+    res = torch.from_numpy(rng.normal(0., 1., (3, 5, 7, 12)).astype(np.float32))
+    y = torch.from_numpy(rng.uniform(0., 1., (3, 12)).astype(np.float32))
+    assert not torch.equal(y[0], y[1]) and not torch.equal(y[1], y[2])
+    xy = x * y.view(3, 1, 1, 12)
+    assert np.array_equal(_bits(lib.ops.se_scale_res_prelu(x.cuda(), y.cuda(), None, 1.0)), _bits(xy))
+    for slope in R.SLOPES:
+        a = torch.tensor(slope)
+        for r, t in ((None, xy), (res, xy + res)):
+            want = torch.where(t > 0, t, a * t)
+            got = lib.ops.se_scale_res_prelu(x.cuda(), y.cuda(), None if r is None else r.cuda(), slope)
+            assert np.array_equal(_bits(got), _bits(want)), (slope, r is None)
+    one = lib.ops.se_scale_res_prelu(x[2:3].cuda(), y[2:3].cuda(), res[2:3].cuda(), -0.5)
+    assert np.array_equal(_bits(one), _bits(lib.ops.se_scale_res_prelu(x.cuda(), y.cuda(), res.cuda(), -0.5)[2:3]))
+
+
+@pytest.mark.parametrize('n', [1, 63, 65])
+def test_cosine_rows_per_element(lib, ac, n):
+    """rows 1, 4, 5 (four rows per block); norms 1, 1e-20 (the product falls below the 1e-8 floor: the floor decides) and 1e+18."""
+    for rows in (1, 4, 5):
+        for norm in (1.0, 1e-20, 1e18):
+            x, y = ac.cosine_rows_family(rows, n, norm)
+            got = _np(lib.ops.cosine_rows(_t(x), _t(y)))
+            assert got.dtype == np.float64 and got.shape == (rows,)
+            _gate(f'cosine_rows n {n} rows {rows} norm {norm:g}', got, ac.cosine_ref(x, y), ac.cosine_bound(x, y))
+            if norm == 1e-20:
+                assert float(np.abs(got).max()) < 1e-30 and (n > 1 or np.all(got != 0))
+
+
+@pytest.mark.parametrize('dtype', ['uint8', 'float32'])
+@pytest.mark.parametrize('shape', [(1, 1, 1, 3), (1, 2, 3, 3), (1, 127, 129, 3), (1, 300, 5, 3)])
+def test_identity_input_small_and_odd_sizes_are_bitwise_the_host_definition(lib, shape, dtype):
+    """One pixel, fewer pixels than taps, odd sizes either side of 128, a strip.  (tests/test_arcface_host.py holds the host definition against the
+    float64 bilinear resize under arcface_check.identity_bound.)"""
+    img = _image(shape, dtype, sum(shape))
+    assert np.array_equal(_bits(lib.M.identity_input(img.cuda())), _bits(lib.M.identity_input(img)))
+
+
+# ---- the block on the forms the network never reaches, per element -------------------------------------------------------------------
+REACH_BLOCKS = {   # name: (planes, H, W, batch, the form conv1 and conv2 take)
+    'wide_128': (128, 25, 41, 1, '128'),        # cout_pad % 128 == 0 and 1025 pixels: the first size past `narrow`
+    'rung_32': (32, 9, 5, 1, '32'),
+    'rows_17': (64, 8, 8, 17, '64'),            # the 32-row bn0 table
+    'rows_33': (64, 8, 8, 33, '64'),            # the 64-row bn0 table
+}
+# (IRBlock(64, 96) does not exist on the device as a 32-wide form: ops._cout_pad(96) is 128, the packer has no cout_pad of 96)
+
+
+@pytest.mark.parametrize('slope', (-0.5, 1.5))
+@pytest.mark.parametrize('name', list(REACH_BLOCKS))
+def test_block_on_the_forms_the_network_never_reaches(lib, ac, name, slope):
+    from _tools import load_script
+    c, H, W, B, form = REACH_BLOCKS[name]
+    gc = load_script('tools/conv_geom_check.py')
+    assert lib.ops._cout_pad(96) == 128
+    for epi in gc.PRELU_EPIS:      # conv1 (AFFINE, PRELU) and conv2 (none, RES_PRELU) at the block's shape
+        assert gc.route_of(0, gc.G(B, H, W, c, c, epi=epi, alpha=slope)) == ('prelu', form), (name, epi)
+    blk = R.fill_state(lib.A.IRBlock(c, c, use_se=False), 500 + c + H, slope=slope).eval()
+    x = torch.from_numpy(np.random.default_rng(c + B).normal(0., 1., (B, c, H, W)).astype(np.float32))
+    with torch.no_grad():
+        ref, bound = ac.block_ref(blk, x)
+        e = float(((ac.block_emulate(blk, x).double() - ref).abs() / bound).max())
+    blk = blk.cuda()
+    dev = blk(x.cuda())
+    r = _gate(f'IRBlock({c}, {c}) {H}x{W} batch {B} slope {slope} form {form}', _np(dev), ref.numpy(), bound.numpy())
+    assert r >= 1e-3 * e, (name, r, e)
+    if B > 16:
+        assert blk._pre_tables(B)[0].shape[0] == B and blk._pre_tables(B)[0]._base is not None and blk._pre_tables(B)[0]._base.shape[0] == (32 if B == 17 else 64)
+        for b in range(B):
+            assert np.array_equal(_bits(blk(x[b:b + 1].cuda())), _bits(dev[b:b + 1])), b

@@ -20,6 +20,9 @@ kernel | CPU emulation (test_family_within_the_gate prints every single ratio; o
     solo_cin              0.3512 | 0.3832 -               0.4747 | 0.4747 0.4995 | 0.4995 .               .               .               .
     solo_cin_act          0.4072 | 0.4072 0.4547 | 0.4547 0.4981 | 0.4981 0.4998 | 0.4995 .               .               .               .
     onehot_pixels         0.4220          0.3679          0.4273          0.4157          0.4741          0.4193          0.2292          0.2243
+(the PReLU instantiations -- route `prelu` of conv_geom_check, merged in by with_prelu() -- have a file of their own, tests/test_gpu_conv_prelu.py, which calls the
+tests of this file that fit; its column, kernel | emulation: mixed_cout 0.4333 | 0.4333, mixed_cin 0.0403 | 0.0162, mixed_cin_act 0.0440 | 0.0182, cancel_pairs
+0.0020 | 0.0046, dc_plus_ripple 0.0109 | 0.0089, swish_leaky_edges 0.3609 | 0.3609, swish_leaky_edges_sft -, solo ., onehot_pixels 0.4312.)
 (.: the solo families run on the two split-half routes and their fp32 partners only.  Their c1 cells sit at one half by construction: a 1x1 with one input
 channel per output is ONE product, every rounding on its way is entered at a whole ulp and attains half of that -- see conv_geom_check.)
 (equal pairs: one rounding both evaluations make alike -- the residual add of swish_leaky_edges, the half rounding of a small channel's weight in

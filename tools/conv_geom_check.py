@@ -1,19 +1,22 @@
 """The stride-2, 1x1 and general-geometry convolutions per element: what tools/conv_check.py does for 3x3 stride 1 on whole tiles, for every other form
 cf_conv2d dispatches to with fp32 or split-half operands.  Library of tests/test_gpu_conv_geom.py (GPU) and tests/test_conv_geom_host.py (CPU); the
 families, rnd, prologue64, act_scale_of, _halves, ratio, bits_equal and U are conv_check's own (family_at: its recipes at another geometry).
-usage (GPU box): python tools/conv_geom_check.py [--ends]    one line per (family, case, route): kernel error, emulation error, both as parts of the gate
+usage (GPU box): python tools/conv_geom_check.py [--ends] [--prelu]    one line per (family, case, route): kernel error, emulation error, both as parts of the gate
+(--prelu: with the PReLU instantiations, PRELU_CASES -- the library of tests/test_gpu_conv_prelu.py and tests/test_conv_prelu_host.py; see with_prelu())
 (--ends: with the NCHW ends, END_CASES -- the library of tests/test_gpu_conv_ends.py and tests/test_conv_ends_host.py; see with_nchw_ends())
 Out of scope: the single-16-bit direct forms (pack_weight(f16=True) / bf16 operands) and bf16 tensors (io_bf16).
 
 Geometry (Geo; CASES: key -> Geo): B, H, W of the INPUT, cin, cout, c_split | taps 1 | 9, stride 1 | 2, up (nearest x2 first), pad_mode, pad_lo,
 sliced (x = buf[..., 16:48] of an 80-wide buffer, x2 = buf2[..., :32] of a 48-wide one, out = obuf[..., 32:96] of a 128-wide one; res / res2 share the
-output's stride), epi (LEAKY / AXPY / AXPY2, on the NCHW input end RESIDUAL / SFT: the case's own epilogue instead of the family's), out_nchw, in_nchw
+output's stride), epi (LEAKY / AXPY / AXPY2 / PRELU / RES_PRELU, on the NCHW input end RESIDUAL / SFT: the case's own epilogue instead of the family's), alpha (the
+PReLU slope of the case, one of SLOPES = tests/arcface_ref.SLOPES: -0.5, 0, 0.25, 1.5 -- negative, zero, ordinary, above one, two significant bits at most), out_nchw, in_nchw
 (the family's NHWC input is handed over as its NCHW permutation; the reference is unchanged).  Nothing above 128x128x32 in or 64x64x384 out.
 The fp64 reference is written from the definitions: padded() builds the image the definition convolves -- F.pad(.., (0, 1, 0, 1)) for stride 2 with
 pad_lo = 0, one row / column of zeros (padding = 1) or mode='reflect' on every side for pad_lo = 1 and for stride 1, nearest x2 and THEN reflect padding
 of the upsampled image for PAD_EDGE -- and an unpadded F.conv2d of the case's stride follows; taps 1 is a matrix product.  Epilogues as the header
 writes them: LEAKY pre > 0 ? pre : 0.2f pre; AXPY pre alpha + res; AXPY2 (pre alpha + res) alpha + res2, alpha = sft_w as the float the descriptor
-carries (0.2f and float(alpha) are the kernel's constants: the reference takes them as given, so they enter no gate).
+carries (0.2f and float(alpha) are the kernel's constants: the reference takes them as given, so they enter no gate); PRELU t = pre, RES_PRELU t = pre + res,
+out = t > 0 ? t : a t -- a select on the sign of t, never max(t, a t).
 tests/test_conv_geom_host.py holds the reference against an index-by-index loop for each padding rule.
 
 Routes (ROUTES; route_of() restates conv_validate's `ext` predicate, launch_direct, launch_ladder, conv1x1_mtiles (cf_igemm.hip) and cf_split_launch;
@@ -27,6 +30,15 @@ weights are packed with the explicit code 0 or ops.SPLIT (stride2=True / a 1x1 w
   ext_d32    code 0   the EXT instantiations of 3x3 stride 1 (off-grid size, reflect, channel slices, LEAKY / AXPY / AXPY2): rungs `128`, `64`, `32`
   ext_up     code 0   the EXT instantiations of the folded upsample (off-grid source, PAD_EDGE): rungs `128`, `64`
   d32_32     code 0   the dense 32-wide rung (cout_pad == 32 on whole 16x16 tiles)
+  (the route below is PRELU_CASES', merged in by with_prelu())
+  prelu      code 0   the five igemm_kernel<.., PRELU = true> instantiations behind CF_EPI_PRELU / CF_EPI_RES_PRELU (route_of() restates the `f.ext &&
+                      d->epilogue >= CF_EPI_PRELU` branch of launch_direct and conv_validate's narrow = cout_pad % 128 == 0 && hout wout <= 1024): `s2` (stride 2,
+                      pad_lo 0 and 1; the residual has the output's shape), `narrow` (8x8 and 32x32 = exactly 1024 pixels, the predicate's last size), `128` (25x41 =
+                      1025 pixels, the first size past it, off-grid), `64` (19x35), `32` (9x5).  Thirteen cases q*: every form sees a negative slope and one above
+                      one, slopes 0 and 0.25 on q64c, q32c, qs1p; every form has a case of cin 32 (two K slabs; qna: 64, four).  ArcFace's pairings are among the
+                      families: prologue AFFINE + PRELU (conv1 with bn0: mixed_cout, mixed_cin, cancel_pairs on the PRELU cases) and prologue none + RES_PRELU
+                      (conv2: dc_plus_ripple, mixed_cin_act, int_coded variant 0 on the RES_PRELU cases).  The packer has no cout_pad of 96
+                      (ops._cout_pad(96) is 128), so the 32-wide form exists at cout <= 32 only.
   (the forms below that no case of CASES reaches -- `few_cout 4`, `few_cout 3` and the whole nchw_in route -- are END_CASES', merged in by with_nchw_ends())
   head       code 0   the few-channel NCHW head (cout <= 4, out_nchw): `few_cout reflect` (cout 3, reflect padding), and under zero padding `few_cout 4`
                       (cout 1, 2, 4: conv3x3_few_cout_kernel<4>) and `few_cout 3` (<3>), at 21x37 and 16x16 with c0 = 16, 32, 64 (1, 2, 4 chunks of the two-slab gather)
@@ -70,6 +82,12 @@ Gate, against fp64, PER ELEMENT, the form of conv_check.gate (u = 2^-24):    gat
          LEAKY   out = pre > 0 ? pre : fl(0.2f pre): the map has slope <= 1, so g0 passes unchanged; one product: g0 + 2 u |out|
          AXPY    out = fl(fl(pre a) + res): |a| g0 + 2 u |a pre| + 2 u |out|
          AXPY2   t = fl(fl(pre a) + res), out = fl(fl(t a) + res2): a^2 g0 + 2 u (a^2 |pre| + |a t|) + 2 u |a t| + 2 u |out|
+         PRELU   out = t > 0 ? t : fl(a t), t = pre: the map has slope <= max(1, |a|); where the computed and the true t differ in sign, |t| + |t'| = |t - t'|
+                 and the same factor holds; one product: max(1, |a|) g0 + 2 u |out|
+         RES_PRELU   t = fl(pre + res): max(1, |a|) (g0 + 2 u |t|) + 2 u |out|
+         (int_coded stays exact: a = m 2^e with m = 1 or 3, so a t is a whole number of units 2^e and exactness_preconditions() holds 3 |t| below 2^24 of
+         them; tap_shift is bitwise the float32 definition prelu32(): pre = +-x is exact, fl(pre + res) and fl(a t) are what float32 does.  swish_leaky_edges
+         runs on the RES_PRELU cases, whose epilogue still adds the family's residual; swish_leaky_edges_sft drops out: EXT has no SFT.)
   The solo families take conv_check's two changes: c counts the ONE channel whose product exists (taps instead of taps cin), and the floor sums |p(x)| over
   that channel alone and enters the subnormal half's spacing whole, 2^-24.  At taps 1 in fp32 the whole sum is one product: its rounding, and the affine
   prologue's two, are then single roundings that attain their u, and go in at a whole ulp each (c = 2, 2 P) -- found by the host test, whose emulation
@@ -104,6 +122,9 @@ from conv_case import stats_rel_err  # noqa: E402,F401
 
 PRO_NONE, PRO_AFFINE, PRO_AFFINE_SWISH, PRO_LEAKY = ops.PRO_NONE, ops.PRO_AFFINE, ops.PRO_AFFINE_SWISH, ops.PRO_LEAKY
 EPI_NONE, EPI_RESIDUAL, EPI_SFT, EPI_LEAKY, EPI_AXPY, EPI_AXPY2 = ops.EPI_NONE, ops.EPI_RESIDUAL, ops.EPI_SFT, ops.EPI_LEAKY, ops.EPI_AXPY, ops.EPI_AXPY2
+EPI_PRELU, EPI_RES_PRELU = ops.EPI_PRELU, ops.EPI_RES_PRELU
+PRELU_EPIS = (EPI_PRELU, EPI_RES_PRELU)
+SLOPES = (-0.5, 0.0, 0.25, 1.5)        # tests/arcface_ref.SLOPES: negative, zero, ordinary, above one; at most two significant bits each
 PAD_ZERO, PAD_REFLECT, PAD_EDGE = ops.PAD_ZERO, ops.PAD_REFLECT, ops.PAD_EDGE
 SLOPE = float(np.float32(0.2))
 ROUTES = ('s2_d32', 's2_dsplit', 'c1_d32', 'c1_dsplit', 'ext_d32', 'ext_up', 'd32_32', 'head')
@@ -115,11 +136,12 @@ SOLO_ROUTES = ('s2_d32', 's2_dsplit', 'c1_d32', 'c1_dsplit')
 GATE_FAMILIES = cc.GATE_FAMILIES
 SLICE = dict(x=(80, 16), x2=(48, 0), out=(128, 32))      # (buffer width, first channel) of the sliced case
 
-Geo = collections.namedtuple('Geo', 'B H W cin cout c_split taps stride up pad_mode pad_lo sliced epi out_nchw in_nchw')
+Geo = collections.namedtuple('Geo', 'B H W cin cout c_split taps stride up pad_mode pad_lo sliced epi out_nchw in_nchw alpha')
 
 
-def G(B, H, W, cin, cout, c_split=None, taps=9, stride=1, up=False, pad_mode=PAD_ZERO, pad_lo=0, sliced=False, epi=None, out_nchw=False, in_nchw=False):
-    return Geo(B, H, W, cin, cout, c_split, taps, stride, up, pad_mode, pad_lo, sliced, epi, out_nchw, in_nchw)
+def G(B, H, W, cin, cout, c_split=None, taps=9, stride=1, up=False, pad_mode=PAD_ZERO, pad_lo=0, sliced=False, epi=None, out_nchw=False, in_nchw=False, alpha=None):
+    assert (alpha is not None) == (epi in PRELU_EPIS) and (alpha is None or alpha in SLOPES)
+    return Geo(B, H, W, cin, cout, c_split, taps, stride, up, pad_mode, pad_lo, sliced, epi, out_nchw, in_nchw, alpha)
 
 
 CASES = {
@@ -147,7 +169,21 @@ END_CASES.update({'nm3a': G(2, 16, 16, 3, 64, in_nchw=True, epi=EPI_RESIDUAL), '
 # the output end under zero padding: cout in {1, 2, 4} (conv3x3_few_cout_kernel<4>) and 3 (<3>), off and on the tile grid, one, two and four 16-channel
 # chunks (the two-slab gather has an odd and an even count to get right)
 END_CASES.update({f'h{n}{t}{c}': G(2, H, W, c, n, out_nchw=True) for n in (1, 2, 4, 3) for t, (H, W) in (('a', (21, 37)), ('b', (16, 16))) for c in (16, 32, 64)})
-SEED_INDEX = {k: i for i, k in enumerate(sorted(CASES) + list(END_CASES))}       # (a case of CASES keeps the seed of its place in sorted(CASES))
+# ---- the PReLU instantiations (route `prelu`; tests/test_gpu_conv_prelu.py, tests/test_conv_prelu_host.py): like the NCHW ends they live beside CASES and
+# are merged in by with_prelu(), so what the earlier test files pin stays.  The smallest shapes that reach each form and its edges; the slope is the case's own
+PRELU_CASES = {
+    'q64a': G(2, 19, 35, 32, 64, epi=EPI_PRELU, alpha=-0.5), 'q64b': G(2, 19, 35, 32, 64, epi=EPI_RES_PRELU, alpha=1.5),
+    'q64c': G(2, 19, 35, 32, 64, epi=EPI_PRELU, alpha=0.0),
+    'q32a': G(1, 9, 5, 16, 32, epi=EPI_PRELU, alpha=1.5), 'q32b': G(1, 9, 5, 32, 32, epi=EPI_RES_PRELU, alpha=-0.5),
+    'q32c': G(1, 9, 5, 16, 32, epi=EPI_RES_PRELU, alpha=0.25),
+    'qna': G(2, 8, 8, 64, 128, epi=EPI_RES_PRELU, alpha=-0.5), 'qnb': G(1, 32, 32, 32, 128, epi=EPI_PRELU, alpha=1.5),
+    'q128a': G(1, 25, 41, 32, 128, epi=EPI_PRELU, alpha=-0.5), 'q128b': G(1, 25, 41, 32, 128, epi=EPI_RES_PRELU, alpha=1.5),
+    'qs0': G(2, 20, 36, 32, 128, stride=2, epi=EPI_PRELU, alpha=1.5), 'qs1': G(2, 20, 36, 32, 128, stride=2, pad_lo=1, epi=EPI_RES_PRELU, alpha=-0.5),
+    'qs1p': G(2, 20, 36, 32, 128, stride=2, pad_lo=1, epi=EPI_PRELU, alpha=0.25),
+}
+PRELU_KEYS = tuple(PRELU_CASES)
+PRELU_ROUTES = ('prelu',)
+SEED_INDEX = {k: i for i, k in enumerate(sorted(CASES) + list(END_CASES) + list(PRELU_CASES))}       # (a case of CASES keeps the seed of its place in sorted(CASES))
 OFF_GRID_NCHW = (G(2, 17, 19, 3, 64, in_nchw=True), G(2, 24, 40, 3, 64, in_nchw=True))       # refused: see route_of()
 BIG = ('s2c', 'p1c')      # the cases that exist for a 128-wide form: tap_shift runs three of its nine taps there
 
@@ -158,6 +194,15 @@ def with_nchw_ends():
     CASES.update(END_CASES)
     if 'nchw_in' not in ROUTES:
         ROUTES = ROUTES + ('nchw_in',)
+    routes.cache_clear()
+
+
+def with_prelu():
+    """CASES and ROUTES of this module object with the PReLU instantiations in them."""
+    global ROUTES
+    CASES.update(PRELU_CASES)
+    if 'prelu' not in ROUTES:
+        ROUTES = ROUTES + PRELU_ROUTES
     routes.cache_clear()
 
 
@@ -220,6 +265,12 @@ def route_of(code, g):
     cp = max(64, ops._cout_pad(g.cout)) if g.up else ops._cout_pad(g.cout)
     ext = g.sliced or epi >= EPI_LEAKY or ((g.pad_mode != PAD_ZERO or g.pad_lo) and not (g.out_nchw and g.cout <= 4)) or \
         (g.taps == 9 and g.stride == 1 and not few_cout and (Ho % 16 != 0 or Wo % 16 != 0))
+    if epi >= EPI_PRELU:                                                 # conv_validate: ext (epilogue >= LEAKY), fp32 operands, no upsample, NHWC
+        if not (g.taps == 9 and (g.stride == 1 or cp % 128 == 0) and not g.out_nchw and g.cout % 4 == 0 and not g.up):
+            return None
+        # launch_direct, the `f.ext && d->epilogue >= CF_EPI_PRELU` branch; narrow is conv_validate's cout_pad % 128 == 0 && hout * wout <= 1024
+        narrow = cp % 128 == 0 and px <= 1024
+        return 'prelu', 's2' if g.stride == 2 else 'narrow' if narrow else '128' if cp % 128 == 0 else '64' if cp % 64 == 0 else '32'
     if ext:
         if not (g.taps == 9 and (g.stride == 1 or cp % 128 == 0) and not g.out_nchw and g.cout % 4 == 0 and epi != EPI_SFT) or (g.up and cp % 64):
             return None
@@ -260,6 +311,8 @@ def cases_of(route):
 def epilogues_of(route, form):
     if route == 'head' or form in ('few_cin 3', 'few_cin n'):
         return (EPI_NONE,)
+    if route == 'prelu':
+        return PRELU_EPIS
     if route in ('ext_d32', 'ext_up') or form == 'ext':
         return (EPI_NONE, EPI_RESIDUAL, EPI_LEAKY, EPI_AXPY, EPI_AXPY2)
     return (EPI_NONE, EPI_RESIDUAL, EPI_SFT)
@@ -310,6 +363,8 @@ def family(name, key, variant=0):
                      positions=lambda bi: onehot_positions(g, bi), key=key, bare_up=False)
     if g.epi is not None:
         d['epi'] = g.epi
+    if g.alpha is not None:
+        d['sft_w'] = g.alpha
     return d
 
 
@@ -330,7 +385,8 @@ def family_of(name, key, route, form, variant=0):
         return None
     d, point = family(name, key, variant), POINT.get(name, ())
     if 'epi' in point and CASES[key].epi is not None:          # (the case's epilogue has replaced the family's)
-        return None
+        if not (name == 'swish_leaky_edges' and CASES[key].epi == EPI_RES_PRELU):      # (RES_PRELU still adds the family's residual)
+            return None
     for what, have, none in (('pro', prologues_of(route), PRO_NONE), ('epi', epilogues_of(route, form), EPI_NONE)):
         if d[what] not in have:
             if what in point:
@@ -393,7 +449,17 @@ def epilogue64(d, pre):
         return pre * alpha_of(d) + r0
     if e == EPI_AXPY2:
         return (pre * alpha_of(d) + r0) * alpha_of(d) + r1
+    if e in PRELU_EPIS:
+        t = pre + r0 if e == EPI_RES_PRELU else pre
+        return torch.where(t > 0, t, alpha_of(d) * t)
     return pre
+
+
+def prelu32(d, pre32):
+    """The two PReLU epilogues in float32 on a float32 `pre`, as the definition orders them: t = fl(pre + res), out = t > 0 ? t : fl(a t).  Where pre is
+    exact in float32 (tap_shift) this IS the float32 result; the fp64 reference rounds a (pre + res) once and differs from it by a double rounding."""
+    t = pre32 + d['res'] if d['epi'] == EPI_RES_PRELU else pre32
+    return torch.where(t > 0, t, torch.tensor(alpha_of(d), dtype=torch.float32) * t)
 
 
 def reference(d, g):
@@ -453,6 +519,10 @@ def gate_of(d, g, route, ref, form=None):
     if e == EPI_LEAKY:
         return g0 + 2 * U * out.abs()
     a = abs(alpha_of(d))
+    if e == EPI_PRELU:
+        return max(1.0, a) * g0 + 2 * U * out.abs()
+    if e == EPI_RES_PRELU:
+        return max(1.0, a) * (g0 + 2 * U * (pre + r0).abs()) + 2 * U * out.abs()
     if e == EPI_AXPY:
         return a * g0 + 2 * U * (a * pre.abs() + out.abs())
     if e == EPI_AXPY2:
@@ -513,6 +583,9 @@ def emulate(d, g, route, act_halves=None):
         v = v * a + r0
     elif e == EPI_AXPY2:
         v = (v * a + r0) * a + r1
+    elif e in PRELU_EPIS:
+        t = v + r0 if e == EPI_RES_PRELU else v
+        v = torch.where(t > 0, t, a * t)
     assert v.dtype == f
     return v
 
@@ -538,11 +611,13 @@ def exactness_preconditions(key, route, form):
             hi, lo = cc.split_halves(t)
             assert np.array_equal(hi, t) and not lo.any()
         a = alpha_of(d) if d['epi'] in (EPI_AXPY, EPI_AXPY2) else d['sft_w'] if d['epi'] == EPI_SFT else 1.0
+        if d['epi'] in PRELU_EPIS:      # a slope m 2^e with m = 1 or 3 (two significant bits): a t is a whole number of units 2^e, and 3 |t| stays below 2^24 of them
+            a = {-0.5: 0.5, 0.0: 1.0, 0.25: 0.25, 1.5: 0.5}[alpha_of(d)]
         unit = 0.5 * 2.0 ** -5 * (a * a if d['epi'] == EPI_AXPY2 else a)
         assert math.log2(unit) == round(math.log2(unit))
         S = _abs_eval(d, g)[0] * (4 if g.up else 1)                       # (a folded tap is a sum of up to four weights)
         epi = float(max(d['b'].abs().max(), d['res'].abs().max() * (1 + d['ss'].abs().max()), d['ss'].abs().max()))
-        tot = (float(S.max()) + epi + float(ref['out'].abs().max())) / unit
+        tot = (float(S.max()) + epi + float(ref['out'].abs().max())) / unit * (3 if d['epi'] in PRELU_EPIS else 1)
         assert tot < 2.0 ** 24, tot
         worst = max(worst, tot)
         if d['epi'] != EPI_LEAKY:                                         # (LEAKY: fl(0.2f pre) is one rounding of an exact pre)
@@ -597,9 +672,9 @@ def run(d, key, code, tag, x=None, images=None, stats=False, out=None, dense=Fal
               emit_stats=stats, split_k=0)
     if d['pro'] in (PRO_AFFINE, PRO_AFFINE_SWISH):
         kw.update(scale=d['sc'][sl].contiguous().cuda(), shift=d['sh'][sl].contiguous().cuda())
-    res = d['res'][sl].contiguous().cuda() if d['epi'] in (EPI_RESIDUAL, EPI_SFT, EPI_AXPY, EPI_AXPY2) else None
+    res = d['res'][sl].contiguous().cuda() if d['epi'] in (EPI_RESIDUAL, EPI_SFT, EPI_AXPY, EPI_AXPY2, EPI_RES_PRELU) else None
     ss = d['ss'][sl].contiguous().cuda() if d['epi'] in (EPI_SFT, EPI_AXPY2) else None
-    if d['epi'] in (EPI_SFT, EPI_AXPY, EPI_AXPY2):
+    if d['epi'] in (EPI_SFT, EPI_AXPY, EPI_AXPY2) + PRELU_EPIS:
         kw['sft_w'] = d['sft_w']
     if g.sliced and not dense:
         (x1, buf), (x2, buf2) = into_slice(x1, *SLICE['x']), into_slice(x2, *SLICE['x2'])
@@ -646,6 +721,8 @@ def case(name, key, code, route, form, variant=0):
 if __name__ == '__main__':
     if '--ends' in sys.argv:
         with_nchw_ends()
+    if '--prelu' in sys.argv:
+        with_prelu()
     bad = 0
     for key in CASES:
         for fam in families_of(key) + ('onehot_pixels',) + SOLO_FAMILIES:
