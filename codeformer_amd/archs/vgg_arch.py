@@ -31,7 +31,7 @@ from torch import nn
 
 from .. import ops
 from ..utils.registry import ARCH_REGISTRY
-from .arcface_arch import bn_affine, fold_conv_bn
+from .arcface_arch import _bn_deps, bn_affine, fold_conv_bn
 from .hip_module import HipModule
 
 VGG_PRETRAIN_PATH = 'experiments/pretrained_models/vgg19-dcbb9e9d.pth'
@@ -99,10 +99,6 @@ class FeaturesOnly(nn.Module):
 
     def load_state_dict(self, state_dict, strict=True):
         return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith('classifier.')}, strict=strict)
-
-
-def _bn_deps(bn):
-    return [bn.weight, bn.bias, bn.running_mean, bn.running_var]
 
 
 @ARCH_REGISTRY.register()

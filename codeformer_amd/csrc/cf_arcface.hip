@@ -1,7 +1,7 @@
 // The pieces of ResNetArcFace (basicsr/archs/arcface_arch.py) and of the identity metric that are not a convolution, for gfx950.
 // The definitions stand at "ArcFace / identity metric" in include/codeformer_hip.h.
 //
-//   prelu_maxpool2_kernel      stem: PReLU, then MaxPool2d(2, 2), channels-last, thread = one float4 of one output pixel
+//   cf_act_maxpool2_kernel<prelu_act>   stem: PReLU, then MaxPool2d(2, 2), channels-last (cf_score_parts.h)
 //   se_pool_part_kernel / se_pool_finish_kernel   squeeze: fixed-order partial sums per (image, 64 channels, 256 pixels), then one
 //                              thread per (image, channel) adds the partials in block order and divides once
 //   se_gate_kernel             excitation: Linear -> PReLU -> Linear -> sigmoid on one pooled row, one workgroup per image
@@ -13,7 +13,7 @@
 //
 // Everything here is bandwidth-bound: no MFMA.  Reductions have one fixed order that depends on the per-image shape only (no float
 // atomics), so results are bitwise repeatable and row b does not depend on the batch.
-#include "cf_common.h"
+#include "cf_score_parts.h"
 
 namespace {
 
@@ -22,32 +22,10 @@ __device__ __forceinline__ float prelu1(float x, float a) {
   return x > 0.f ? x : a * x;
 }
 
-// ---- stem ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void prelu_maxpool2_kernel(const float* __restrict__ x, float* __restrict__ out, int h, int w, int c4n, float alpha,
-                                                             long total) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int k = (int)(idx % c4n);
-  const long p = idx / c4n;
-  const int ox = (int)(p % w);
-  const long q = p / w;
-  const int oy = (int)(q % h);
-  const long b = q / h;
-  const f32x4* const xb = reinterpret_cast<const f32x4*>(x);
-  f32x4 m = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-  for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 2; ++dx) {
-      const f32x4 v = xb[(((size_t)b * 2 * h + 2 * oy + dy) * 2 * w + 2 * ox + dx) * c4n + k];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float t = prelu1(v[e], alpha);
-        if (t > m[e] || t != t) m[e] = t;  // torch's max_pool2d: a NaN wins
-      }
-    }
-  reinterpret_cast<f32x4*>(out)[idx] = m;
-}
+struct prelu_act {
+  float alpha;
+  __device__ float operator()(float x) const { return prelu1(x, alpha); }
+};
 
 // ---- squeeze and excitation -------------------------------------------------------------------------------------------------------
 constexpr int SE_PIX = 256;  // pixels per partial
@@ -195,9 +173,8 @@ __global__ __launch_bounds__(256) void fc_rows_finish_kernel(const float* __rest
 
 // ---- identity metric ------------------------------------------------------------------------------------------------------------------
 struct IdArgs {
-  const void* img;
+  cf_img_view img;
   float* out;
-  long st[4];  // element strides of (image, row, column, channel)
   int batch, h, w, dtype, bgr;
   float sy, sx;  // h / 128, w / 128: one fp32 division each per launch
 };
@@ -224,11 +201,7 @@ __device__ __forceinline__ float id_gray(const IdArgs& a, long base) {
   float v[3];
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) {
-    const long o = base + ch * a.st[3];
-    float f;
-    if (a.dtype == 0) f = (float)reinterpret_cast<const uint8_t*>(a.img)[o] / 255.0f;
-    else f = reinterpret_cast<const float*>(a.img)[o];
-    f = f * 2.0f;
+    const float f = cf_img_unit(a.img.p, a.dtype, base + ch * a.img.st[3]) * 2.0f;
     v[ch] = f - 1.0f;
   }
   const float r = a.bgr ? v[2] : v[0], g = v[1], bl = a.bgr ? v[0] : v[2];
@@ -245,9 +218,9 @@ __global__ __launch_bounds__(256) void identity_input_kernel(const IdArgs a) {
   float ly, hy, lx, hx;
   id_axis(oy, a.sy, a.h, y0, y1, ly, hy);
   id_axis(ox, a.sx, a.w, x0, x1, lx, hx);
-  const long ib = (long)b * a.st[0];
-  const float g00 = id_gray(a, ib + y0 * a.st[1] + x0 * a.st[2]), g01 = id_gray(a, ib + y0 * a.st[1] + x1 * a.st[2]);
-  const float g10 = id_gray(a, ib + y1 * a.st[1] + x0 * a.st[2]), g11 = id_gray(a, ib + y1 * a.st[1] + x1 * a.st[2]);
+  const long ib = (long)b * a.img.st[0];
+  const float g00 = id_gray(a, ib + y0 * a.img.st[1] + x0 * a.img.st[2]), g01 = id_gray(a, ib + y0 * a.img.st[1] + x1 * a.img.st[2]);
+  const float g10 = id_gray(a, ib + y1 * a.img.st[1] + x0 * a.img.st[2]), g11 = id_gray(a, ib + y1 * a.img.st[1] + x1 * a.img.st[2]);
   const float top = hx * g00 + lx * g01, bot = hx * g10 + lx * g11;
   a.out[idx] = hy * top + ly * bot;
 }
@@ -262,32 +235,21 @@ __global__ __launch_bounds__(256) void cosine_rows_kernel(const float* __restric
     xx += p * p;
     yy += q * q;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    d += __shfl_xor(d, o, 64);
-    xx += __shfl_xor(xx, o, 64);
-    yy += __shfl_xor(yy, o, 64);
-  }
+  d = cf_wave_sum(d), xx = cf_wave_sum(xx), yy = cf_wave_sum(yy);
   if (lane == 0) {
     const double den = sqrt(xx) * sqrt(yy);
     out[row] = d / (den > 1e-8 ? den : 1e-8);
   }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-constexpr long GRID_LIM = 1L << 31;
-
 }  // namespace
 
 extern "C" int cf_prelu_maxpool2(const float* x, int batch, int h, int w, int c, float alpha, float* out, cf_stream_t stream) {
   CF_REQUIRE(x && out, "cf_prelu_maxpool2: null x/out");
   CF_REQUIRE(batch > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0, "cf_prelu_maxpool2: bad dims (batch %d, output %dx%d, c %d: c %% 4 == 0)", batch, h, w, c);
-  CF_REQUIRE(aligned16(x) && aligned16(out), "cf_prelu_maxpool2: x and out must be 16-byte aligned");
-  const long total = (long)batch * h * w * (c / 4);
-  CF_REQUIRE((total + 255) / 256 < GRID_LIM, "cf_prelu_maxpool2: tensor too large");
-  hipLaunchKernelGGL(prelu_maxpool2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, out, h, w, c / 4, alpha, total);
-  CF_CHECK_LAUNCH("cf_prelu_maxpool2");
-  return CF_OK;
+  CF_REQUIRE(cf_aligned16(x) && cf_aligned16(out), "cf_prelu_maxpool2: x and out must be 16-byte aligned");
+  CF_REQUIRE(h < (1 << 30) && w < (1 << 30), "cf_prelu_maxpool2: tensor too large");
+  return cf_act_maxpool2("cf_prelu_maxpool2", x, batch, 2 * h, 2 * w, c, out, nullptr, prelu_act{alpha}, stream);  // (h, w: the output's)
 }
 
 extern "C" int cf_se_pool_parts(int hw) { return hw > 0 ? (hw + SE_PIX - 1) / SE_PIX : -1; }
@@ -295,10 +257,10 @@ extern "C" int cf_se_pool_parts(int hw) { return hw > 0 ? (hw + SE_PIX - 1) / SE
 extern "C" int cf_se_pool(const float* x, int batch, int hw, int c, float* parts, float* out, cf_stream_t stream) {
   CF_REQUIRE(x && parts && out, "cf_se_pool: null x/parts/out");
   CF_REQUIRE(batch > 0 && hw > 0 && c > 0 && c % 4 == 0, "cf_se_pool: bad dims (batch %d, hw %d, c %d: c %% 4 == 0)", batch, hw, c);
-  CF_REQUIRE(aligned16(x) && aligned16(parts), "cf_se_pool: x and parts must be 16-byte aligned");
+  CF_REQUIRE(cf_aligned16(x) && cf_aligned16(parts), "cf_se_pool: x and parts must be 16-byte aligned");
   const int ncb = (c + 63) / 64, nrb = (hw + SE_PIX - 1) / SE_PIX;
   const long blocks = (long)batch * ncb * nrb;
-  CF_REQUIRE(blocks < GRID_LIM && (long)batch * c < GRID_LIM, "cf_se_pool: tensor too large");
+  CF_REQUIRE(blocks < CF_GRID_LIM && (long)batch * c < CF_GRID_LIM, "cf_se_pool: tensor too large");
   hipLaunchKernelGGL(se_pool_part_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, parts, hw, c, ncb, nrb);
   CF_CHECK_LAUNCH("cf_se_pool");
   hipLaunchKernelGGL(se_pool_finish_kernel, dim3((unsigned)(((long)batch * c + 255) / 256)), dim3(256), 0, (hipStream_t)stream, parts, out, batch, hw, c, nrb);
@@ -319,9 +281,9 @@ extern "C" int cf_se_gate(const float* pooled, const float* w1, const float* b1,
 extern "C" int cf_se_scale_res_prelu(const float* x, const float* y, const float* res, int batch, int hw, int c, float alpha, float* out, cf_stream_t stream) {
   CF_REQUIRE(x && y && out, "cf_se_scale_res_prelu: null x/y/out");
   CF_REQUIRE(batch > 0 && hw > 0 && c > 0 && c % 4 == 0, "cf_se_scale_res_prelu: bad dims (batch %d, hw %d, c %d: c %% 4 == 0)", batch, hw, c);
-  CF_REQUIRE(aligned16(x) && aligned16(y) && aligned16(res) && aligned16(out), "cf_se_scale_res_prelu: tensors must be 16-byte aligned");
+  CF_REQUIRE(cf_aligned16(x) && cf_aligned16(y) && cf_aligned16(res) && cf_aligned16(out), "cf_se_scale_res_prelu: tensors must be 16-byte aligned");
   const long per_img = (long)hw * (c / 4), total = per_img * batch;
-  CF_REQUIRE((total + 255) / 256 < GRID_LIM, "cf_se_scale_res_prelu: tensor too large");
+  CF_REQUIRE((total + 255) / 256 < CF_GRID_LIM, "cf_se_scale_res_prelu: tensor too large");
   hipLaunchKernelGGL(se_scale_res_prelu_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, res, out, c / 4, per_img, alpha,
                      total);
   CF_CHECK_LAUNCH("cf_se_scale_res_prelu");
@@ -337,8 +299,8 @@ extern "C" int cf_fc_rows(const float* x, const float* wp, const float* bias, in
   CF_REQUIRE(x && wp && ws && out, "cf_fc_rows: null x/wp/ws/out");
   CF_REQUIRE(m >= 1 && m <= FC_ROWS, "cf_fc_rows: %d rows (1 .. %d per launch)", m, FC_ROWS);
   CF_REQUIRE(n >= 1 && n % 4 == 0 && k >= FC_KC && k % FC_KC == 0, "cf_fc_rows: n %d (%% 4 == 0), k %d (%% %d == 0)", n, k, FC_KC);
-  CF_REQUIRE(aligned16(x) && aligned16(wp), "cf_fc_rows: x and wp must be 16-byte aligned");
-  CF_REQUIRE(k / FC_KC <= 65535 && (long)m * n < GRID_LIM, "cf_fc_rows: matrix too large");
+  CF_REQUIRE(cf_aligned16(x) && cf_aligned16(wp), "cf_fc_rows: x and wp must be 16-byte aligned");
+  CF_REQUIRE(k / FC_KC <= 65535 && (long)m * n < CF_GRID_LIM, "cf_fc_rows: matrix too large");
   hipLaunchKernelGGL(fc_rows_kernel, dim3((n + 63) / 64, k / FC_KC), dim3(256), 0, (hipStream_t)stream, x, wp, ws, m, n, k);
   CF_CHECK_LAUNCH("cf_fc_rows");
   hipLaunchKernelGGL(fc_rows_finish_kernel, dim3((m * n + 256 / FC_FIN - 1) / (256 / FC_FIN)), dim3(256), 0, (hipStream_t)stream, ws, bias, out, m, n, k / FC_KC);
@@ -347,21 +309,13 @@ extern "C" int cf_fc_rows(const float* x, const float* wp, const float* bias, in
 }
 
 extern "C" int cf_identity_input(const void* img, int batch, int h, int w, const int64_t* stride, int dtype, int bgr, float* out, cf_stream_t stream) {
-  CF_REQUIRE(img && stride && out, "cf_identity_input: null img/stride/out");
+  CF_REQUIRE(out, "cf_identity_input: null out");
   CF_REQUIRE(batch > 0 && h > 0 && w > 0 && h < (1 << 24) && w < (1 << 24), "cf_identity_input: bad dims (batch %d, %dx%d)", batch, h, w);
-  CF_REQUIRE(dtype == 0 || dtype == 1, "cf_identity_input: dtype %d (0 uint8, 1 float32)", dtype);
   CF_REQUIRE(bgr == 0 || bgr == 1, "cf_identity_input: bgr %d (0 or 1)", bgr);
-  long reach = 0;
-  const int dims[4] = {batch, h, w, 3};
-  for (int i = 0; i < 4; ++i) {
-    CF_REQUIRE(stride[i] >= 0, "cf_identity_input: negative stride");
-    reach += (long)(dims[i] - 1) * stride[i];
-  }
-  CF_REQUIRE(reach < GRID_LIM, "cf_identity_input: the largest element offset reaches 2^31");
-  CF_REQUIRE((long)batch * ID_SIZE * ID_SIZE < GRID_LIM, "cf_identity_input: batch too large");
+  CF_REQUIRE((long)batch * ID_SIZE * ID_SIZE < CF_GRID_LIM, "cf_identity_input: batch too large");
   IdArgs a;
-  a.img = img, a.out = out;
-  for (int i = 0; i < 4; ++i) a.st[i] = stride[i];
+  if (int e = cf_img_view_fill("cf_identity_input", img, stride, dtype, batch, h, w, 3, a.img)) return e;
+  a.out = out;
   a.batch = batch, a.h = h, a.w = w, a.dtype = dtype, a.bgr = bgr;
   a.sy = (float)h / (float)ID_SIZE;
   a.sx = (float)w / (float)ID_SIZE;

@@ -15,7 +15,7 @@
 //
 // This file is compiled without contraction: the Y conversion has to give the host's bits (a fused multiply-add can flip one float32 ulp of
 // Y), and the SSIM map of two identical images has to be exactly 1.  The filter passes name their fused multiply-adds themselves (fma()).
-#include "cf_common.h"
+#include "cf_score_parts.h"
 
 #include <math.h>
 
@@ -32,9 +32,7 @@ static_assert(TH * TW == 512 && IH * (TW / 4) <= 256, "ssim_kernel: two outputs 
 static_assert(2 * IH * IS * 4 + 5 * IH * TW * 8 + 64 <= 65536, "ssim_kernel: static LDS");
 
 struct MetricArgs {
-  const void* a;
-  const void* b;
-  long sa[4], sb[4];  // element strides: batch, row, column, channel
+  cf_img_view a, b;
   int batch, h, w, c; // c: channels in memory (1 or 3)
   int y;              // 1: score the BT.601 Y of a BGR image (c == 3), or the float32 round trip of a grey one (c == 1)
   int planes;         // channels scored: 1 with y, else c
@@ -43,12 +41,6 @@ struct MetricArgs {
   double* parts;
   double g[TAPS];     // the normalised Gaussian window
 };
-
-template <int DT>
-__device__ __forceinline__ float load_elem(const void* p, long off) {
-  if (DT == 0) return (float)static_cast<const uint8_t*>(p)[off];
-  return static_cast<const float*>(p)[off];
-}
 
 // to_y_channel (basicsr/metrics/metric_util.py) of one BGR pixel with values in [0, 255]: every step one operation, in the host's order.
 __device__ __forceinline__ float y_of_bgr(float b, float g, float r) {
@@ -61,23 +53,9 @@ __device__ __forceinline__ float y_of_grey(float v) { return (v / 255.0f) * 255.
 // The value the metric sees at pixel `off` (an element offset that already holds batch, row and column) of plane p.
 template <int DT>
 __device__ __forceinline__ float load_plane(const void* img, long off, long sc, int c, int y, int p) {
-  if (!y) return load_elem<DT>(img, off + p * sc);
-  if (c == 3) return y_of_bgr(load_elem<DT>(img, off), load_elem<DT>(img, off + sc), load_elem<DT>(img, off + 2 * sc));
-  return y_of_grey(load_elem<DT>(img, off));
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Sum over the 256 threads of a workgroup in a fixed order; the result is valid in thread 0.
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  v = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
+  if (!y) return cf_img_elem<DT>(img, off + p * sc);
+  if (c == 3) return y_of_bgr(cf_img_elem<DT>(img, off), cf_img_elem<DT>(img, off + sc), cf_img_elem<DT>(img, off + 2 * sc));
+  return y_of_grey(cf_img_elem<DT>(img, off));
 }
 
 // ---- squared-error sum ----------------------------------------------------------------------------------------------------------------
@@ -91,14 +69,14 @@ __global__ __launch_bounds__(256) void sse_kernel(const MetricArgs m) {
   const int strips = (m.h + SSE_ROWS - 1) / SSE_ROWS;
   const int img = blockIdx.x / strips, strip = blockIdx.x - img * strips;
   const int y0 = strip * SSE_ROWS, rows = m.h - y0 < SSE_ROWS ? m.h - y0 : SSE_ROWS;
-  const long ba = img * m.sa[0], bb = img * m.sb[0];
+  const long ba = img * m.a.st[0], bb = img * m.b.st[0];
   double acc = 0.0;
   if (m.y) {
     const int items = rows * m.w;
     for (int i = threadIdx.x; i < items; i += 256) {
       const int r = i / m.w, x = i - r * m.w;
-      const float va = load_plane<DT>(m.a, ba + (y0 + r) * m.sa[1] + x * m.sa[2], m.sa[3], m.c, 1, 0);
-      const float vb = load_plane<DT>(m.b, bb + (y0 + r) * m.sb[1] + x * m.sb[2], m.sb[3], m.c, 1, 0);
+      const float va = load_plane<DT>(m.a.p, ba + (y0 + r) * m.a.st[1] + x * m.a.st[2], m.a.st[3], m.c, 1, 0);
+      const float vb = load_plane<DT>(m.b.p, bb + (y0 + r) * m.b.st[1] + x * m.b.st[2], m.b.st[3], m.c, 1, 0);
       const double d = (double)va - (double)vb;
       acc += d * d;
     }
@@ -107,11 +85,11 @@ __global__ __launch_bounds__(256) void sse_kernel(const MetricArgs m) {
     for (int i = threadIdx.x; i < items; i += 256) {
       const int r = i / groups, e0 = (i - r * groups) * G;
       const int cnt = n - e0 < G ? n - e0 : G;
-      const long ra = ba + (y0 + r) * m.sa[1], rb = bb + (y0 + r) * m.sb[1];
+      const long ra = ba + (y0 + r) * m.a.st[1], rb = bb + (y0 + r) * m.b.st[1];
       float va[G], vb[G];
       if (m.vec && cnt == G) {  // 16 bytes per image: the logical elements e0 .. e0 + G - 1 are G consecutive elements of memory
-        const cf_u32x4 qa = *reinterpret_cast<const cf_u32x4*>(static_cast<const char*>(m.a) + (ra + e0) * (DT == 0 ? 1 : 4));
-        const cf_u32x4 qb = *reinterpret_cast<const cf_u32x4*>(static_cast<const char*>(m.b) + (rb + e0) * (DT == 0 ? 1 : 4));
+        const cf_u32x4 qa = *reinterpret_cast<const cf_u32x4*>(static_cast<const char*>(m.a.p) + (ra + e0) * (DT == 0 ? 1 : 4));
+        const cf_u32x4 qb = *reinterpret_cast<const cf_u32x4*>(static_cast<const char*>(m.b.p) + (rb + e0) * (DT == 0 ? 1 : 4));
 #pragma unroll
         for (int k = 0; k < G; ++k) {
           if (DT == 0) {
@@ -129,8 +107,8 @@ __global__ __launch_bounds__(256) void sse_kernel(const MetricArgs m) {
           va[k] = vb[k] = 0.f;
           if (k < cnt) {
             const int e = e0 + k, x = e / m.c, ch = e - x * m.c;
-            va[k] = load_elem<DT>(m.a, ra + x * m.sa[2] + ch * m.sa[3]);
-            vb[k] = load_elem<DT>(m.b, rb + x * m.sb[2] + ch * m.sb[3]);
+            va[k] = cf_img_elem<DT>(m.a.p, ra + x * m.a.st[2] + ch * m.a.st[3]);
+            vb[k] = cf_img_elem<DT>(m.b.p, rb + x * m.b.st[2] + ch * m.b.st[3]);
           }
         }
       }
@@ -151,7 +129,7 @@ __global__ __launch_bounds__(256) void sse_kernel(const MetricArgs m) {
       }
     }
   }
-  acc = block_sum_f64(acc, red);
+  acc = cf_block_sum_f64(acc, red);
   if (threadIdx.x == 0) m.parts[(size_t)img * strips + strip] = acc;
 }
 
@@ -159,9 +137,7 @@ __global__ __launch_bounds__(256) void sse_kernel(const MetricArgs m) {
 __global__ __launch_bounds__(64) void sse_finalize_kernel(const double* __restrict__ parts, int strips, double count, double* __restrict__ sse,
                                                           double* __restrict__ psnr) {
   const int img = blockIdx.x;
-  double s = 0.0;
-  for (int i = threadIdx.x; i < strips; i += 64) s += parts[(size_t)img * strips + i];
-  s = wave_sum_f64(s);
+  const double s = cf_finish_sum_f64(parts + (size_t)img * strips, strips);
   if (threadIdx.x == 0) {
     sse[img] = s;
     if (psnr) {
@@ -184,7 +160,7 @@ __global__ __launch_bounds__(256) void ssim_kernel(const MetricArgs m) {
   const int p = blk % m.planes, img = blk / m.planes;
   const int ty = tile / m.tiles_x, tx = tile - ty * m.tiles_x;
   const int y0 = ty * TH, x0 = tx * TW;  // the tile's first output = its first input row and column
-  const long ba = img * m.sa[0], bb = img * m.sb[0];
+  const long ba = img * m.a.st[0], bb = img * m.b.st[0];
 
   // stage: inputs outside the image are never read; they become 0 and reach only outputs that are masked below
   for (int i = tid; i < IH * IW; i += 256) {
@@ -192,8 +168,8 @@ __global__ __launch_bounds__(256) void ssim_kernel(const MetricArgs m) {
     const int y = y0 + r, x = x0 + c;
     float va = 0.f, vb = 0.f;
     if (y < m.h && x < m.w) {
-      va = load_plane<DT>(m.a, ba + y * m.sa[1] + x * m.sa[2], m.sa[3], m.c, m.y, p);
-      vb = load_plane<DT>(m.b, bb + y * m.sb[1] + x * m.sb[2], m.sb[3], m.c, m.y, p);
+      va = load_plane<DT>(m.a.p, ba + y * m.a.st[1] + x * m.a.st[2], m.a.st[3], m.c, m.y, p);
+      vb = load_plane<DT>(m.b.p, bb + y * m.b.st[1] + x * m.b.st[2], m.b.st[3], m.c, m.y, p);
     }
     s_a[r * IS + c] = va;
     s_b[r * IS + c] = vb;
@@ -253,7 +229,7 @@ __global__ __launch_bounds__(256) void ssim_kernel(const MetricArgs m) {
     const double v = ((2 * mu1_mu2 + C1) * (2 * sigma12 + C2)) / ((mu1_sq + mu2_sq + C1) * (sigma1_sq + sigma2_sq + C2));
     if (y0 + 2 * rp + j < oh && x0 + c < ow) sum += v;
   }
-  sum = block_sum_f64(sum, red);
+  sum = cf_block_sum_f64(sum, red);
   if (tid == 0) m.parts[((size_t)img * m.planes + p) * m.tiles + tile] = sum;
 }
 
@@ -262,11 +238,7 @@ __global__ __launch_bounds__(64) void ssim_finalize_kernel(const double* __restr
                                                            double* __restrict__ ssim) {
   const int img = blockIdx.x;
   double total = 0.0;
-  for (int p = 0; p < planes; ++p) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < tiles; i += 64) s += parts[((size_t)img * planes + p) * tiles + i];
-    total += wave_sum_f64(s) / count;
-  }
+  for (int p = 0; p < planes; ++p) total += cf_finish_sum_f64(parts + ((size_t)img * planes + p) * tiles, tiles) / count;
   if (threadIdx.x == 0) ssim[img] = total / (double)planes;
 }
 
@@ -278,22 +250,14 @@ inline int ssim_tiles_y(int h) { return (h - HALO + TH - 1) / TH; }
 // Checks shared by the entry points; fills the arguments that do not depend on the kernel.
 static int metric_args(const char* who, const void* a, const void* b, int batch, int h, int w, int channels, const int64_t* stride_a,
                        const int64_t* stride_b, int dtype, int y_channel, double* parts, const void* out, MetricArgs& m) {
-  CF_REQUIRE(a && b && stride_a && stride_b && parts && out, "%s: null a/b/stride_a/stride_b/parts/output", who);
+  CF_REQUIRE(parts && out, "%s: null parts/output", who);
   CF_REQUIRE(channels == 1 || channels == 3, "%s: channels %d (1 or 3)", who, channels);
   CF_REQUIRE(batch > 0 && h > 0 && w > 0, "%s: bad dims (batch %d, %dx%d)", who, batch, h, w);
-  CF_REQUIRE(dtype == 0 || dtype == 1, "%s: dtype %d (0 uint8, 1 float32)", who, dtype);
   CF_REQUIRE(y_channel == 0 || y_channel == 1, "%s: y_channel %d (0 or 1)", who, y_channel);
-  const long dims[4] = {batch, h, w, channels}, lim = 1L << 31;
-  for (const int64_t* s : {stride_a, stride_b}) {
-    long top = 0;  // the largest element offset of the tensor
-    for (int i = 0; i < 4; ++i) {
-      CF_REQUIRE(s[i] >= 0 && s[i] < lim, "%s: stride %ld (0 .. 2^31 - 1 elements)", who, (long)s[i]);
-      top += (dims[i] - 1) * s[i];
-      CF_REQUIRE(top < lim, "%s: the largest element offset reaches 2^31", who);
-    }
-  }
-  m.a = a, m.b = b;
-  for (int i = 0; i < 4; ++i) m.sa[i] = stride_a[i], m.sb[i] = stride_b[i];
+  if (int e = cf_img_view_fill(who, a, stride_a, dtype, batch, h, w, channels, m.a)) return e;
+  if (int e = cf_img_view_fill(who, b, stride_b, dtype, batch, h, w, channels, m.b)) return e;
+  for (int i = 0; i < 4; ++i)  // (an axis of one element adds nothing to the largest offset, whatever its stride)
+    CF_REQUIRE(stride_a[i] < CF_GRID_LIM && stride_b[i] < CF_GRID_LIM, "%s: stride above 2^31 - 1 elements", who);
   m.batch = batch, m.h = h, m.w = w, m.c = channels;
   m.y = y_channel;
   m.planes = y_channel ? 1 : channels;
@@ -310,7 +274,7 @@ extern "C" int cf_metric_parts(int h, int w, int channels) {
   const long strips = (h + SSE_ROWS - 1) / SSE_ROWS;
   const long tiles = h > HALO && w > HALO ? (long)channels * ssim_tiles_x(w) * ssim_tiles_y(h) : 0;
   const long n = strips > tiles ? strips : tiles;
-  CF_REQUIRE(n < (1L << 31), "cf_metric_parts: image too large (%dx%d)", h, w);
+  CF_REQUIRE(n < CF_GRID_LIM, "cf_metric_parts: image too large (%dx%d)", h, w);
   return (int)n;
 }
 
@@ -319,14 +283,13 @@ extern "C" int cf_psnr(const void* a, const void* b, int batch, int h, int w, in
   MetricArgs m;
   if (int e = metric_args("cf_psnr", a, b, batch, h, w, channels, stride_a, stride_b, dtype, y_channel, parts, sse, m)) return e;
   const long strips = (h + SSE_ROWS - 1) / SSE_ROWS;
-  CF_REQUIRE(strips * batch < (1L << 31), "cf_psnr: too many workgroups");
+  CF_REQUIRE(strips * batch < CF_GRID_LIM, "cf_psnr: too many workgroups");
   if (!y_channel) {
     const long es = dtype == 0 ? 1 : 4;
     bool ok = true;
     for (int i = 0; i < 2; ++i) {
-      const long* s = i ? m.sb : m.sa;
-      ok = ok && (channels == 1 || s[3] == 1) && s[2] == channels && (s[0] * es) % 16 == 0 && (s[1] * es) % 16 == 0 &&
-           ((uintptr_t)(i ? b : a) & 15) == 0;
+      const long* s = i ? m.b.st : m.a.st;
+      ok = ok && (channels == 1 || s[3] == 1) && s[2] == channels && (s[0] * es) % 16 == 0 && (s[1] * es) % 16 == 0 && cf_aligned16(i ? b : a);
     }
     m.vec = ok;
   }
@@ -348,7 +311,7 @@ extern "C" int cf_ssim(const void* a, const void* b, int batch, int h, int w, in
   m.tiles_x = ssim_tiles_x(w);
   m.tiles = m.tiles_x * ssim_tiles_y(h);
   const long blocks = (long)m.tiles * m.planes * batch;
-  CF_REQUIRE(blocks < (1L << 31), "cf_ssim: too many workgroups");
+  CF_REQUIRE(blocks < CF_GRID_LIM, "cf_ssim: too many workgroups");
   if (dtype == 0) hipLaunchKernelGGL(ssim_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m);
   else hipLaunchKernelGGL(ssim_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, m);
   CF_CHECK_LAUNCH("cf_ssim");

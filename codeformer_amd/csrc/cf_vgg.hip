@@ -3,27 +3,27 @@
 //
 //   vgg_input_kernel        image (uint8 / float32, any strides, BGR or RGB) -> normalised dense NHWC with zero-padded channels, thread = pixel
 //   relu_kernel             x > 0 ? x : +0, float4, in place or not
-//   relu_maxpool2_kernel    ReLU, then MaxPool2d(2, 2) with floor; thread = one float4 of one 2x2 cell; optionally the full-size ReLU tensor too
+//   cf_act_maxpool2_kernel<relu_act>   ReLU, then MaxPool2d(2, 2) with floor; optionally the full-size ReLU tensor too (cf_score_parts.h)
 //   gram_kernel / gram_finish_kernel   F^T F per image on v_mfma_f32_32x32x2_f32: a workgroup owns one 64 x 64 tile (j0 >= i0) of one chunk of
 //                           1024 pixels, four waves = 2 x 2 sub-tiles of 32 x 32; chunk products in a workspace, added in chunk order
-//   feat_dist_kernel / feat_dist_finish_kernel   per image sum |a - b| and sum (a - b)^2 in fp64, one partial per chunk of 16384 elements
-//   lpips_head_kernel / lpips_head_finish_kernel   the LPIPS layer term: channel-normalise both features per pixel, weighted squared difference, pixel mean
+//   feat_dist_kernel        per image sum |a - b| and sum (a - b)^2 in fp64, one partial per chunk of 16384 elements
+//   lpips_head_kernel       the LPIPS layer term: channel-normalise both features per pixel, weighted squared difference, pixel mean
+//   score_finish_kernel     one wave per image adds its partials of either in the finish order
 //
 // No float atomics; every order of summation is a function of the per-image shape only.
-#include "cf_common.h"
+#include "cf_score_parts.h"
 
 namespace {
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-constexpr long GRID_LIM = 1L << 31;
-
 __device__ __forceinline__ float relu1(float x) { return x > 0.f ? x : (x != x ? x : 0.f); }
+struct relu_act {
+  __device__ float operator()(float x) const { return relu1(x); }
+};
 
 // ---- input ----------------------------------------------------------------------------------------------------------------------------
 struct VggInArgs {
-  const void* img;
+  cf_img_view img;
   float* out;
-  long st[4];  // element strides of (image, row, column, channel)
   long pixels;
   int h, w, dtype, bgr, range_norm, use_norm, c4n;
   float mean[3], std[3];
@@ -37,14 +37,11 @@ __global__ __launch_bounds__(256) void vgg_input_kernel(const VggInArgs a) {
   const long q = idx / a.w;
   const int y = (int)(q % a.h);
   const long b = q / a.h;
-  const long base = b * a.st[0] + y * a.st[1] + x * a.st[2];
+  const long base = b * a.img.st[0] + y * a.img.st[1] + x * a.img.st[2];
   float v[4];
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) {
-    const long o = base + (a.bgr ? 2 - ch : ch) * a.st[3];
-    float f;
-    if (a.dtype == 0) f = (float)reinterpret_cast<const uint8_t*>(a.img)[o] / 255.0f;
-    else f = reinterpret_cast<const float*>(a.img)[o];
+    float f = cf_img_unit(a.img.p, a.dtype, base + (a.bgr ? 2 - ch : ch) * a.img.st[3]);
     if (a.range_norm) {
       f = f + 1.0f;
       f = f / 2.0f;
@@ -60,47 +57,13 @@ __global__ __launch_bounds__(256) void vgg_input_kernel(const VggInArgs a) {
   for (int k = 1; k < a.c4n; ++k) o4[k] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-// ---- ReLU, ReLU + max-pool --------------------------------------------------------------------------------------------------------------
+// ---- ReLU --------------------------------------------------------------------------------------------------------------------------------
 // x and out are not __restrict__: cf_relu allows out == x (every element is read and written by the same thread)
 __global__ __launch_bounds__(256) void relu_kernel(const float* x, float* out, long n4) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= n4) return;
   const f32x4 v = reinterpret_cast<const f32x4*>(x)[idx];
   reinterpret_cast<f32x4*>(out)[idx] = f32x4{relu1(v[0]), relu1(v[1]), relu1(v[2]), relu1(v[3])};
-}
-
-// cells: ceil(h / 2) x ceil(w / 2) windows; a window that hangs over the last row / column gives no pooled output (floor) but its
-// elements still reach `full`.  x and full are not __restrict__: they may be the same tensor (each element belongs to one thread).
-__global__ __launch_bounds__(256) void relu_maxpool2_kernel(const float* x, float* __restrict__ out, float* full, int h, int w, int c4n, long total) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int ch = (h + 1) >> 1, cw = (w + 1) >> 1, oh = h >> 1, ow = w >> 1;
-  const int k = (int)(idx % c4n);
-  const long p = idx / c4n;
-  const int cx = (int)(p % cw);
-  const long q = p / cw;
-  const int cy = (int)(q % ch);
-  const long b = q / ch;
-  const bool pooled = cy < oh && cx < ow;
-  if (!pooled && !full) return;
-  f32x4 m = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-  for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 2; ++dx) {
-      const int yy = 2 * cy + dy, xx = 2 * cx + dx;
-      if (yy >= h || xx >= w) continue;
-      const size_t o = (((size_t)b * h + yy) * w + xx) * c4n + k;
-      const f32x4 v = reinterpret_cast<const f32x4*>(x)[o];
-      f32x4 t;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        t[e] = relu1(v[e]);
-        if (t[e] > m[e] || t[e] != t[e]) m[e] = t[e];  // torch's max_pool2d: a NaN wins
-      }
-      if (full) reinterpret_cast<f32x4*>(full)[o] = t;
-    }
-  if (pooled) reinterpret_cast<f32x4*>(out)[(((size_t)b * oh + cy) * ow + cx) * c4n + k] = m;
 }
 
 // ---- Gram matrix ------------------------------------------------------------------------------------------------------------------------
@@ -193,12 +156,6 @@ __global__ __launch_bounds__(256) void gram_finish_kernel(const float* __restric
 }
 
 // ---- feature distances ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // A chunk is groups of 4 elements; group g belongs to thread g % 256, which adds its groups in ascending order and the elements of a
 // group in ascending order.  VEC: 16-byte loads (n % 4 == 0, aligned pointers) -- the same elements in the same order as the scalar form.
 template <bool VEC>
@@ -228,23 +185,19 @@ __global__ __launch_bounds__(256) void feat_dist_kernel(const float* __restrict_
       s2 += dd * dd;
     }
   }
-  s1 = wave_sum_f64(s1);
-  s2 = wave_sum_f64(s2);
-  if ((tid & 63) == 0) red[0][tid >> 6] = s1, red[1][tid >> 6] = s2;
-  __syncthreads();
-  if (tid < 2) parts[((size_t)img * nparts + chunk) * 2 + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+  s1 = cf_block_sum_f64(s1, red[0]);
+  s2 = cf_block_sum_f64(s2, red[1]);
+  if (tid == 0) parts[((size_t)img * nparts + chunk) * 2] = s1, parts[((size_t)img * nparts + chunk) * 2 + 1] = s2;
 }
 
-__global__ __launch_bounds__(64) void feat_dist_finish_kernel(const double* __restrict__ parts, int nparts, double* __restrict__ out) {
-  const int img = blockIdx.x;
-  double s1 = 0.0, s2 = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 64) {
-    s1 += parts[((size_t)img * nparts + i) * 2];
-    s2 += parts[((size_t)img * nparts + i) * 2 + 1];
-  }
-  s1 = wave_sum_f64(s1);
-  s2 = wave_sum_f64(s2);
-  if (threadIdx.x == 0) out[(size_t)img * 2] = s1, out[(size_t)img * 2 + 1] = s2;
+// out[img][j] = (the image's partials parts[img][..][j] in the finish order) / count, j < NV; a count of 1 leaves the sum as it is
+template <int NV>
+__global__ __launch_bounds__(64) void score_finish_kernel(const double* __restrict__ parts, int nparts, double count, double* __restrict__ out) {
+  const size_t img = blockIdx.x;
+  double s[NV];
+  cf_finish_sum_f64(parts + img * nparts * NV, nparts, s);
+  if (threadIdx.x == 0)
+    for (int j = 0; j < NV; ++j) out[img * NV + j] = s[j] / count;
 }
 
 // ---- LPIPS head ---------------------------------------------------------------------------------------------------------------------------
@@ -295,42 +248,25 @@ __global__ __launch_bounds__(256) void lpips_head_kernel(const float* __restrict
     d = cf_wave_sum(d);
     acc += (double)d;
   }
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (tid == 0) parts[(size_t)img * nparts + chunk] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-__global__ __launch_bounds__(64) void lpips_head_finish_kernel(const double* __restrict__ parts, int nparts, double count, double* __restrict__ out) {
-  const int img = blockIdx.x;
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 64) s += parts[(size_t)img * nparts + i];
-  s = wave_sum_f64(s);
-  if (threadIdx.x == 0) out[img] = s / count;
+  acc = cf_waves_sum_f64(acc, red);  // (every lane of a wave holds the wave's sum already)
+  if (tid == 0) parts[(size_t)img * nparts + chunk] = acc;
 }
 
 }  // namespace
 
 extern "C" int cf_vgg_input(const void* img, int batch, int h, int w, const int64_t* stride, int dtype, int bgr, int range_norm, int use_norm,
                             const float* mean, const float* std, int c_pad, float* out, cf_stream_t stream) {
-  CF_REQUIRE(img && stride && out, "cf_vgg_input: null img/stride/out");
+  CF_REQUIRE(out, "cf_vgg_input: null out");
   CF_REQUIRE(batch > 0 && h > 0 && w > 0 && h < (1 << 24) && w < (1 << 24), "cf_vgg_input: bad dims (batch %d, %dx%d)", batch, h, w);
-  CF_REQUIRE(dtype == 0 || dtype == 1, "cf_vgg_input: dtype %d (0 uint8, 1 float32)", dtype);
   CF_REQUIRE((bgr == 0 || bgr == 1) && (range_norm == 0 || range_norm == 1) && (use_norm == 0 || use_norm == 1), "cf_vgg_input: flags must be 0 or 1");
   CF_REQUIRE(!use_norm || (mean && std), "cf_vgg_input: use_norm needs mean and std");
   CF_REQUIRE(c_pad >= 4 && c_pad <= 64 && c_pad % 4 == 0, "cf_vgg_input: c_pad %d (4 .. 64, %% 4 == 0)", c_pad);
-  CF_REQUIRE(aligned16(out), "cf_vgg_input: out must be 16-byte aligned");
-  long reach = 0;
-  const int dims[4] = {batch, h, w, 3};
-  for (int i = 0; i < 4; ++i) {
-    CF_REQUIRE(stride[i] >= 0, "cf_vgg_input: negative stride");
-    reach += (long)(dims[i] - 1) * stride[i];
-  }
-  CF_REQUIRE(reach < GRID_LIM, "cf_vgg_input: the largest element offset reaches 2^31");
+  CF_REQUIRE(cf_aligned16(out), "cf_vgg_input: out must be 16-byte aligned");
   const long pixels = (long)batch * h * w;
-  CF_REQUIRE((pixels + 255) / 256 < GRID_LIM, "cf_vgg_input: batch too large");
+  CF_REQUIRE((pixels + 255) / 256 < CF_GRID_LIM, "cf_vgg_input: batch too large");
   VggInArgs a;
-  a.img = img, a.out = out;
-  for (int i = 0; i < 4; ++i) a.st[i] = stride[i];
+  if (int e = cf_img_view_fill("cf_vgg_input", img, stride, dtype, batch, h, w, 3, a.img)) return e;
+  a.out = out;
   a.pixels = pixels, a.h = h, a.w = w, a.dtype = dtype, a.bgr = bgr, a.range_norm = range_norm, a.use_norm = use_norm, a.c4n = c_pad / 4;
   for (int i = 0; i < 3; ++i) a.mean[i] = use_norm ? mean[i] : 0.f, a.std[i] = use_norm ? std[i] : 1.f;
   hipLaunchKernelGGL(vgg_input_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
@@ -341,8 +277,8 @@ extern "C" int cf_vgg_input(const void* img, int batch, int h, int w, const int6
 extern "C" int cf_relu(const float* x, int64_t n, float* out, cf_stream_t stream) {
   CF_REQUIRE(x && out, "cf_relu: null x/out");
   CF_REQUIRE(n > 0 && n % 4 == 0, "cf_relu: n %lld (> 0, %% 4 == 0)", (long long)n);
-  CF_REQUIRE(aligned16(x) && aligned16(out), "cf_relu: x and out must be 16-byte aligned");
-  CF_REQUIRE((n / 4 + 255) / 256 < GRID_LIM, "cf_relu: tensor too large");
+  CF_REQUIRE(cf_aligned16(x) && cf_aligned16(out), "cf_relu: x and out must be 16-byte aligned");
+  CF_REQUIRE((n / 4 + 255) / 256 < CF_GRID_LIM, "cf_relu: tensor too large");
   hipLaunchKernelGGL(relu_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, out, (long)(n / 4));
   CF_CHECK_LAUNCH("cf_relu");
   return CF_OK;
@@ -351,13 +287,9 @@ extern "C" int cf_relu(const float* x, int64_t n, float* out, cf_stream_t stream
 extern "C" int cf_relu_maxpool2(const float* x, int batch, int h, int w, int c, float* out, float* full, cf_stream_t stream) {
   CF_REQUIRE(x && out, "cf_relu_maxpool2: null x/out");
   CF_REQUIRE(batch > 0 && h >= 2 && w >= 2 && c > 0 && c % 4 == 0, "cf_relu_maxpool2: bad dims (batch %d, input %dx%d >= 2x2, c %d: c %% 4 == 0)", batch, h, w, c);
-  CF_REQUIRE(aligned16(x) && aligned16(out) && aligned16(full), "cf_relu_maxpool2: tensors must be 16-byte aligned");
+  CF_REQUIRE(cf_aligned16(x) && cf_aligned16(out) && cf_aligned16(full), "cf_relu_maxpool2: tensors must be 16-byte aligned");
   CF_REQUIRE(out != x && out != full, "cf_relu_maxpool2: out must not alias x or full");
-  const long total = (long)batch * ((h + 1) / 2) * ((w + 1) / 2) * (c / 4);
-  CF_REQUIRE((total + 255) / 256 < GRID_LIM, "cf_relu_maxpool2: tensor too large");
-  hipLaunchKernelGGL(relu_maxpool2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, out, full, h, w, c / 4, total);
-  CF_CHECK_LAUNCH("cf_relu_maxpool2");
-  return CF_OK;
+  return cf_act_maxpool2("cf_relu_maxpool2", x, batch, h, w, c, out, full, relu_act{}, stream);
 }
 
 static bool gram_dims_ok(int batch, int hw, int c) { return batch > 0 && batch <= 65535 && hw > 0 && c > 0 && c % GR_T == 0 && c <= GR_MAXC; }
@@ -370,7 +302,7 @@ extern "C" int64_t cf_gram_workspace_elems(int batch, int hw, int c) {
 extern "C" int cf_gram(const float* f, int batch, int hw, int c, float* ws, float* g, cf_stream_t stream) {
   CF_REQUIRE(f && ws && g, "cf_gram: null f/ws/g");
   CF_REQUIRE(gram_dims_ok(batch, hw, c), "cf_gram: bad dims (batch %d <= 65535, hw %d, c %d: c %% %d == 0, c <= %d)", batch, hw, c, GR_T, GR_MAXC);
-  CF_REQUIRE(aligned16(f), "cf_gram: f must be 16-byte aligned");
+  CF_REQUIRE(cf_aligned16(f), "cf_gram: f must be 16-byte aligned");
   const int nchunks = (hw + CF_GRAM_CHUNK - 1) / CF_GRAM_CHUNK, T = c / GR_T;
   CF_REQUIRE(nchunks <= 65535, "cf_gram: hw %d is more than 65535 chunks", hw);
   const long total = (long)batch * c * c;
@@ -382,17 +314,17 @@ extern "C" int cf_gram(const float* f, int batch, int hw, int c, float* ws, floa
   return CF_OK;
 }
 
-extern "C" int cf_feat_dist_parts(int64_t n) { return n > 0 && (n + CF_FEAT_CHUNK - 1) / CF_FEAT_CHUNK < GRID_LIM ? (int)((n + CF_FEAT_CHUNK - 1) / CF_FEAT_CHUNK) : -1; }
+extern "C" int cf_feat_dist_parts(int64_t n) { return n > 0 && (n + CF_FEAT_CHUNK - 1) / CF_FEAT_CHUNK < CF_GRID_LIM ? (int)((n + CF_FEAT_CHUNK - 1) / CF_FEAT_CHUNK) : -1; }
 
 extern "C" int cf_feat_dist(const float* a, const float* b, int batch, int64_t n, double* parts, double* out, cf_stream_t stream) {
   CF_REQUIRE(a && b && parts && out, "cf_feat_dist: null a/b/parts/out");
   const int nparts = cf_feat_dist_parts(n);
   CF_REQUIRE(batch > 0 && batch <= 65535 && nparts > 0, "cf_feat_dist: bad dims (batch %d <= 65535, n %lld)", batch, (long long)n);
-  const bool vec = n % 4 == 0 && aligned16(a) && aligned16(b);
+  const bool vec = n % 4 == 0 && cf_aligned16(a) && cf_aligned16(b);
   if (vec) hipLaunchKernelGGL(feat_dist_kernel<true>, dim3(nparts, batch), dim3(256), 0, (hipStream_t)stream, a, b, parts, (long)n, nparts);
   else hipLaunchKernelGGL(feat_dist_kernel<false>, dim3(nparts, batch), dim3(256), 0, (hipStream_t)stream, a, b, parts, (long)n, nparts);
   CF_CHECK_LAUNCH("cf_feat_dist");
-  hipLaunchKernelGGL(feat_dist_finish_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, parts, nparts, out);
+  hipLaunchKernelGGL(score_finish_kernel<2>, dim3(batch), dim3(64), 0, (hipStream_t)stream, parts, nparts, 1.0, out);
   CF_CHECK_LAUNCH("cf_feat_dist(finish)");
   return CF_OK;
 }
@@ -403,11 +335,11 @@ extern "C" int cf_lpips_head(const float* a, const float* b, const float* lin, i
   CF_REQUIRE(a && b && lin && parts && out, "cf_lpips_head: null argument");
   CF_REQUIRE(batch > 0 && batch <= 65535 && hw > 0 && c > 0 && c % 4 == 0 && c <= 512, "cf_lpips_head: bad dims (batch %d <= 65535, hw %d, c %d: c %% 4 == 0, c <= 512)",
              batch, hw, c);
-  CF_REQUIRE(aligned16(a) && aligned16(b) && aligned16(lin), "cf_lpips_head: a, b and lin must be 16-byte aligned");
+  CF_REQUIRE(cf_aligned16(a) && cf_aligned16(b) && cf_aligned16(lin), "cf_lpips_head: a, b and lin must be 16-byte aligned");
   const int nparts = cf_lpips_parts(hw);
   hipLaunchKernelGGL(lpips_head_kernel, dim3(nparts, batch), dim3(256), 0, (hipStream_t)stream, a, b, lin, parts, hw, c, nparts);
   CF_CHECK_LAUNCH("cf_lpips_head");
-  hipLaunchKernelGGL(lpips_head_finish_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, parts, nparts, (double)hw, out);
+  hipLaunchKernelGGL(score_finish_kernel<1>, dim3(batch), dim3(64), 0, (hipStream_t)stream, parts, nparts, (double)hw, out);
   CF_CHECK_LAUNCH("cf_lpips_head(finish)");
   return CF_OK;
 }

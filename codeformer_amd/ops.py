@@ -1449,6 +1449,16 @@ def scale_clear_border_(x, border, scale):
 METRIC_DTYPES = {torch.uint8: 0, torch.float32: 1}
 
 
+def _image_view(t, what, channels):
+    """The check of a strided (B,H,W,C) image VIEW (cf_img_view in csrc/cf_score_parts.h): uint8 or float32, C one of `channels`, no empty
+    dimension, non-negative strides, largest element offset below 2^31.  Returns (its element strides as ctypes, its dtype code)."""
+    if t.dim() != 4 or t.shape[3] not in channels or min(t.shape) < 1 or t.dtype not in METRIC_DTYPES:
+        raise ValueError(f'{what}: a uint8 or float32 (B,H,W,C) view with C in {channels} and no empty dimension is needed, got {t.dtype} {tuple(t.shape)}')
+    if min(t.stride()) < 0 or sum((n - 1) * s for n, s in zip(t.shape, t.stride())) >= 1 << 31:
+        raise ValueError(f'{what}: strides must be non-negative and the largest element offset below 2^31')
+    return (ctypes.c_int64 * 4)(*t.stride()), METRIC_DTYPES[t.dtype]
+
+
 def _metric_call(a, b, y_channel, ssim_):
     """The checks and scratch shared by psnr / ssim.  a, b: (B,H,W,C) VIEWS (any strides: a crop, a permuted CHW tensor, a slice)."""
     if not (a.is_cuda and b.is_cuda):
@@ -1459,22 +1469,17 @@ def _metric_call(a, b, y_channel, ssim_):
         raise ValueError(f'metrics: two (B,H,W,C) views of one shape are needed, got {tuple(a.shape)} and {tuple(b.shape)}')
     if a.dtype not in METRIC_DTYPES or b.dtype != a.dtype:
         raise TypeError(f'metrics: both images must be uint8 or both float32, got {a.dtype} and {b.dtype}')
+    (sa, dt), (sb, _) = (_image_view(t, 'metrics', (1, 3)) for t in (a, b))
     B, H, W, C = a.shape
-    if C not in (1, 3) or min(B, H, W) < 1:
-        raise ValueError(f'metrics: shape {tuple(a.shape)} (B,H,W,C) needs C in (1, 3) and no empty dimension')
     if ssim_ and (H < 11 or W < 11):
         raise ValueError(f'ssim: the image ({H}x{W}) is smaller than the 11x11 window')
-    for t in (a, b):
-        if sum((n - 1) * s for n, s in zip(t.shape, t.stride())) >= 1 << 31:
-            raise ValueError('metrics: the largest element offset of an image reaches 2^31')
     lib = L.ensure_device(a.device)
     planes = 1 if y_channel else C
     nparts = lib.cf_metric_parts(H, W, planes)
     if nparts < 0:
         raise RuntimeError(f'cf_metric_parts failed: {L.last_error()}')
     parts = torch.empty(B * nparts, dtype=torch.float64, device=a.device)
-    strides = [(ctypes.c_int64 * 4)(*t.stride()) for t in (a, b)]
-    return lib, parts, strides, METRIC_DTYPES[a.dtype]
+    return lib, parts, (sa, sb), dt
 
 
 def psnr(a, b, y_channel=False):
@@ -1579,16 +1584,12 @@ def fc_rows(x, wp, bias=None):
 
 def identity_input(view, bgr):
     """(B,H,W,3) VIEW (any non-negative strides), uint8 or float32 in [0, 1] -> (B,1,128,128) float32: RGB in [-1, 1], gray, bilinear resize."""
-    if view.dim() != 4 or view.shape[3] != 3 or min(view.shape) < 1 or view.dtype not in METRIC_DTYPES:
-        raise ValueError(f'identity_input: a uint8 or float32 (B,H,W,3) view is needed, got {view.dtype} {tuple(view.shape)}')
-    if min(view.stride()) < 0 or sum((n - 1) * s for n, s in zip(view.shape, view.stride())) >= 1 << 31:
-        raise ValueError('identity_input: strides must be non-negative and the largest element offset below 2^31')
+    st, dt = _image_view(view, 'identity_input', (3,))
     lib = L.ensure_device(view.device)
     B, H, W, _ = view.shape
     with torch.cuda.device(view.device):
         out = torch.empty((B, 1, 128, 128), dtype=torch.float32, device=view.device)
-        L.check(lib.cf_identity_input(view.data_ptr(), B, H, W, (ctypes.c_int64 * 4)(*view.stride()), METRIC_DTYPES[view.dtype], int(bool(bgr)),
-                                      L.ptr(out), L.stream_ptr()), 'cf_identity_input')
+        L.check(lib.cf_identity_input(view.data_ptr(), B, H, W, st, dt, int(bool(bgr)), L.ptr(out), L.stream_ptr()), 'cf_identity_input')
     return out
 
 
@@ -1613,10 +1614,7 @@ def vgg_input(view, bgr, range_norm=False, mean=None, std=None, c_pad=VGG_IN_CPA
     """(B,H,W,3) VIEW (any non-negative strides), uint8 (v / 255) or float32 -> dense (B,H,W,c_pad) float32, channels R, G, B then zeros:
     (x + 1) / 2 with range_norm, then (x - mean[c]) / std[c] when mean / std (three Python floats each) are given.  out: a dense
     destination (a batch slice of a larger buffer)."""
-    if view.dim() != 4 or view.shape[3] != 3 or min(view.shape) < 1 or view.dtype not in METRIC_DTYPES:
-        raise ValueError(f'vgg_input: a uint8 or float32 (B,H,W,3) view is needed, got {view.dtype} {tuple(view.shape)}')
-    if min(view.stride()) < 0 or sum((n - 1) * s for n, s in zip(view.shape, view.stride())) >= 1 << 31:
-        raise ValueError('vgg_input: strides must be non-negative and the largest element offset below 2^31')
+    st, dt = _image_view(view, 'vgg_input', (3,))
     if (mean is None) != (std is None) or (mean is not None and (len(mean) != 3 or len(std) != 3)):
         raise ValueError('vgg_input: mean and std are three floats each, or both None')
     if c_pad < 4 or c_pad > 64 or c_pad % 4:
@@ -1631,8 +1629,8 @@ def vgg_input(view, bgr, range_norm=False, mean=None, std=None, c_pad=VGG_IN_CPA
     with torch.cuda.device(view.device):
         if out is None:
             out = torch.empty((B, H, W, c_pad), dtype=torch.float32, device=view.device)
-        L.check(lib.cf_vgg_input(view.data_ptr(), B, H, W, (ctypes.c_int64 * 4)(*view.stride()), METRIC_DTYPES[view.dtype], int(bool(bgr)),
-                                 int(bool(range_norm)), int(mean is not None), None if mean is None else f3(*mean), None if std is None else f3(*std),
+        L.check(lib.cf_vgg_input(view.data_ptr(), B, H, W, st, dt, int(bool(bgr)), int(bool(range_norm)), int(mean is not None),
+                                 None if mean is None else f3(*mean), None if std is None else f3(*std),
                                  int(c_pad), L.ptr(out), L.stream_ptr()), 'cf_vgg_input')
     return out
 
@@ -1666,14 +1664,19 @@ def relu_maxpool2(x, full=False):
     return (out, fl) if full else out
 
 
+def _features(f, what):
+    """(B,H,W,C) or (B,HW,C) dense float32 features -> (B, HW, C)."""
+    _f32(f)
+    if f.dim() not in (3, 4) or not f.is_contiguous() or min(f.shape) < 1:
+        raise ValueError(f'{what}: expected dense (B,H,W,C) or (B,HW,C) features, got {tuple(f.shape)}')
+    B, C = f.shape[0], f.shape[-1]
+    return B, f.numel() // (B * C), C
+
+
 def gram(f):
     """(B,H,W,C) or (B,HW,C) dense float32 features -> (B,C,C): F^T F / (float)(C * HW) per image on the fp32 MFMA, C % 64 == 0, C <= 512.
     Bitwise symmetric, bitwise repeatable, image b bitwise the call on it alone."""
-    _f32(f)
-    if f.dim() not in (3, 4) or not f.is_contiguous() or min(f.shape) < 1:
-        raise ValueError(f'gram: expected dense (B,H,W,C) or (B,HW,C) features, got {tuple(f.shape)}')
-    B, C = f.shape[0], f.shape[-1]
-    hw = f.numel() // (B * C)
+    B, hw, C = _features(f, 'gram')
     if C % 64 or C > 512 or B > 65535:
         raise ValueError(f'gram: C % 64 == 0, C <= 512 and B <= 65535, got B {B}, C {C}')
     lib = L.load()
@@ -1709,11 +1712,10 @@ def feat_dist(a, b):
 def lpips_head(fa, fb, lin):
     """(B,) float64: one layer of the LPIPS distance of dense channels-last float32 features fa, fb (B,H,W,C) or (B,HW,C), C % 4 == 0, C <= 512,
     under the non-negative channel weights lin (C,): the pixel mean of sum_c lin[c] (fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10))^2."""
-    _f32(fa), _f32(fb), _f32(lin)
-    if tuple(fa.shape) != tuple(fb.shape) or fa.dim() not in (3, 4) or fa.device != fb.device or not (fa.is_contiguous() and fb.is_contiguous()) or fa.numel() == 0:
-        raise ValueError(f'lpips_head: two dense feature tensors of one shape on one device, got {tuple(fa.shape)} and {tuple(fb.shape)}')
-    B, C = fa.shape[0], fa.shape[-1]
-    hw = fa.numel() // (B * C)
+    _f32(lin)
+    (B, hw, C), _ = _features(fa, 'lpips_head'), _features(fb, 'lpips_head')
+    if tuple(fa.shape) != tuple(fb.shape) or fa.device != fb.device:
+        raise ValueError(f'lpips_head: two feature tensors of one shape on one device, got {tuple(fa.shape)} and {tuple(fb.shape)}')
     if C % 4 or C > 512 or B > 65535 or tuple(lin.shape) != (C,) or lin.device != fa.device or not lin.is_contiguous():
         raise ValueError(f'lpips_head: C % 4 == 0, C <= 512, B <= 65535 and lin of shape ({C},) on {fa.device}, got B {B}, C {C}, lin {tuple(lin.shape)}')
     lib = L.load()

@@ -30,6 +30,7 @@ GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'arcface_ref.npz')
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from oracle.ref_loader import REF  # noqa: E402  (where the reference tree lies when it is present)
+from _tools import rel_err  # noqa: E402,F401  (beside this file; R.rel_err for the tests and tools)
 
 CASES = {
     'r18': dict(layers=[2, 2, 2, 2], use_se=False, batch=3, seed=101),
@@ -164,12 +165,6 @@ def host_id():
     """The torch version the bitwise host checks are keyed on.  (Thread count does not matter: 1, 4, 8, 16 give the same bits.  The CPU
     model does -- see test_forward_host_against_reference.)"""
     return torch.__version__
-
-
-def rel_err(x, ref):
-    """max|x - ref| / max|ref| in float64."""
-    x, ref = np.asarray(x, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    return float(np.abs(x - ref).max() / np.abs(ref).max())
 
 
 def cosines(e):

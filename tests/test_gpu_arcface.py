@@ -44,9 +44,9 @@ import torch
 from torch.nn import functional as F
 
 import arcface_ref as R
+from _tools import _bits, _np, _yardstick
 
 pytestmark = pytest.mark.gpu
-MARGIN = 8.0
 
 
 @pytest.fixture(scope='module')
@@ -68,21 +68,6 @@ def nets(lib):
 def embeddings(nets):
     """Device embeddings of both cases, computed once."""
     return {case: nets[case](R.case_input(case).cuda()) for case in R.CASES}
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.numpy().view(np.uint64 if t.dtype == torch.float64 else np.uint32)
-
-
-def _yardstick(what, dev, f32, f64):
-    e_dev, e_ref = R.rel_err(dev, f64), R.rel_err(f32, f64)
-    print(f'\n{what}: e(device) {e_dev:.3e}  e(float32 reference) {e_ref:.3e}  ratio {e_dev / e_ref if e_ref else float("inf"):.3f}')
-    assert e_dev <= MARGIN * e_ref, (what, e_dev, e_ref)
 
 
 # ---- the whole network ---------------------------------------------------------------------------------------------------------------

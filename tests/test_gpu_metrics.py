@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import metrics_ref as R
+from _tools import _bits
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +29,6 @@ def M():
 
 def _dev(a):
     return torch.from_numpy(np.array(a)).cuda()
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().numpy().view(np.uint64)
 
 
 def _both(M, a, b, crop, order, y):

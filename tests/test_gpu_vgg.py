@@ -14,9 +14,9 @@ import torch
 from torch.nn import functional as F
 
 import vgg_ref as R
+from _tools import _bits, _np, _yardstick
 
 pytestmark = pytest.mark.gpu
-MARGIN = 8.0
 HALF_ULP = 2.0 ** -24
 
 
@@ -39,21 +39,6 @@ def nets(lib):
 def taps(nets):
     """Device forward of the three cases, computed once."""
     return {case: nets[case](R.case_input(case).cuda()) for case in R.CASES}
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.numpy().view(np.uint64 if t.dtype == torch.float64 else np.uint32)
-
-
-def _yardstick(what, dev, f32, f64, floor=0.0):
-    e_dev, e_ref = R.rel_err(dev, f64), max(R.rel_err(f32, f64), floor)
-    print(f'\n{what}: e(device) {e_dev:.3e}  e(float32 reference) {e_ref:.3e}  ratio {e_dev / e_ref if e_ref else float("inf"):.3f}')
-    assert e_dev <= MARGIN * e_ref, (what, e_dev, e_ref)
 
 
 # ---- the network ---------------------------------------------------------------------------------------------------------------------

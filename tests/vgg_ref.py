@@ -29,6 +29,7 @@ GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'vgg_ref.npz')
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from oracle.ref_loader import REF  # noqa: E402  (where the reference tree lies when it is present)
+from _tools import rel_err  # noqa: E402,F401  (beside this file; R.rel_err for the tests and tools)
 
 SAMPLES = 1024
 CASES = {
@@ -173,9 +174,3 @@ def load_reference():
             del sys.modules[k]
         sys.modules.update(saved)
     return mods[1], mods[3]
-
-
-def rel_err(x, ref):
-    """max|x - ref| / max|ref| in float64."""
-    x, ref = np.asarray(x, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    return float(np.abs(x - ref).max() / np.abs(ref).max())
