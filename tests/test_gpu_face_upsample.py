@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+from paste_cases import resize_linear_f32  # noqa: F401  (the float32 cv2.resize restatement; also read by test_face_upsample_host.py)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
 pytestmark = pytest.mark.gpu
@@ -22,31 +24,6 @@ def reduce_2to1_u8(img):
     """cv2.resize(uint8 (2h, 2w, 3), (w, h), INTER_LINEAR) at exactly 2:1: (a + b + c + d + 2) >> 2 (:459)."""
     s = img.astype(np.int64)
     return ((s[0::2, 0::2] + s[0::2, 1::2] + s[1::2, 0::2] + s[1::2, 1::2] + 2) >> 2).astype(np.uint8)
-
-
-def resize_linear_f32(img, dsize):
-    """cv2.resize(float32 plane, (dw, dh), INTER_LINEAR) (:482): f = float32((d + 0.5) * scale - 0.5), s = floor(f), f -= s, edges
-    clamped to (0, 0) / (n - 1, 0); rows horizontally first (a plain copy where s + 1 is past the edge), then vertically; float32
-    products and sums rounded separately."""
-    h, w = img.shape
-    dw, dh = dsize
-
-    def axis(n_src, n_dst):
-        f = ((np.arange(n_dst, dtype=np.float64) + 0.5) * (n_src / n_dst) - 0.5).astype(np.float32)
-        s = np.floor(f).astype(np.int64)
-        f = f - s.astype(np.float32)
-        lo, hi = s < 0, s >= n_src - 1
-        f[lo | hi] = 0
-        s[lo] = 0
-        s[hi] = n_src - 1
-        return s, f
-
-    sx, fx = axis(w, dw)
-    sy, fy = axis(h, dh)
-    one = np.float32(1)
-    two = sx + 1 < w
-    hr = np.where(two[None, :], img[:, sx] * (one - fx)[None, :] + img[:, np.minimum(sx + 1, w - 1)] * fx[None, :], img[:, sx])
-    return hr[sy] * (one - fy)[:, None] + hr[np.minimum(sy + 1, h - 1)] * fy[:, None]
 
 
 def band_mask(fs, border):
