@@ -1269,7 +1269,10 @@ static int conv_validate(const cf_conv_desc* d, const int* pq, ConvFacts& f) {
   const bool ext = !d->winograd && d->bf16_mfma != CF_OPERAND_F16X2 && (ld0 != d->c0 || ld1 != d->c1 || ldo != d->cout || d->epilogue >= CF_EPI_LEAKY ||
                    ((d->pad_mode != CF_PAD_ZERO || d->pad_lo) && !(d->out_nchw && d->cout <= 4)) ||
                    (d->bf16_mfma == CF_OPERAND_F16 && d->cout_pad % 64 != 0) ||
-                   (d->taps == 9 && d->stride == 1 && !d->in_nchw && !few_cout && (d->hout % 16 != 0 || d->wout % 16 != 0)));
+                   (d->taps == 9 && d->stride == 1 && !d->in_nchw && !few_cout && (d->hout % 16 != 0 || d->wout % 16 != 0)) ||
+                   // the folded upsample's dense tiles lie on the SOURCE grid (8 x 16 for 128-wide channel tiles): an 8x8 source gives an
+                   // on-grid 16x16 output that only the general instantiation can tile (BiSeNet's conv_head16 on a 128x128 face)
+                   (d->upsample && d->bf16_mfma == CF_OPERAND_F32 && d->cout_pad % 128 == 0 && (d->hin % 8 != 0 || d->win % 16 != 0)));
   if (ext) {
     CF_REQUIRE(d->taps == 9 && (d->stride == 1 || (d->bf16_mfma == CF_OPERAND_F32 && d->cout_pad % 128 == 0)) && !d->in_nchw &&
                    !d->out_nchw && d->bf16_mfma != CF_OPERAND_BF16 && !d->stats_out &&

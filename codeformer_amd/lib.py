@@ -125,6 +125,13 @@ SIGNATURES = {
     'cf_feat_dist': (_I, [_P, _P, _I, _L, _P, _P, _P]),
     'cf_lpips_parts': (_I, [_I]),
     'cf_lpips_head': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    'cf_pack_stem7x7': (_I, [_P, _P, _P]),
+    'cf_stem7x7s2': (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    'cf_maxpool3s2': (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    'cf_pooled_fc': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    'cf_scale_add_row': (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    'cf_resize_bilinear_ac': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    'cf_resize_bilinear_ac_argmax': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     'cf_warp_affine_u8':(_I, [_P, _L, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'cf_warp_affine_f32': (_I, [_P, _I, _I, ctypes.POINTER(ctypes.c_double), _P, _I, _I, _I, _I, _P]),
     'cf_erode_f32': (_I, [_P, _P, _P, _I, _I, _I, _P]),

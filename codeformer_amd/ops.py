@@ -1723,3 +1723,91 @@ def lpips_head(fa, fb, lin):
     out = torch.empty(B, dtype=torch.float64, device=fa.device)
     L.check(lib.cf_lpips_head(L.ptr(fa), L.ptr(fb), L.ptr(lin), B, hw, C, L.ptr(parts, dtype=torch.float64), L.ptr(out, dtype=torch.float64), L.stream_ptr()), 'cf_lpips_head')
     return out
+
+
+# ---- BiSeNet (cf_bisenet.hip) -- definitions at "BiSeNet / face parsing" in include/codeformer_hip.h --------------------------------------
+STEM_K = 148        # K of the 7x7 stem: 3 * 7 * 7 = 147 padded to a multiple of 4
+FC_MAX_C, FC_MAX_N = 4096, 512
+FC_ACT = {None: 0, 'none': 0, 'relu': 1, 'sigmoid': 2}
+
+
+def pack_stem7x7(weight):
+    """(64,3,7,7) float32 -> the (148,64) layout cf_stem7x7s2 reads: K ascending in (c, ky, kx), the last row zero."""
+    if tuple(_f32(weight).shape) != (64, 3, 7, 7):
+        raise ValueError(f'pack_stem7x7: a (64,3,7,7) weight, got {tuple(weight.shape)}')
+    w = weight.detach().contiguous()
+    wp = torch.empty((STEM_K, 64), dtype=torch.float32, device=w.device)
+    L.check(L.load().cf_pack_stem7x7(L.ptr(w), L.ptr(wp), L.stream_ptr()), 'cf_pack_stem7x7')
+    return wp
+
+
+def stem7x7s2(x, wp, bias):
+    """relu(conv 7x7 / stride 2 / pad 3 + bias) of a dense (B,3,H,W) float32 image -> (B,(H-1)//2+1,(W-1)//2+1,64) channels-last, on the
+    fp32 MFMA; wp from pack_stem7x7, bias (64,)."""
+    _f32(x)
+    if x.dim() != 4 or x.shape[1] != 3 or min(x.shape) < 1 or not x.is_contiguous():
+        raise ValueError(f'stem7x7s2: expected a dense float32 (B,3,H,W) image, got {tuple(x.shape)}')
+    if tuple(wp.shape) != (STEM_K, 64) or tuple(bias.shape) != (64,):
+        raise ValueError(f'stem7x7s2: wp {tuple(wp.shape)} / bias {tuple(bias.shape)} are not a pack_stem7x7 weight and 64 biases')
+    B, _, H, W = x.shape
+    out = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64), dtype=torch.float32, device=x.device)
+    L.check(L.load().cf_stem7x7s2(L.ptr(x), L.ptr(wp), L.ptr(bias), B, H, W, L.ptr(out), L.stream_ptr()), 'cf_stem7x7s2')
+    return out
+
+
+def maxpool3s2(x):
+    """MaxPool2d(3, 2, 1) of (B,H,W,C) channels-last -> (B,(H-1)//2+1,(W-1)//2+1,C); padding is -inf, a NaN wins."""
+    B, H, W, C = _nhwc_dense(x, 'maxpool3s2')
+    out = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=torch.float32, device=x.device)
+    L.check(L.load().cf_maxpool3s2(L.ptr(x), B, H, W, C, L.ptr(out), L.stream_ptr()), 'cf_maxpool3s2')
+    return out
+
+
+def pooled_fc(pooled, weight, bias, act=None):
+    """act(pooled @ weight^T + bias) on (B,C) rows: weight (N,C), bias (N,), act None | 'relu' | 'sigmoid'; one fmaf chain per output in
+    ascending c.  C <= FC_MAX_C with C % 4 == 0, N <= FC_MAX_N."""
+    B, C = _f32(pooled).shape
+    N = weight.shape[0]
+    if act not in FC_ACT:
+        raise ValueError(f'pooled_fc: act {act!r} (None, relu, sigmoid)')
+    if tuple(_f32(weight).shape) != (N, C) or tuple(_f32(bias).shape) != (N,) or C % 4 or C > FC_MAX_C or N > FC_MAX_N:
+        raise ValueError(f'pooled_fc: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} do not fit {C} channels (C % 4 == 0, C <= {FC_MAX_C}, N <= {FC_MAX_N})')
+    out = torch.empty((B, N), dtype=torch.float32, device=pooled.device)
+    L.check(L.load().cf_pooled_fc(L.ptr(pooled), L.ptr(weight), L.ptr(bias), B, C, N, FC_ACT[act], L.ptr(out), L.stream_ptr()), 'cf_pooled_fc')
+    return out
+
+
+def scale_add_row(x, g, r):
+    """x * g[b][c] + r[b][c]: x (B,H,W,C), g and r (B,C); multiply and add rounded separately."""
+    B, H, W, C = _nhwc_dense(x, 'scale_add_row')
+    if tuple(g.shape) != (B, C) or tuple(r.shape) != (B, C):
+        raise ValueError(f'scale_add_row: x {tuple(x.shape)}, g {tuple(g.shape)}, r {tuple(r.shape)}')
+    out = torch.empty_like(x)
+    L.check(L.load().cf_scale_add_row(L.ptr(x), L.ptr(g), L.ptr(r), B, H * W, C, L.ptr(out), L.stream_ptr()), 'cf_scale_add_row')
+    return out
+
+
+def _resize_ac_args(x, c, size, what):
+    B, H, W, ld = _nhwc_dense(x, what)
+    c = ld if c is None else int(c)
+    oh, ow = int(size[0]), int(size[1])
+    if not 1 <= c <= ld or oh < 1 or ow < 1:
+        raise ValueError(f'{what}: the first {c} of {ld} channels to {oh}x{ow}')
+    return B, H, W, ld, c, oh, ow
+
+
+def resize_bilinear_ac(x, size, c=None):
+    """F.interpolate(mode='bilinear', align_corners=True) of the first c channels of (B,h,w,ld) channels-last -> (B,c,H,W) NCHW."""
+    B, H, W, ld, c, oh, ow = _resize_ac_args(x, c, size, 'resize_bilinear_ac')
+    out = torch.empty((B, c, oh, ow), dtype=torch.float32, device=x.device)
+    L.check(L.load().cf_resize_bilinear_ac(L.ptr(x), B, H, W, ld, c, L.ptr(out), oh, ow, L.stream_ptr()), 'cf_resize_bilinear_ac')
+    return out
+
+
+def resize_bilinear_ac_argmax(x, size, c=None):
+    """(B,H,W) int64: the per-pixel argmax over the first c channels of what resize_bilinear_ac would write (lowest index among equal
+    maxima); the resized values are never stored and channels >= c are never read."""
+    B, H, W, ld, c, oh, ow = _resize_ac_args(x, c, size, 'resize_bilinear_ac_argmax')
+    out = torch.empty((B, oh, ow), dtype=torch.int64, device=x.device)
+    L.check(L.load().cf_resize_bilinear_ac_argmax(L.ptr(x), B, H, W, ld, c, L.ptr(out, dtype=torch.int64), oh, ow, L.stream_ptr()), 'cf_resize_bilinear_ac_argmax')
+    return out

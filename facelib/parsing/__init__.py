@@ -1,1 +1,1 @@
-from codeformer_amd.facelib.parsing import ParseNet, init_parsing_model  # noqa: F401
+from codeformer_amd.facelib.parsing import BiSeNet, ParseNet, init_parsing_model, load_bisenet  # noqa: F401

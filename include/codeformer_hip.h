@@ -615,6 +615,46 @@ int cf_feat_dist(const float* a, const float* b, int batch, int64_t n, double* p
 int cf_lpips_parts(int hw); /* -1: bad argument */
 int cf_lpips_head(const float* a, const float* b, const float* lin, int batch, int hw, int c, double* parts, double* out, cf_stream_t stream);
 
+/* ---- BiSeNet / face parsing (facelib/parsing/bisenet.py BiSeNet; facelib/parsing/resnet.py ResNet18) -------------------------------------
+ * Additive exports, CF_ABI_VERSION stays 22.  fp32; every pointer a kernel reads as float4 is 16-byte aligned (checked).  No reduction crosses
+ * a thread but the stem's matrix instruction, whose order is fixed: bitwise repeatable, image / row b of a batch is bitwise the call on it
+ * alone, no float atomics.  Every argument is checked before a launch.
+ *   cf_pack_stem7x7    w [64][3][7][7] -> wp [148][64] (9472 floats): wp[k][n] = w[n][c][ky][kx] at k = (c * 7 + ky) * 7 + kx -- ascending
+ *                      (c, ky, kx) -- and row 147, the padding of K = 147 to a multiple of 4, is zero.
+ *   cf_stem7x7s2       x [batch][3][h][w] contiguous -> out [batch][ho][wo][64], ho = (h - 1) / 2 + 1, wo likewise, any h, w >= 1:
+ *                      out = relu(bias[n] + sum_k wp[k][n] * x[c][2 oy - 3 + ky][2 ox - 3 + kx]), taps outside the image are zero (resnet.py:52,
+ *                      :61-62 with bn1 folded into wp / bias by the caller).  An implicit GEMM on v_mfma_f32_32x32x2_f32 with IEEE-fp32
+ *                      operands: the 148 products of an output are added in ONE accumulation chain from zero in ascending k, two k per
+ *                      instruction; then one addition of the bias; relu(v) = v > 0 ? v : +0, a NaN stays.  A padded k multiplies the zero
+ *                      weight by a stored zero, never by an image value.
+ *   cf_maxpool3s2      x [batch][h][w][c], c % 4 == 0 -> out [batch][(h - 1) / 2 + 1][(w - 1) / 2 + 1][c]: the max over rows 2 oy - 1 .. 2 oy + 1
+ *                      and columns 2 ox - 1 .. 2 ox + 1 that lie inside the image (nn.MaxPool2d(3, 2, 1), resnet.py:54: padding is -inf, not
+ *                      zero); a NaN wins.
+ *   cf_pooled_fc       pooled [batch][c], w [n][c], bias [n] -> out [batch][n] = act(s + bias[j]), s = one fmaf chain from zero over
+ *                      i = 0 .. c - 1 in ascending order of w[j][i] * pooled[b][i]; the bias is one more addition.  act: CF_FC_NONE,
+ *                      CF_FC_RELU (v > 0 ? v : +0, a NaN stays) or CF_FC_SIGMOID (1 / (1 + expf(-v)), as cf_se_gate).  c <= 4096, c % 4 == 0,
+ *                      n <= 512.  The 1x1 convolutions on a 1x1 map of bisenet.py:45-48 and :70-71, BatchNorm folded by the caller.
+ *   cf_scale_add_row   out[b][p][ch] = x[b][p][ch] * g[b][ch] + r[b][ch]; x / out [batch][hw][c], g / r [batch][c], c % 4 == 0; multiply and
+ *                      add rounded separately (bisenet.py:49 then :72-75: the nearest upsampling of a 1x1 map is a row broadcast).
+ *   cf_resize_bilinear_ac   x [batch][h][w][ld], the first c of ld channels (c <= ld, ld % 4 == 0) -> out [batch][c][oh][ow]:
+ *                      F.interpolate(mode='bilinear', align_corners=True) (bisenet.py:130-137).  Per axis, source size n_in, output size
+ *                      n_out, output index o:  scale = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0 (once per launch);
+ *                      src = scale * (float)o;  i0 = (int)src, clamped to 0 .. n_in - 1 before any address is formed;  i1 = i0 + (i0 < n_in - 1);
+ *                      l1 = src - (float)i0;  l0 = 1 - l1.  Value = l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d) with a, b the row-i0y
+ *                      neighbours and c, d the row-i1y ones; every step is one fp32 operation, none contracted.
+ *   cf_resize_bilinear_ac_argmax   the same values, compared and never stored: labels [batch][oh][ow] int64 = the index of the largest of the c
+ *                      values, the lowest index among equal maxima, a NaN counting as the largest.  Channels >= c are never read. */
+#define CF_FC_NONE 0
+#define CF_FC_RELU 1
+#define CF_FC_SIGMOID 2
+int cf_pack_stem7x7(const float* w, float* wp, cf_stream_t stream);
+int cf_stem7x7s2(const float* x, const float* wp, const float* bias, int batch, int h, int w, float* out, cf_stream_t stream);
+int cf_maxpool3s2(const float* x, int batch, int h, int w, int c, float* out, cf_stream_t stream);
+int cf_pooled_fc(const float* pooled, const float* w, const float* bias, int batch, int c, int n, int act, float* out, cf_stream_t stream);
+int cf_scale_add_row(const float* x, const float* g, const float* r, int batch, int hw, int c, float* out, cf_stream_t stream);
+int cf_resize_bilinear_ac(const float* x, int batch, int h, int w, int ld, int c, float* out, int oh, int ow, cf_stream_t stream);
+int cf_resize_bilinear_ac_argmax(const float* x, int batch, int h, int w, int ld, int c, int64_t* labels, int oh, int ow, cf_stream_t stream);
+
 /* ---- alignment warp and paste-back of the whole-image / video path ----------------------------------------------------------
  * Replaces the OpenCV calls of facelib/utils/face_restoration_helper.py: cv2.warpAffine of align_warp_face (:343-344) and of
  * paste_faces_to_input_image (:400, :428, :479), cv2.erode (:430-431, :447), cv2.GaussianBlur (:449), np.sum (:433), the soft-mask
