@@ -371,7 +371,9 @@ class CodeFormer(VQAutoEncoder):
         # (reference gap) / (2 x max |our logit - reference logit|) must stay >= 5 (review of round 4) -- measured 7.0 (split halves) /
         # 7.3 (fp32 operands) with the switch on against 9.9 / 8.7 with it off, over the seeded face, the three real crops, the masked face,
         # the four range variants and the 32-face sweep; no index differs anywhere; logits move by 5-11e-6 (tolerance 1e-4).  It buys 4 % of
-        # the step in the default mode and 9 % in 'fp32'.  Gate: tests/test_gpu_real_images.py::test_encoder_logit_margin (tools/logit_margin.py,
+        # the step in the default mode and 9 % in 'fp32'.  With fp32 operands the switch also puts the 512-channel 16^2 and 256-channel 32^2 latent
+        # layers on the K-part form of F(4x4,3x3) (ops.WINOGRAD_F43K): the smallest fp32 margin is then 6.3, no index differs, the largest logit
+        # error on those goldens stays at 1.0e-5 (profiles/NOTES.md).  Gate: tests/test_gpu_real_images.py::test_encoder_logit_margin (tools/logit_margin.py,
         # profiles/r05_logit_margin.txt).
         self.winograd_f43_encoder = os.environ.get('CODEFORMER_HIP_F43_ENCODER', '1') == '1'
         # Logit guard (CODEFORMER_HIP_LOGIT_GUARD): the gate above was measured with random-init weights only, so the network can watch the
@@ -466,7 +468,7 @@ class CodeFormer(VQAutoEncoder):
             raise ValueError(f"encoder_precision must be 'auto', 'fp32' or 'f16x2', got {self.encoder_precision!r}")
         enc_code = ops.SPLIT if self.encoder_precision == 'f16x2' or (self.encoder_precision == 'auto' and self.precision != 'fp32') else ops.WINOGRAD
         if self.winograd_f43_encoder if f43_encoder is None else f43_encoder:
-            enc_code = {ops.SPLIT: ops.SPLIT_F43, ops.WINOGRAD: ops.WINOGRAD_F43}[enc_code]
+            enc_code = {ops.SPLIT: ops.SPLIT_F43, ops.WINOGRAD: ops.WINOGRAD_F43K}[enc_code]
         lq = self.encoder.forward_nhwc(x, enc_taps, bf16=enc_code, img_u8=u8)        # (B,16,16,256) channels-last
         T = lq.shape[1] * lq.shape[2]
         tokens = lq.view(B * T, lq.shape[3])
@@ -504,8 +506,9 @@ class CodeFormer(VQAutoEncoder):
         when given), which is returned in place of the NCHW tensor."""
         B = quant.shape[0]
         # operand code of the generator + CFT 3x3 convs; 'fp32': F(4x4,3x3) on fp32 operands (four v_mfma_f32_16x16x4_f32 per 16 channels
-        # instead of three f16 MFMAs); 'f16x2': the encoder gets SPLIT_F43 through winograd_f43_encoder only (_encode_hip)
-        bf16 = {'fp32': ops.WINOGRAD_F43, 'f16x2': ops.SPLIT_F43, 'bf16': 1, 'fp16': 2}[self.precision]
+        # instead of three f16 MFMAs), in K parts of 128 input channels on the 16x16 / 32x32 layers (ops.f43k_ok; the encoder's latent layers take the
+        # same code under winograd_f43_encoder, _encode_hip); 'f16x2': the encoder gets SPLIT_F43 through winograd_f43_encoder only (_encode_hip)
+        bf16 = {'fp32': ops.WINOGRAD_F43K,'f16x2': ops.SPLIT_F43, 'bf16': 1, 'fp16': 2}[self.precision]
         gen_taps = None
         if (torch.is_tensor(w) and w.dim() == 1) or w > 0:      # (a 0-dim tensor is a number: `w > 0` decides, as ever)
             def fuse(t):
@@ -631,13 +634,16 @@ class CodeFormer(VQAutoEncoder):
                 torch.cuda.synchronize(x.device)
                 graph = torch.cuda.CUDAGraph()
                 # The zero-initialised scratch words of the range-scale / split-K kernels are kept per (device, stream).  Created inside the
-                # capture they would be two fill launches of every replay: create them for the capture stream first, outside the capture.
+                # capture they would be two fill launches of every replay (three with the workspace of the K-part F(4,3) layers, which comes
+                # from the same pool): create them for the capture stream first, outside the capture.
                 cap = _CAPTURE_STREAMS.get(str(x.device))
                 if cap is None:
                     cap = _CAPTURE_STREAMS[str(x.device)] = torch.cuda.Stream(device=x.device)
                 with torch.cuda.stream(cap):
                     ops._act_cells(x.device, 4 * max(int(x.shape[0]), 1))
                     ops._counters(x.device, 4096)
+                    if self.precision == 'fp32':    # the K-part F(4,3) layers' partial sums: this network's largest layer is 512 -> 256 @ 32x32, 2^20 words per face
+                        ops._kpart_ws(x.device, max(int(x.shape[0]), 1) << 20)
                 cap.synchronize()
                 # No garbage collection while capturing: a dead network (each one holds itself in _sig_modules, so it waits for the
                 # cyclic collector) takes its captured graphs with it, and tearing a graph down during a capture aborts the process.

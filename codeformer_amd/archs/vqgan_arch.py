@@ -135,7 +135,7 @@ class Upsample(HipModule):
         if int(bf16) == 2:
             bf16 = ops.SPLIT   # the input is the un-normalised residual stream: single IEEE halves have no range scaling on the direct kernel
         c = self.conv.in_channels
-        if int(bf16) == ops.WINOGRAD_F43 and x.dtype == torch.float32 and ops.f43_up_ok(c, self.conv.out_channels, 2 * x.shape[1], 2 * x.shape[2]):
+        if int(bf16) in ops.F43_FP32_CODES and x.dtype == torch.float32 and ops.f43_up_ok(c, self.conv.out_channels, 2 * x.shape[1], 2 * x.shape[2]):
             # precision 'fp32': four Winograd F(4x4,2x2) sub-pixel phases of the low-resolution image: 1.5625 fp32 products per output
             # instead of the 4 of the folded sub-pixel form on the direct kernel
             pw = self._packed(('conv', 'f42up'), lambda: ops.pack_weight(self.conv.weight, self.conv.bias, bf16=ops.WF42U), self.conv.weight, self.conv.bias)

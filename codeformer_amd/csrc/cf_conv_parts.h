@@ -29,7 +29,8 @@ int cf_winograd_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_que
 bool cf_wsplit_covers(const cf_conv_desc* d);                                         // cf_wsplit.hip: the eight-wave, 128-channel F(2,3) form,
 int cf_wsplit_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img = nullptr);   // called by cf_winograd_launch for what it covers
 int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img = nullptr);      // cf_wf43.hip: F(4,3)
-bool cf_wf43_k32(int cout, int cin);                                                  // cf_wf43.hip: F(4,3) / F(4,2) on 32-channel slabs? (cf_wf43_launch and the packers of cf_pack.hip)
+int cf_ksum_launch(const cf_conv_desc* d, hipStream_t stream, const float* sft_w_img);                                    // cf_ksum.hip: sum of the K parts of cf_wf43_launch + epilogue + statistics
+bool cf_wf43_k32(int cout, int cin);                                                // cf_wf43.hip: F(4,3) / F(4,2) on 32-channel slabs? (cf_wf43_launch and the packers of cf_pack.hip)
 int cf_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, const float* sft_w_img = nullptr);     // cf_split.hip: direct, split-half operands
 int cf_gemm_split_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query);  // cf_gemm_split.hip: split-half token GEMM
 int cf_gemm_f32_tile_try(const cf_conv_desc* d, hipStream_t stream);                  // cf_gemm_split.hip: fp32 token tiles (CF_OK: launched, 1: not its shape)

@@ -2,7 +2,9 @@
 //   <PRO, EPI, 8, 16>   64 output channels per eight-wave workgroup, TWO workgroups per CU (the text below describes this form)
 //   <PRO, EPI, 16, 32>  128 output channels per sixteen-wave workgroup on 32-channel slabs (see "The 16-wave form" at the end)
 //   <PRO, EPI, 16, 16>  the same on 16-channel slabs (cin % 32 != 0)
-// and, on the stages of <NONE, NONE, 16, 32> with fp32 operands, the Upsample blocks as four F(4x4,2x2) sub-pixel phases (see "UP" at the kernel)
+// and, on the stages of <NONE, NONE, 16, 32> with fp32 operands, the Upsample blocks as four F(4x4,2x2) sub-pixel phases (see "UP" at the kernel);
+// on those of <PRO, NONE, 16, 32> with fp32 operands, the 16x16 .. 32x32 layers in K parts of 128 input channels (see "KP" at the kernel; the sum
+// of the parts and the epilogue: cf_ksum.hip)
 //
 // Serves 3x3 stride-1 convolutions of generator and fusion (CFT) blocks (vqgan_arch.py:141-164,296-323, codeformer_arch.py:136-157) and,
 // since round 5, the encoder's covered layers (vqgan_arch.py:243-262) -- the encoder decides the code indices, so that use sits behind a
@@ -179,7 +181,8 @@ template <int PRO, int EPI, int NW, int KS, bool F32, int UPF = 0>
 __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   constexpr bool UP = UPF == 2;                  // the sub-pixel F(4,2) form
   constexpr bool GUP = UPF == 1;                 // the upsampling gather of F(4,3)
-  static_assert(UPF == 0 || (F32 && NW == 16 && KS == 32 && PRO == CF_PRO_NONE && EPI == CF_EPI_NONE), "the upsampling forms: fp32 operands on 32-channel slabs, no prologue, no epilogue operand");
+  constexpr bool KP = UPF == 3;                  // the K-part form (see "KP" at the slab base below)
+  static_assert(UPF == 0 || (F32 && NW == 16 && KS == 32 && (PRO == CF_PRO_NONE || KP) && EPI == CF_EPI_NONE), "the upsampling forms: fp32 operands on 32-channel slabs, no prologue, no epilogue operand; the K-part form: any prologue");
   constexpr int NPW = UP ? 13 : 18;              // transform-domain positions of a wave (UP: 13 of the lower half, 12 of the upper)
   constexpr int NXI = UP ? 5 : 6;                // positions per xi
   constexpr int OS = UP ? 2 : 1;                 // output pixels between the outputs of a workgroup
@@ -206,7 +209,15 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
 
   const int bid = cf_xcd_tile(blockIdx.x, gridDim.x);
   const int ntile = bid % a.ntn;
-  const int mt = bid / a.ntn;
+  // KP (UPF = 3; fp32 operands on 32-channel slabs, any prologue, no epilogue): a workgroup is (patch, K part, 128-channel block).  Part p covers the
+  // input channels [128 p, 128 p + 128) = slabs 4 p .. 4 p + 3, the virtual chunk of cf_common.h (CF_SK_SLABS x 16); the number of parts is
+  // cin / 128, fixed by the layer.  It gathers and transforms only those channels -- GroupNorm rows, concat select and the packed weight's slab
+  // offset all follow the absolute slab index -- accumulates from zero, runs the output transform and writes the RAW partial sums to plane p of
+  // a.out = the workspace [part][B][H][W][cout]; cf_ksum.hip adds the planes in part order and applies the epilogue.
+  const int kparts = KP ? a.cin / (4 * KS) : 1;
+  const int mtp = bid / a.ntn;
+  const int part = KP ? mtp % kparts : 0;
+  const int mt = KP ? mtp / kparts : mtp;
   const int n0 = ntile * F4_BN;
   const int b = mt / a.tiles_per_img;
   const int rt = mt - b * a.tiles_per_img;
@@ -217,11 +228,12 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   const int tyw = blk / a.tiles_x;
   const int y0 = tyw * F4_TH;
   const int x0 = (blk - tyw * a.tiles_x) * F4_TW;
-  const int n = a.cin / KS;   // slabs
+  const int s0 = KP ? 4 * part : 0;          // first slab of this workgroup
+  const int n = KP ? s0 + 4 : a.cin / KS;    // ... one past its last
 
   constexpr bool affine = PRO == CF_PRO_AFFINE || PRO == CF_PRO_AFFINE_SWISH;
   if (affine) {  // this image's GroupNorm rows -> LDS, read per slab by the patch store (first use is behind the first barrier)
-    for (int i = tid; i < a.cin; i += F4_THREADS) {
+    for (int i = tid + s0 * KS; i < (KP ? n * KS : a.cin); i += F4_THREADS) {
       tab[i] = a.pro_scale[(size_t)b * a.cin + i];
       tab[TABN + i] = a.pro_shift[(size_t)b * a.cin + i];
     }
@@ -642,7 +654,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
     if (wave < TWV) {
       __syncthreads();
       __syncthreads();  // patch(0) visible
-      for (int s = 0; s < n; ++s) {
+      for (int s = s0; s < n; ++s) {
         transform(s, [&]() __attribute__((always_inline)) {
           set_lane32();
           load_B32(s, 0);
@@ -671,12 +683,12 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
           store_patch_range(s, h1, h2);
         }
       };
-      load_A_range(0, h0, h1);
+      load_A_range(s0, h0, h1);
       __syncthreads();  // (the GroupNorm rows are in LDS)
-      feed2(0);
-      if (n > 1) load_A_range(1, h0, h1);
+      feed2(s0);
+      if (n > s0 + 1) load_A_range(s0 + 1, h0, h1);
       __syncthreads();
-      for (int s = 0; s < n; ++s) {
+      for (int s = s0; s < n; ++s) {
         feed2(s + 1);
         __builtin_amdgcn_sched_barrier(0);
         set_lane32();
@@ -775,7 +787,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
   const unsigned e_rowc = (unsigned)(OS * OS * a.w) * (unsigned)a.cout * 4u;   // bytes between the workgroup's output rows
   const unsigned e_px = (unsigned)(OS * a.cout) * 4u;                          // ... between its pixels
   const unsigned e_img = (unsigned)(OS * OS) * img_px * (unsigned)a.cout * 4u;
-  const __amdgpu_buffer_rsrc_t rs_out = f4_rsrc(a.out + (size_t)(OS * OS) * img0 * a.cout, e_img);
+  const __amdgpu_buffer_rsrc_t rs_out = f4_rsrc(a.out + ((size_t)(OS * OS) * img0 + (KP ? (size_t)part * a.batch * img_px : (size_t)0)) * a.cout, e_img);
   const __amdgpu_buffer_rsrc_t rs_res = f4_rsrc(EPI == CF_EPI_NONE ? a.out : a.res + img0 * a.cout, e_img);
   const __amdgpu_buffer_rsrc_t rs_sft = f4_rsrc(EPI == CF_EPI_SFT ? a.sft_scale + img0 * a.cout : a.out, e_img);
   const bool rh1 = e_rh != 0;
@@ -879,7 +891,7 @@ __global__ __launch_bounds__(NW * 64, 4) void wf43_kernel(const F4Args a) {
       f4_f32x2 rs = {0.f, 0.f}, rq = {0.f, 0.f};
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        f4_f32x2 v = o[aa][c] * acc_s + bias2;
+        f4_f32x2 v = KP ? o[aa][c] : o[aa][c] * acc_s + bias2;   // (KP: the raw partial sum)
         if (EPI == CF_EPI_RESIDUAL) v += r0[aa][c];
         else if (EPI == CF_EPI_SFT) v = r0[aa][c] + sft_w * (r0[aa][c] * r1[aa][c] + v);
         o[aa][c] = v;   // (stored below: the eight stores of a pass sit behind ONE wave-uniform choice of their cache policy)
@@ -992,7 +1004,14 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, 
   const int tab_max = cf_wf43_k32(d->cout, d->c0 + d->c1) ? F4_TAB_32 : F4_TAB;   // (the 32-channel-slab form holds 512 GroupNorm rows)
   CF_REQUIRE(d->c0 + d->c1 <= tab_max, "cf_conv2d(winograd 2): at most %d input channels in this form (got %d)", tab_max, d->c0 + d->c1);
   CF_REQUIRE(cf_epi_is_quad_triple(d), "cf_conv2d(winograd 2): epilogues are none / residual / SFT");
-  CF_REQUIRE(cf_dense_zero_pad(d) && d->split_k < 1, "cf_conv2d(winograd 2): reads / writes dense tensors with zero padding, no split_k");
+  // The K-part form (fp32 operands; the 16x16 .. 32x32 layers, where an image has 1 .. 4 patches): split_k = cin / 128 parts, each a workgroup
+  // of its own that writes raw partial sums to d->workspace [part][B][H][W][cout]; cf_ksum_launch adds them in part order and applies the epilogue.
+  const bool kp = d->split_k >= 2;
+  CF_REQUIRE(cf_dense_zero_pad(d) && (d->split_k < 1 || kp), "cf_conv2d(winograd 2): reads / writes dense tensors with zero padding, no split_k but the K-part form's cin / 128");
+  CF_REQUIRE(!kp || (f32 && !d->upsample && !d->io_bf16 && d->cout % 128 == 0 && (d->c0 + d->c1) % 128 == 0 && d->c0 + d->c1 <= 512 && d->c0 % 128 == 0 &&
+                     d->split_k == (d->c0 + d->c1) / 128 && (parts_query || d->workspace)),
+             "cf_conv2d(winograd 2, K parts): fp32 operands, cout %% 128 == 0, cin %% 128 == 0 and <= 512, a concat boundary on a multiple of 128, split_k == cin / 128 "
+             "(got %d for cin %d) and a workspace of split_k x batch x hout x wout x cout floats", d->split_k, d->c0 + d->c1);
   CF_REQUIRE(d->stats_cpg == 0 || (d->stats_cpg <= 64 && (d->stats_cpg & (d->stats_cpg - 1)) == 0 && d->stats_cpg >= 2),
              "cf_conv2d(winograd 2): stats_cpg %d (a power of two, 2..64)", d->stats_cpg);
   F4Args a;
@@ -1031,8 +1050,26 @@ int cf_wf43_launch(const cf_conv_desc* d, hipStream_t stream, int* parts_query, 
     CF_CHECK_LAUNCH("cf_conv2d(winograd F(4,3) / F(4,2) fp32, upsampling forms)");
     return CF_OK;
   }
+  if (kp) {
+    CF_REQUIRE(k32, "cf_conv2d(winograd 2, K parts): runs on 32-channel slabs only (CF_F43_WIDE=k16 is set)");
+    // first launch: no scale, bias, epilogue operand or statistics -- those belong to the sum; the workspace is read back at once, so it stays in the caches
+    F4Args p = a;
+    p.out = d->workspace;
+    p.epilogue = CF_EPI_NONE;
+    p.bias = p.res = p.sft_scale = nullptr;
+    p.stats_out = nullptr;
+    p.nt_out = 0;
+    const dim3 pgrid(grid.x * d->split_k);
+    cf_with_prologue(d->prologue, [&](auto pro) {
+      constexpr int P = decltype(pro)::value;
+      CF_LDS_ATTR((wf43_kernel<P, CF_EPI_NONE, 16, 32, true, 3>), F4_LDS_FLOATS_32 * sizeof(float));
+      hipLaunchKernelGGL((wf43_kernel<P, CF_EPI_NONE, 16, 32, true, 3>), pgrid, block, lds, stream, p);
+    });
+    CF_CHECK_LAUNCH("cf_conv2d(winograd F(4,3) fp32, K parts)");
+    return cf_ksum_launch(d, stream, sft_w_img);
+  }
   // one (PRO, EPI, operand) -> its three forms, of which the layer's shape picks one
-  auto launch = [&](auto pro, auto epi, auto op) {
+  auto launch =[&](auto pro, auto epi, auto op) {
     constexpr int P = decltype(pro)::value, E = decltype(epi)::value;
     constexpr bool O = decltype(op)::value;
     CF_LDS_ATTR((wf43_kernel<P, E, 8, 16, O>), F4_LDS_FLOATS * sizeof(float));

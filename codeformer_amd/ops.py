@@ -137,10 +137,11 @@ class PackedWeight:
     """A conv / linear weight in the kernel layout [tap][cin_pad/16][cout_pad][16] (+ bias).
     `bf16` is the operand code of cf_conv_desc.bf16_mfma: 0 / False fp32, 1 / True bf16, 2 IEEE half."""
 
-    __slots__ = ('w', 'bias', 'cout', 'cin', 'taps', 'cout_pad', 'cin_pad', 'bf16', 'up2x', 'wino', 'scale', 's2', 'conv1')
+    __slots__ = ('w', 'bias', 'cout', 'cin', 'taps', 'cout_pad', 'cin_pad', 'bf16', 'up2x', 'wino', 'scale', 's2', 'conv1', 'kparts')
 
-    def __init__(self, w, bias, cout, cin, taps, cout_pad, cin_pad, bf16=False, up2x=False, wino=False, scale=1.0, s2=False, conv1=False):
+    def __init__(self, w, bias, cout, cin, taps, cout_pad, cin_pad, bf16=False, up2x=False, wino=False, scale=1.0, s2=False, conv1=False, kparts=0):
         self.w, self.bias, self.cout, self.cin, self.taps = w, bias, cout, cin, taps
+        self.kparts = kparts  # fp32 F(4,3) packing that runs the K-part form: cin / 128 parts (WF43K), else 0
         self.cout_pad, self.cin_pad, self.bf16, self.up2x, self.wino = cout_pad, cin_pad, bf16, up2x, wino
         self.s2 = s2         # f16x2 packing in the stride-2 (space-to-depth) form: only conv2d(stride=2) takes it
         self.conv1 = conv1   # f16x2 1x1 weight in the convolution kernel's layout (images of more than TOKEN_IMAGE_MAX pixels), not the token GEMM's
@@ -166,6 +167,9 @@ WF43 = 11      # ... Winograd F(4x4,3x3) with split-half operands (cf_wf43.hip; 
 WINOGRAD_F43 = 12   # ... REQUEST: WINOGRAD (exact fp32), with Winograd F(4x4,3x3) on fp32 operands where its kernel applies (generator / CFT only)
 WF43F = 13     # ... Winograd F(4x4,3x3) with IEEE-fp32 operands (cf_wf43.hip on v_mfma_f32_16x16x4_f32; winograd = 2, operand fp32)
 WF42U = 14     # ... nearest x2 + 3x3 as four Winograd F(4x4,2x2) sub-pixel phases with IEEE-fp32 operands (cf_wf43.hip; winograd = 2 + upsample)
+WINOGRAD_F43K = 15  # ... REQUEST: WINOGRAD_F43, and the K-part form of the fp32 F(4,3) kernel on the 16x16 .. 32x32 layers it covers (f43k_ok)
+WF43K = 16     # ... the WF43F packing, launched in K parts of 128 input channels + a sum-and-epilogue launch (cf_wf43.hip "KP", cf_ksum.hip)
+F43_FP32_CODES = (WINOGRAD_F43, WINOGRAD_F43K)   # the requests for exact-fp32 operands with F(4,3) where it applies
 OPERAND_F16X2 = 3   # enum cf_operand value behind SPLIT / WSPLIT / GSPLIT / WF43
 SPLIT_CODES = (SPLIT, SPLIT_F43)   # requested codes that put un-normalised inputs / stride-2 / 1x1 layers on the split-half kernels
 
@@ -197,7 +201,10 @@ def winograd_ok(cin, cout, hout, wout):
 # 8-wave form, two workgroups per CU: x1.0-1.17 at sixteen faces) and the layers with a multiple of 128 output channels (the 16-wave form)
 # from F43_WIDE_MIN_PIXELS up.  Split-half operands: 128x128 -- at 64x64 the form wins x1.11 at sixteen faces (0.15 ms of a 36 ms step) but a
 # 64x64 image has 16 patches, and at one face per call its 9 launches cost 0.5 ms of 7.1 (140 -> 150 faces/s with the limit at 128x128);
-# fp32 operands: 64x64 (x1.75 there: the fp32 MFMA work itself is the bound).  At 32x32 it loses at any batch (x0.6: 4 patches per image).
+# fp32 operands: 64x64 (x1.75 there: the fp32 MFMA work itself is the bound).  Below 64x64 the WHOLE-K form loses at any batch (x0.6 at 32x32: 4
+# patches per image, a K chain of 8 - 16 slabs per workgroup); with fp32 operands those layers run the K-PART form instead (WINOGRAD_F43K ->
+# f43k_ok below: x1.3 - 1.5 against F(2,3) on the three adopted classes at sixteen faces, 0.8 ms of the 45 ms step; at one face per call the
+# fp32 forward is 8 % slower, 8.63 -> 9.33 ms -- the rule cannot follow the batch).
 # The rule is a function of the per-image shape only: results do not depend on the batch.
 F43_WIDE_MIN_PIXELS = 128 * 128        # smallest image of the 16-wave form, split-half operands
 F43_WIDE_MIN_PIXELS_FP32 = 64 * 64     # ... fp32 operands
@@ -211,6 +218,29 @@ def f43_ok(cin, cout, hout, wout, fp32=False):
         return False
     cin_max = 512 if (cout % 128 == 0 and cin % 32 == 0) else 256     # GroupNorm rows in LDS: 512 in the 16-wave form on 32-channel slabs (round 6), else 256
     return cin % 16 == 0 and cin <= cin_max and cout % 64 == 0 and hout % 16 == 0 and wout % 16 == 0
+
+
+F43K_MIN_WORKGROUPS = 16               # K-part form: fewest workgroups an image must give (256 CUs / 16 faces)
+
+
+def f43k_ok(cin, cout, hout, wout, c_split=None):
+    """Shapes a WINOGRAD_F43K request puts on the K-part form of the fp32 F(4x4,3x3) kernel (3x3 stride-1 dense NHWC): the 16x16 .. 32x32 layers
+    with whole 128-channel parts on both sides.  An image of these sizes has 1 or 4 patches, too few workgroups for the whole-K form; one
+    workgroup per (patch, 128 input channels, 128 output channels) fills the chip at sixteen faces and shortens the K chain to 4 slabs.  A
+    function of the per-image shape only: the number of parts is cin / 128 whatever the batch.  (cin = 128 is one part: the whole-K form plus
+    a pass over the output, so it stays where WINOGRAD_F43 puts it.)
+    Narrowed to where the pair of launches measured shorter than the F(2,3) launch it replaces (sixteen faces, profiles/NOTES.md): an image must
+    give at least F43K_MIN_WORKGROUPS (patch, part, channel block) workgroups, so that sixteen faces fill the 256 CUs in one round.  512 -> 512 @
+    16x16 (16 per image: 117 -> 77 us), 256 -> 256 @ 32x32 (16: 91 -> 69 us) and 512 -> 256 @ 32x32 (32: 183 -> 130 us) pass; 256 -> 512 and
+    512 -> 256 @ 16x16 (8 per image, half the chip: 59 -> 65 us and 70 -> 69 us, together longer) stay on F(2,3)."""
+    return f43k_covers(cin, cout, hout, wout, c_split) and (hout // 16) * (wout // 16) * (cin // 128) * (cout // 128) >= F43K_MIN_WORKGROUPS
+
+
+def f43k_covers(cin, cout, hout, wout, c_split=None):
+    """Shapes a weight packed with bf16=WF43K can be launched on (the form itself; f43k_ok is the policy): 2 .. 4 whole parts of 128 input
+    channels, 128-wide channel blocks, whole 16x16 patches, images of 16x16 up to (not including) 64x64 pixels, a concat boundary between parts."""
+    return cout % 128 == 0 and cin % 128 == 0 and 256 <= cin <= 512 and hout % 16 == 0 and wout % 16 == 0 and 256 <= hout * wout < F43_WIDE_MIN_PIXELS_FP32 and \
+        (c_split is None or c_split % 128 == 0)
 
 
 # precision 'fp32': the Upsample blocks (nearest x2 + 3x3) as four Winograd F(4x4,2x2) sub-pixel phases on the fp32 F(4,3) kernel's stages
@@ -247,6 +277,10 @@ def conv_code(code, cin, cout, h, w, up2x=False, c_split=None, plain=True):
     on the per-image shape only (never on the batch), so results stay batch-invariant."""
     code = int(code)
     f43_slab = 32 if (cout % 128 == 0 and cin % 32 == 0) else 16   # slab of the form cf_conv2d runs: a concat boundary must not cut one
+    if code == WINOGRAD_F43K:
+        if plain and not up2x and f43k_ok(cin, cout, h, w, c_split):
+            return WF43K
+        code = WINOGRAD_F43
     if code == WINOGRAD_F43:
         if plain and not up2x and c_split_ok(c_split, f43_slab) and f43_ok(cin, cout, h, w, fp32=True):
             return WF43F
@@ -477,6 +511,7 @@ _WINO = {WINOGRAD: ('winograd', 'cf_pack_conv_weight_winograd', 16, None, False,
          WF16: ('winograd f16x2', 'cf_pack_conv_weight_winograd_f16x2', 16, _f23_max, 2, True),   # (reads the hi slot)
          WBF16: ('winograd f16x2', 'cf_pack_conv_weight_winograd_bf16', 16, _f23_max, 1, True),
          WF43F: ('winograd F(4,3)', 'cf_pack_conv_weight_winograd43', 36, None, False, 2),
+         WF43K: ('winograd F(4,3) K parts', 'cf_pack_conv_weight_winograd43', 36, None, False, 2),   # (the WF43F packing; PackedWeight.kparts selects the launch form)
          WF42U: ('winograd F(4,2) sub-pixel', 'cf_pack_conv_weight_winograd42_up', 100, None, False, 2),   # (4 phases x 25 positions)
          WF43: ('winograd F(4,3) f16x2', 'cf_pack_conv_weight_winograd43_f16x2', 36, _f43_max, OPERAND_F16X2, 2)}
 
@@ -484,10 +519,14 @@ _WINO = {WINOGRAD: ('winograd', 'cf_pack_conv_weight_winograd', 16, None, False,
 def _pack_winograd(w, b, code, up2x, stride2):
     what, fn, npos, domain_max, operand, wino = _WINO[code]
     up = code == WF42U
-    _require_3x3(w, 32 if up else 16, 128 if up else 64, what, up2x)
+    kp = code == WF43K
+    _require_3x3(w, 128 if kp else 32 if up else 16, 128 if (up or kp) else 64, what, up2x)
     cout, cin = w.shape[:2]
+    if kp and not 256 <= cin <= 512:
+        raise ValueError(f'{what} packing needs 2 .. 4 parts of 128 input channels (got cin {cin})')
     scale = () if domain_max is None else (pack_scale(domain_max(w)),)
-    return PackedWeight(_packed(fn, npos * cin * cout, w, cout, cin, cout, cin, *scale), b, cout, cin, 9, cout, cin, bf16=operand, up2x=up, wino=wino, scale=(*scale, 1.0)[0])
+    return PackedWeight(_packed(fn, npos * cin * cout, w, cout, cin, cout, cin, *scale), b, cout, cin, 9, cout, cin, bf16=operand, up2x=up, wino=wino, scale=(*scale, 1.0)[0],
+                        kparts=cin // 128 if kp else 0)
 
 
 def _pack_split(w, b, code, up2x, stride2):
@@ -615,6 +654,16 @@ def splitk_for(pw, ho, wo, cin, batch=1):
 def _counters(device, n):
     """n zero-initialised tile counters per (device, stream); every split-K launch leaves its counters at zero again."""
     return _scratch(_COUNTERS, device, n, 4096)
+
+
+_KPART_WS = {}
+
+
+def _kpart_ws(device, n):
+    """n words per (device, stream) for the partial sums of a K-part F(4,3) launch (conv2d, pw.kparts): written by its first launch and read by its
+    second, so every such layer of a stream shares one buffer.  The retired-scratch rule of _scratch holds: a captured graph keeps the raw address,
+    so a buffer that a larger layer replaces stays allocated for the life of the process."""
+    return _scratch(_KPART_WS, device, n, 1 << 22)
 
 
 def _roofline_kind(pw, io, stride, upsample, c0, in_nchw, out_nchw, out_pixels, split_k):
@@ -765,7 +814,15 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
         if tuple(act.shape) != (B, 2) or prologue not in (PRO_NONE, PRO_LEAKY):
             raise ValueError('act: expected a (B, 2) table and a none / leaky prologue')
         d.act_scale = L.ptr(act)
-    if split_k is None:
+    if pw.kparts:
+        # the K-part form of the fp32 F(4,3) kernel: cin / 128 planes of raw partial sums in the per-stream workspace, then the sum-and-epilogue launch
+        dense = not in_nchw and not out_nchw and ld0 == c0 and (c1 == 0 or ld1 == c1) and ldo in (0, pw.cout)
+        if split_k or upsample or stride != 1 or not dense or io != torch.float32 or not f43k_covers(c0 + c1, pw.cout, Ho, Wo, c0 if c1 else None):
+            raise ValueError('a weight packed with bf16=WF43K serves dense fp32 3x3 stride-1 launches of the shapes f43k_covers names (conv_code decides: pack with its answer)')
+        d.split_k = pw.kparts
+        d.workspace = L.ptr(_kpart_ws(dev, pw.kparts * B * Ho * Wo * pw.cout), dtype=torch.int32)
+        split_k = 0
+    elif split_k is None:
         dense = not in_nchw and not out_nchw and ld0 == c0 and (c1 == 0 or ld1 == c1) and ldo in (0, pw.cout)
         split_k = splitk_for(pw, Ho, Wo, c0 + c1, B) if (stride == 1 and dense) else 0
     if split_k:

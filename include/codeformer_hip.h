@@ -199,7 +199,11 @@ typedef struct cf_conv_desc {
    * tile (cf_conv2d_tiles(d)), left at zero by every launch.
    * ABI v21: CF_SPLITK_IN_WORKGROUP (-1), taps == 1 with CF_OPERAND_F16X2 only (token GEMMs of one to a few faces): the K chunks of a
    * 32 x 32 output tile are shared by the four waves of ONE workgroup and added in chunk order through LDS -- the same bits as every
-   * other split count, no workspace / counters (K <= 1024, M % 32 == 0; N % 64 == 0 as for every form: the weight packing). */
+   * other split count, no workspace / counters (K <= 1024, M % 32 == 0; N % 64 == 0 as for every form: the weight packing).
+   * winograd == 2 with CF_OPERAND_F32 (additive, the ABI version stays): split_k == cin / 128 (2 .. 4) selects the K-part form of F(4x4,3x3) --
+   * one workgroup per (patch, 128 input channels, 128 output channels) writes raw partial sums to `workspace`
+   * ([split_k][batch][hout][wout][cout] floats, no counters), a second launch adds them in part order from zero and applies acc_scale,
+   * bias, epilogue and statistics.  cout % 128 == 0, cin % 128 == 0, cin <= 512, c0 % 128 == 0, no upsample; any other split_k is refused. */
   int32_t split_k;
   float* workspace;
   uint32_t* counters;
