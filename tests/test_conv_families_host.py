@@ -10,7 +10,12 @@ For the input families of tools/conv_check.py:
   * onehot_pixels / tap_shift: the fp64 result IS the flipped weight slice + bias / the shifted input, the pixels are >= 3 apart and sit where
     the docstring says; cancel_pairs is ill-conditioned, mixed_cout reaches subnormal lo and hi halves under the host's own scale rule;
   * routes() against a table of expected kernel forms for the issue's shapes, every route reached, and the C library's own validation
-    (cf_conv2d_stats_parts: the code of a launch up to the point where a kernel would start) accepts every launch the GPU test makes.
+    (cf_conv2d_stats_parts: the code of a launch up to the point where a kernel would start) accepts every launch the GPU test makes;
+  * the sub-pixel F(4,2) route w42_up at its shapes u1, zu1, zu2 (1, 3 and 8 slabs): its fp64 evaluation is conv_case.reference(upsample=True), its
+    weights are ops.f42_weights, its S lies between the folded direct sum and 4556.25 sum_c max|g_p,c| max|p_c|; the float32 emulation stays within half
+    the gate for every family the route admits, onehot_pixels and all nine tap_shift taps; the emulation with the taps of phase (b, a) given to phase
+    (a, b), or with one position lost to the idle accumulator, stands at >= 10 times the gate on some family at every shape; and the older keys' data is
+    what it was before zu1 / zu2 existed (digests).
 """
 import ctypes
 
@@ -23,11 +28,14 @@ from _tools import load_script
 
 @pytest.fixture(scope='module')
 def cc():
-    return load_script('tools/conv_check.py')
+    m = load_script('tools/conv_check.py')
+    m.with_f42()          # (zu1, zu2 behind the older keys, whose data test_every_older_key_keeps_its_data pins)
+    return m
 
 
 LARGEST = ('d', 'f', 'g', 'u1')        # most pixels, most input channels, most output channels, folded
-ALL_KEYS = ('a', 'b', 'c', 'd', 'e', 'f', 'g', 'u1', 'u2')
+ALL_KEYS = ('a', 'b', 'c', 'd', 'e', 'f', 'g', 'u1', 'u2', 'zu1', 'zu2')
+W42_KEYS = ('u1', 'zu1', 'zu2')        # the shapes of the sub-pixel F(4,2) form: 1, 3 and 8 slabs
 GATE_FAMILIES = ('mixed_cout', 'mixed_cin', 'mixed_cin_act', 'cancel_pairs', 'dc_plus_ripple', 'swish_leaky_edges', 'swish_leaky_edges_sft')
 PROLOGUE_ONLY = ('mixed_cin', 'swish_leaky_edges', 'swish_leaky_edges_sft', 'solo_cin')      # families that ARE their prologue: not on upsampling shapes
 SOLO_FAMILIES = ('solo_cin', 'solo_cin_act')
@@ -37,7 +45,9 @@ def test_families_and_shapes_are_the_issue_s(cc):
     assert cc.GATE_FAMILIES == GATE_FAMILIES and cc.SOLO_FAMILIES == SOLO_FAMILIES
     assert {k: v[:5] for k, v in cc.SHAPES.items()} == {'a': (1, 16, 16, 16, 64), 'b': (2, 16, 32, 32, 64), 'c': (2, 32, 32, 64, 128), 'd': (3, 32, 48, 48, 128),
                                                         'e': (1, 16, 16, 256, 64), 'f': (1, 16, 16, 512, 128), 'g': (1, 48, 32, 192, 192),
-                                                        'u1': (2, 16, 16, 32, 128), 'u2': (1, 16, 16, 64, 64)}
+                                                        'u1': (2, 16, 16, 32, 128), 'u2': (1, 16, 16, 64, 64), 'zu1': (1, 32, 48, 96, 256),
+                                                        'zu2': (1, 16, 16, 256, 128)}
+    assert tuple(cc.SHAPES) == ALL_KEYS and all(cc.SHAPES[k][6] for k in W42_KEYS)
     assert all(B <= 3 and H <= 48 and W <= 48 and cin <= 512 for B, H, W, cin, _, _, _ in cc.SHAPES.values())
 
 
@@ -49,7 +59,7 @@ def _schemes(cc, key):
     return list(seen.values())
 
 
-@pytest.mark.parametrize('family,key', [(f, k) for f in GATE_FAMILIES + SOLO_FAMILIES + ('onehot_pixels',) for k in ALL_KEYS if not (k.startswith('u') and f in PROLOGUE_ONLY)])
+@pytest.mark.parametrize('family,key', [(f, k) for f in GATE_FAMILIES + SOLO_FAMILIES + ('onehot_pixels',) for k in ALL_KEYS if not ('u' in k and f in PROLOGUE_ONLY)])
 def test_emulation_within_half_of_the_gate(cc, family, key):
     assert not (cc.SHAPES[key][6] and family in PROLOGUE_ONLY)            # (upsampling shapes take no prologue)
     for cname, code, route in _schemes(cc, key):
@@ -58,7 +68,7 @@ def test_emulation_within_half_of_the_gate(cc, family, key):
         assert r <= 0.5, (family, key, route, cname, r, err)
 
 
-@pytest.mark.parametrize('key', ('b', 'c', 'd', 'u1'))            # the shapes of the GPU test's tap_shift cases
+@pytest.mark.parametrize('key', ('b', 'c', 'd', 'u1', 'zu1', 'zu2'))            # the shapes of the GPU test's tap_shift cases
 def test_tap_shift_emulation_within_half_of_the_gate(cc, key):
     for tap in range(9):
         for cname, code, route in _schemes(cc, key):
@@ -151,12 +161,18 @@ def test_tap_shift_moves_the_input_by_one_pixel(cc):
 
 def test_hard_families_are_hard(cc):
     from codeformer_amd import ops
-    for key in LARGEST:
+    for key in LARGEST + W42_KEYS[1:]:
         d, ref = cc.prepared('cancel_pairs', key)
         S = cc._abs_eval('cancel_pairs', key, 0, 0)[0]
         cond = float((S / ref['pre'].abs()).median())
         print(f'cancel_pairs {key}: median S / |pre| {cond:.3g}')
         assert cond >= 100 and torch.equal(d['x'][..., 0::2], d['x'][..., 1::2])
+        if key in W42_KEYS:          # the same two preconditions with the S of the sub-pixel form, whose operand is the folded tap (a sum of up to four weights)
+            for fam in ('cancel_pairs', 'dc_plus_ripple'):
+                pre, S42 = cc.prepared(fam, key)[1]['pre'], cc._abs_eval(fam, key, 0, cc.F42)[0]
+                cond = float((S42 / pre.abs()).median())
+                print(f'{fam} {key}: median S / |pre| {cond:.3g} with the F(4,2) S')
+                assert cond >= 100, (fam, key, cond)
         assert not torch.equal(d['w'][:, 0::2].abs(), d['w'][:, 1::2].abs())
         d = cc.family('mixed_cout', key)
         for m in (0, 2, 4):
@@ -268,8 +284,10 @@ EXPECTED_FORMS = {
           ('WSPLIT', 2): ('w23_h4', 'split-K 2'), ('WSPLIT', 4): ('w23_h4', 'split-K 4'), ('WF43', 0): ('w43_16k32', 'ntn 1'), ('WF43F', 0): ('w43_16k32', 'ntn 1')},
     'g': {('F32', 0): ('d32', '128x128'), ('SPLIT', 0): ('dsplit', 'form 0 64-wide'), ('WINOGRAD', 0): ('w23_f32', 'four-wave'), ('WSPLIT', 0): ('w23_h4', 'four-wave'),
           ('WF43', 0): ('w43_8', 'ntn 3'), ('WF43F', 0): ('w43_8', 'ntn 3')},
-    'u1': {('F32', 0): ('d32', 'folded narrow 128x64'), ('SPLIT', 0): ('dsplit', 'form 1 64-wide'), ('WF43F', 0): ('w43_up', 'k32 gather')},
+    'u1': {('F32', 0): ('d32', 'folded narrow 128x64'), ('SPLIT', 0): ('dsplit', 'form 1 64-wide'), ('WF43F', 0): ('w43_up', 'k32 gather'), ('WF42U', 0): ('w42_up', 'sub-pixel phases')},
     'u2': {('F32', 0): ('d32', 'folded 256x64'), ('SPLIT', 0): ('dsplit', 'form 1 64-wide')},
+    'zu1': {('F32', 0): ('d32', 'folded 128x128'), ('SPLIT', 0): ('dsplit', 'form 1 64-wide'), ('WF43F', 0): ('w43_up', 'k32 gather'), ('WF42U', 0): ('w42_up', 'sub-pixel phases')},
+    'zu2': {('F32', 0): ('d32', 'folded narrow 128x64'), ('SPLIT', 0): ('dsplit', 'form 1 64-wide'), ('WF43F', 0): ('w43_up', 'k32 gather'), ('WF42U', 0): ('w42_up', 'sub-pixel phases')},
 }
 
 
@@ -285,6 +303,12 @@ def test_routes_against_the_table_of_expected_forms(cc):
     assert cc.route_of(ops.SPLIT, 16, 16, 16, 64) is None and cc.route_of(ops.WF16, 16, 16, 16, 64) is None
     assert cc.route_of(ops.WF43, 16, 16, 512, 64) is None and cc.route_of(ops.WF43, 16, 16, 32, 128, up=True) is None
     assert cc.route_of(ops.WINOGRAD, 16, 16, 256, 64, split_k=4) is None and cc.route_of(ops.WF43F, 32, 32, 64, 128, c_split=16) is None
+    # the sub-pixel form, by the rule of cf_wf43_launch: an upsampling launch of one input on whole slabs, channel tiles and 16x16 input blocks -- and
+    # nothing of the ops.f43_up_ok policy (no smallest size: 16x16 inputs are launched)
+    up42 = lambda H, W, cin, cout, **kw: cc.route_of(ops.WF42U, H, W, cin, cout, **{'up': True, **kw})
+    assert up42(16, 16, 32, 128) == ('w42_up', 'sub-pixel phases') and not ops.f43_up_ok(32, 128, 32, 32)
+    assert up42(16, 16, 32, 128, up=False) is None and up42(16, 16, 48, 128) is None and up42(16, 16, 32, 64) is None and up42(16, 24, 32, 128) is None
+    assert up42(8, 16, 32, 128) is None and up42(16, 16, 64, 128, c_split=32) is None and up42(16, 16, 128, 128, split_k=1) is None and up42(16, 16, 544, 128) is None
 
 
 def test_the_library_accepts_every_launch_of_the_table(cc):
@@ -303,7 +327,89 @@ def test_the_library_accepts_every_launch_of_the_table(cc):
             operand, wino = (int(ops._WINO[code][4]), int(ops._WINO[code][5])) if code in ops._WINO else (ops.OPERAND_F16X2 if code == ops.SPLIT else 0, 0)
             cp = max(64, ops._cout_pad(cout)) if (code == 0 and up) else ops._cout_pad(cout) if code == 0 else cout
             c0 = cin if cs is None else cs
-            d = lib.ConvDesc(**D(H, W, c0, cout, cp, upsample=int(up), bf16_mfma=operand, batch=B, stats_cpg=0, c1=cin - c0, winograd=wino, acc_scale=1.0, split_k=sk,
-                                 in0=ctypes.addressof(dummy), in1=ctypes.addressof(dummy) if cin - c0 else None))
+            fields = D(H, W, c0, cout, cp, upsample=int(up), bf16_mfma=operand, batch=B, stats_cpg=0, c1=cin - c0, winograd=wino, acc_scale=1.0, split_k=sk,
+                       in0=ctypes.addressof(dummy), in1=ctypes.addressof(dummy) if cin - c0 else None)
+            if code == ops.WF42U:
+                fields['upsample'] = 2            # (what ops.conv2d enters for this packing: the sub-pixel phases; the output stays twice the input)
+            d = lib.ConvDesc(**fields)
             got = native.cf_conv2d_stats_parts(ctypes.byref(d))
             assert got > 0, (key, cname, sk, route, lib.last_error())
+            assert code != ops.WF42U or got == 4 * (H // 16) * (W // 16)      # one workgroup per phase and 16x16 input block
+
+
+# ---- the sub-pixel F(4,2) form (w42_up) -------------------------------------------------------------------------------------------------------------
+W42_FAMILIES = tuple(f for f in GATE_FAMILIES + SOLO_FAMILIES if f not in PROLOGUE_ONLY) + ('onehot_pixels',)
+OLD_X = {'a': '92582c1860532c58', 'b': '247dff1910251f45', 'c': 'd9de3fb100fab667', 'd': '3acc8fffa4c2da42', 'e': '7b7c0985824c2d86', 'f': 'e5678036f11c7a23',
+         'g': '377c9f00e12e59b2', 'u1': 'bf66bd9fba02b991', 'u2': '3c1397b9212ba5fc', 'zk1': '126bce5b0f6f9209', 'zk2': '9505c16f12c2f75b',
+         'zk3': '57d428bd35acd34c', 'zk4': 'fa82475c09373db7', 'zk5': '5e2c471f9338ab85'}
+
+
+def test_every_older_key_keeps_its_data(cc):
+    """family() seeds by the sorted position of a key.  sha256 of family('mixed_cout', key)['x'] (the seeded draw itself), taken before zu1 / zu2
+    existed: the checker's nine keys with the new ones behind them, and the zk* keys as tests/test_gpu_wf43_kparts.py appends them."""
+    import hashlib
+    from test_gpu_wf43_kparts import KSHAPES
+    digest = lambda m, k: hashlib.sha256(m.family('mixed_cout', k)['x'].numpy().tobytes()).hexdigest()[:16]
+    got = {k: digest(cc, k) for k in ALL_KEYS[:9]}
+    plain = load_script('tools/conv_check.py')                  # as the K-part test loads it
+    assert tuple(plain.SHAPES) == ALL_KEYS[:9] and min(KSHAPES) > max(plain.SHAPES) and min(plain.UP_SHAPES) > max(KSHAPES)
+    plain.SHAPES.update(KSHAPES)
+    got.update({k: digest(plain, k) for k in KSHAPES})
+    print(got)
+    assert got == OLD_X
+
+
+def test_f42_evaluation_is_the_convolution_and_its_weights_are_the_packer_s(cc):
+    """fp64 through wino42 == conv_case.reference(upsample=True) at every w42_up shape: the tiling, the phases and the interleave (the algebra on
+    windows is pinned by tests/test_f42_transforms.py).  S is never below the folded direct sum and never above 4556.25 sum_c max|g_p,c| max|p_c|."""
+    from codeformer_amd import ops
+    for key in W42_KEYS:
+        for fam in W42_FAMILIES + ('int_coded',):
+            d, ref = cc.prepared(fam, key)
+            assert d['pro'] == cc.PRO_NONE and d['epi'] == cc.EPI_NONE and d['up']
+            want = cc.case_ref(d)
+            S = cc._abs_eval(fam, key, 0, cc.F42)[0]
+            y, _ = cc.wino42(d['x'].double(), d['w'])
+            err = float(((y + d['b'].double() - want).abs() / (S + 1e-300)).max())
+            assert tuple(y.shape) == tuple(want.shape) and err <= 1e-13, (fam, key, err)
+            x = d['x'].double().abs()
+            xp = torch.nn.functional.pad(x.permute(0, 3, 1, 2), (1, 1, 1, 1))
+            H, W = x.shape[1:3]
+            gmax = torch.zeros(d['w'].shape[:2], dtype=torch.float64)
+            for p in range(4):
+                a, b = p >> 1, p & 1
+                g = ops.fold_phase_taps(d['w'].double(), a, b).abs()
+                direct = torch.nn.functional.conv2d(xp[:, :, a:a + H + 1, b:b + W + 1], g).permute(0, 2, 3, 1)
+                assert bool((S[:, a::2, b::2] >= direct * (1 - 1e-12)).all()), (fam, key, p)
+                gmax = torch.maximum(gmax, g.amax((2, 3)))
+            win = xp.unfold(2, 6, 4).unfold(3, 6, 4).amax((4, 5))                # (B, C, H / 4, W / 4): the union of a tile's four phase windows
+            T = torch.einsum('bcyx,kc->byxk', win, gmax).repeat_interleave(8, 1).repeat_interleave(8, 2)
+            assert bool((S <= (10.125 * 4 / 3 * 5) ** 2 * T * (1 + 1e-12)).all()), (fam, key, float((S / T.clamp_min(1e-300)).max()))
+        w = cc.family('mixed_cout', key)['w']
+        BT, G, AT = cc.mats(cc.F42)
+        mine = torch.stack([torch.einsum('ia,kcab,jb->kcij', G, ops.fold_phase_taps(w.double(), p >> 1, p & 1), G) for p in range(4)])
+        assert torch.equal(mine, ops.f42_weights(w))
+        assert [float(m.abs().sum(1).max()) for m in (AT, G, BT)] == [10.125, 12 / 9, 5.0]
+
+
+@pytest.mark.parametrize('key', W42_KEYS)
+def test_f42_edits_exceed_the_gate_and_the_unedited_emulation_does_not(cc, key):
+    """Two subtly wrong kernels, as edits of the emulation: (a) phase (a, b) multiplied with the taps folded for (b, a); (b) the products of one
+    transform-domain position lost to the idle accumulator -- position 12, the thirteenth of the lower wave half, or position 24, the last of the upper.
+    Each stands at >= 10 times the gate on some family at every shape; unedited, every family stays within half."""
+    from codeformer_amd import ops
+    route, code = 'w42_up', ops.WF42U
+    edits = {'swapped fold': dict(fold=cc.swapped_fold), 'position 12 lost': dict(zero_positions=cc.IDLE_LOWER), 'position 24 lost': dict(zero_positions=cc.IDLE_UPPER)}
+    worst = {name: (0.0, None) for name in edits}
+    for fam in W42_FAMILIES:
+        d, ref = cc.prepared(fam, key)
+        tol = cc.gate(fam, key, route, code)
+        r0, _ = cc.emulated(fam, key, route, code)
+        assert r0 <= 0.5 and cc.bits_equal(cc.emulate(d, route, code), cc.emulate(d, route, code, fold=lambda a, b: (a, b), zero_positions=())), (fam, key, r0)
+        for name, kw in edits.items():
+            r, _ = cc.ratio(cc.emulate(d, route, code, **kw), ref, tol)
+            print(f'{fam} {key} w42_up: {name} {r:.1f} of the gate (unedited {r0:.4f})')
+            worst[name] = max(worst[name], (r, fam))
+    for name, (r, fam) in worst.items():
+        print(f'{key}: {name} is seen best by {fam}, {r:.1f} of the gate')
+        assert r >= 10.0, (key, name, fam, r)

@@ -3,22 +3,23 @@
 The families, the fp64 reference, the routes, the per-element gate with its derivation and the CPU emulation live in tools/conv_check.py;
 tests/test_conv_families_host.py proves on the CPU that the emulation stays within 0.5 of the gate and that the exactness preconditions hold, so every
 condition here is a condition on the reference.  Weights are packed with the explicit code; conv_check.routes() says which code and shape reaches
-which kernel form (d32, dsplit, w23_f32, w23_h4, w23_h8, w43_8, w43_16k32, w43_16k16, w43_up), and the union of the cases below reaches all nine.
+which kernel form (d32, dsplit, w23_f32, w23_h4, w23_h8, w43_8, w43_16k32, w43_16k16, w43_up, w42_up), and the union of the cases below reaches all ten.
 Nothing is larger than 48x48 pixels, batch 3 or 512 channels.
 
-Measured on an MI355X, the whole file 13.8 s (109 cases; no case above 0.5 s, the slowest 0.46 s: solo_cin_act on dsplit).  Largest |error| / gate per family
+Measured on an MI355X, the whole file 16.9 s (125 cases; the slowest 1.2 s: tap_shift at zu1, nine taps on four routes, then 0.9 s: solo_cin_act on dsplit) against 13.0 s
+of the 109 cases before the w42_up route and its shapes zu1 / zu2, in the same session: 3.9 s for all that the sub-pixel form adds.  Largest |error| / gate per family
 and route, kernel | CPU emulation (test_family_within_the_gate prints every single ratio; onehot_pixels: the kernel's, d32 being the folded form):
-                          d32             dsplit          w23_f32         w23_h4          w23_h8          w43_8           w43_16k32       w43_16k16       w43_up
-    mixed_cout            0.0301 | 0.0246 0.1806 | 0.2101 0.0094 | 0.0101 0.1301 | 0.1301 0.0795 | 0.0795 0.1338 | 0.1338 0.0728 | 0.0728 0.0751 | 0.0751 0.0058 | 0.0064
-    mixed_cin             0.0573 | 0.0174 0.0056 | 0.0038 0.0181 | 0.0176 0.0112 | 0.0109 0.0852 | 0.0852 0.0119 | 0.0115 0.0043 | 0.0038 0.0084 | 0.0088 -
-    mixed_cin_act         0.0656 | 0.0169 0.0061 | 0.0047 0.0172 | 0.0167 0.0128 | 0.0097 0.0884 | 0.0884 0.0111 | 0.0102 0.0038 | 0.0033 0.0061 | 0.0057 0.0075 | 0.0079
-    cancel_pairs          0.0021 | 0.0044 0.0011 | 0.0009 0.0037 | 0.0039 0.0033 | 0.0034 0.0223 | 0.0223 0.0024 | 0.0030 0.0006 | 0.0005 0.0011 | 0.0011 0.0012 | 0.0014
-    dc_plus_ripple        0.0109 | 0.0097 0.0015 | 0.0018 0.0043 | 0.0031 0.0015 | 0.0019 0.0082 | 0.0082 0.0022 | 0.0020 0.0011 | 0.0011 0.0013 | 0.0013 0.0017 | 0.0016
-    swish_leaky_edges     0.4295 | 0.4295 0.2952 | 0.2952 0.3366 | 0.3366 0.2981 | 0.2981 0.2063 | 0.2063 0.2390 | 0.2390 0.1767 | 0.1767 0.2089 | 0.2089 -
-    swish_leaky_edges_sft 0.2921 | 0.4235 0.2462 | 0.4148 0.2887 | 0.4238 0.2414 | 0.4038 0.2459 | 0.4160 0.2415 | 0.4018 0.2445 | 0.4108 0.2460 | 0.4119 -
-    solo_cin              0.3338 | 0.3738 0.4544 | 0.4544 0.1214 | 0.1409 0.3117 | 0.3117 0.2653 | 0.2653 0.2746 | 0.2746 0.2612 | 0.2612 0.2693 | 0.2694 -
-    solo_cin_act          0.4258 | 0.4258 0.4937 | 0.4937 0.1463 | 0.1352 0.2570 | 0.2570 0.2906 | 0.2906 0.2696 | 0.2696 0.2474 | 0.2474 0.2545 | 0.2545 0.0356 | 0.0314
-    onehot_pixels         0.3916          0.3964          0.4667          0.4278          0.4920          0.3518          0.3503          0.2761          0.2917
+                          d32             dsplit          w23_f32         w23_h4          w23_h8          w43_8           w43_16k32       w43_16k16       w43_up          w42_up
+    mixed_cout            0.0301 | 0.0246 0.1806 | 0.2101 0.0094 | 0.0101 0.1301 | 0.1301 0.0795 | 0.0795 0.1338 | 0.1338 0.0728 | 0.0728 0.0751 | 0.0751 0.0058 | 0.0064 0.0066 | 0.0068
+    mixed_cin             0.0573 | 0.0174 0.0056 | 0.0038 0.0181 | 0.0176 0.0112 | 0.0109 0.0852 | 0.0852 0.0119 | 0.0115 0.0043 | 0.0038 0.0084 | 0.0088 -               -
+    mixed_cin_act         0.0656 | 0.0169 0.0061 | 0.0047 0.0172 | 0.0167 0.0128 | 0.0097 0.0884 | 0.0884 0.0111 | 0.0102 0.0038 | 0.0033 0.0061 | 0.0057 0.0075 | 0.0079 0.0116 | 0.0098
+    cancel_pairs          0.0021 | 0.0044 0.0011 | 0.0009 0.0037 | 0.0039 0.0033 | 0.0034 0.0223 | 0.0223 0.0024 | 0.0030 0.0006 | 0.0005 0.0011 | 0.0011 0.0012 | 0.0014 0.0021 | 0.0021
+    dc_plus_ripple        0.0109 | 0.0097 0.0015 | 0.0018 0.0043 | 0.0031 0.0015 | 0.0019 0.0082 | 0.0082 0.0022 | 0.0020 0.0011 | 0.0011 0.0013 | 0.0013 0.0017 | 0.0016 0.0021 | 0.0018
+    swish_leaky_edges     0.4295 | 0.4295 0.2952 | 0.2952 0.3366 | 0.3366 0.2981 | 0.2981 0.2063 | 0.2063 0.2390 | 0.2390 0.1767 | 0.1767 0.2089 | 0.2089 -               -
+    swish_leaky_edges_sft 0.2921 | 0.4235 0.2462 | 0.4148 0.2887 | 0.4238 0.2414 | 0.4038 0.2459 | 0.4160 0.2415 | 0.4018 0.2445 | 0.4108 0.2460 | 0.4119 -               -
+    solo_cin              0.3338 | 0.3738 0.4544 | 0.4544 0.1214 | 0.1409 0.3117 | 0.3117 0.2653 | 0.2653 0.2746 | 0.2746 0.2612 | 0.2612 0.2693 | 0.2694 -               -
+    solo_cin_act          0.4258 | 0.4258 0.4991 | 0.4990 0.1463 | 0.1352 0.2570 | 0.2570 0.2906 | 0.2906 0.2696 | 0.2696 0.2474 | 0.2474 0.2545 | 0.2545 0.0378 | 0.0406 0.0623 | 0.0803
+    onehot_pixels         0.4026          0.3964          0.4667          0.4278          0.4920          0.3518          0.3503          0.2761          0.4161          0.4039
 (equal pairs: the worst element is one whose error is a single rounding both evaluations make alike -- the residual add of swish_leaky_edges, the half
 rounding of a small channel's U in mixed_cout, the half rounding of a subnormal activation half in the solo families, whose gate enters it at the whole
 spacing; the w23_h8 column is its bf16 form, whose gate is the operand format's 2^-8.  The swish / leaky families sit at
@@ -27,6 +28,13 @@ Read the equal cells as what they are: they exercise the epilogue add (swish_lea
 columns of mixed_cout), NOT the MFMA accumulation, and meet the >= 1e-3 condition trivially; the evidence on the accumulation path is in the cells that differ,
 in int_coded, tap_shift and onehot_pixels.)
 The kernels needed no change: every exact, impulse, gate, bitwise and containment condition held on the first run.
+The w42_up column (ops.WF42U at u1, zu1, zu2: 1, 3 and 8 slabs; per shape, kernel | emulation: mixed_cout 0.0066 | 0.0068, 0.0037 | 0.0037, 0.0011 | 0.0008;
+mixed_cin_act 0.0116 | 0.0098, 0.0033 | 0.0033, 0.0008 | 0.0007; cancel_pairs 0.0021 | 0.0021, 0.0005 | 0.0005, 0.0001 | 0.0001; dc_plus_ripple 0.0021 | 0.0018,
+0.0008 | 0.0010, 0.0004 | 0.0002; solo_cin_act 0.0623 | 0.0605, 0.0615 | 0.0803, 0.0581 | 0.0505; onehot_pixels 0.2375, 0.4039, 0.2113) was measured when the route was added:
+the kernel stands where the float32 emulation of its own pipeline stands at every shape, and needed no change either.  Its dense cells are small because
+c = cin + 15 counts a whole u S per channel of the chain; what holds the form to its arithmetic are the one-term sums (solo_cin_act, onehot_pixels, tap_shift)
+and the two edits of the emulation that tests/test_conv_families_host.py shows at 2 x 10^5 .. 5 x 10^7 times the gate of the family that sees each best (cancel_pairs at cin 256 sees them at 2 times its gate only).  The older columns changed where zu1 / zu2
+now reach them too (solo_cin_act on dsplit and w43_up, onehot_pixels on d32 and w43_up).
 
 Scratch builds with one in-range edit each (not committed; addresses, barriers and launch geometry untouched), tests of this file that fail | of the
 eight 3x3 tests of test_gpu_split.py that were run against each build (split_conv_against_fp64, split_conv_is_bitwise.., splitk_winograd.., winograd_single.., the four winograd_f43..):
@@ -74,11 +82,13 @@ from _tools import load_script
 
 pytestmark = pytest.mark.gpu
 
-ROUTES = ('d32', 'dsplit', 'w23_f32', 'w23_h4', 'w23_h8', 'w43_8', 'w43_16k32', 'w43_16k16', 'w43_up')
+ROUTES = ('d32', 'dsplit', 'w23_f32', 'w23_h4', 'w23_h8', 'w43_8', 'w43_16k32', 'w43_16k16', 'w43_up', 'w42_up')
+UP_ROUTES = ('w43_up', 'w42_up')                  # prologue none, no epilogue operand, one input
 GATE_FAMILIES = ('mixed_cout', 'mixed_cin', 'mixed_cin_act', 'cancel_pairs', 'dc_plus_ripple', 'swish_leaky_edges', 'swish_leaky_edges_sft')
 SOLO_FAMILIES = ('solo_cin', 'solo_cin_act')      # one input channel per output channel, under conv_check's solo gate
 PROLOGUE_ONLY = ('mixed_cin', 'swish_leaky_edges', 'swish_leaky_edges_sft', 'solo_cin')       # families that ARE their prologue: the upsampling forms take none
-SHAPE_KEYS = ('a', 'b', 'c', 'd', 'e', 'f', 'g', 'u1', 'u2')
+SHAPE_KEYS = ('a', 'b', 'c', 'd', 'e', 'f', 'g', 'u1', 'u2', 'zu1', 'zu2')
+W42_KEYS = ('u1', 'zu1', 'zu2')                   # the shapes of the sub-pixel F(4,2) form: 1, 3 and 8 slabs; one block per phase, 2 x 3 blocks, one block
 
 
 @pytest.fixture(scope='module')
@@ -88,6 +98,7 @@ def cc():
     from codeformer_amd import lib
     lib.load()
     m = load_script('tools/conv_check.py')
+    m.with_f42()
     assert m.ROUTES == ROUTES and m.GATE_FAMILIES == GATE_FAMILIES and m.SOLO_FAMILIES == SOLO_FAMILIES and tuple(m.SHAPES) == SHAPE_KEYS
     return m
 
@@ -98,7 +109,8 @@ def test_the_cases_reach_every_route(cc):
     forms = {(r, f) for key in SHAPE_KEYS for _, _, _, r, f in cc.launches(key)}
     assert {('d32', '256x64'), ('d32', '128x128'), ('d32', 'narrow 128x64'), ('d32', 'folded 256x64'), ('d32', 'folded narrow 128x64'), ('dsplit', 'form 0 64-wide'),
             ('dsplit', 'form 1 64-wide'), ('w23_f32', 'split-K 1'), ('w23_f32', 'split-K 2'), ('w23_f32', 'split-K 4'), ('w23_h4', 'split-K 4'), ('w23_h8', 'f16x2'),
-            ('w23_h8', 'f16'), ('w23_h8', 'bf16'), ('w43_8', 'ntn 3'), ('w43_up', 'k32 gather')} <= forms
+            ('w23_h8', 'f16'), ('w23_h8', 'bf16'), ('w43_8', 'ntn 3'), ('w43_up', 'k32 gather'), ('w42_up', 'sub-pixel phases')} <= forms
+    assert tuple(key for key in SHAPE_KEYS if any(r == 'w42_up' for _, _, _, r, _ in cc.launches(key))) == W42_KEYS
 
 
 # ---- 1. the exact family ---------------------------------------------------------------------------------------------------------------------
@@ -122,7 +134,7 @@ def test_int_coded_is_the_fp64_result_bitwise(cc, key):
 
 
 # ---- 2. the impulse families -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('key', ('a', 'b', 'c', 'd', 'g', 'u1'))
+@pytest.mark.parametrize('key', ('a', 'b', 'c', 'd', 'g', 'u1', 'zu1', 'zu2'))
 def test_onehot_pixels_select_the_flipped_weight(cc, key):
     """out = the flipped weight slice + bias around each pixel, the bias elsewhere: d32 bitwise fp32(w + b); every other route within the gate."""
     import torch
@@ -142,7 +154,7 @@ def test_onehot_pixels_select_the_flipped_weight(cc, key):
             assert r <= 1.0, (key, route, cname, form, r, err)
 
 
-@pytest.mark.parametrize('key', ('b', 'c', 'd', 'u1'))
+@pytest.mark.parametrize('key', ('b', 'c', 'd', 'u1', 'zu1', 'zu2'))
 def test_tap_shift_moves_the_input_and_pads_each_border_with_zeros(cc, key):
     """Per tap a signed channel permutation: the input moved by one pixel.  d32 bitwise; dsplit within the 22-bit split of x (and the absolute 2^-25 / s of
     a subnormal lo half); the Winograd routes within the gate."""
@@ -166,7 +178,7 @@ def test_tap_shift_moves_the_input_and_pads_each_border_with_zeros(cc, key):
 
 
 # ---- 3. the gate families --------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('family,route', [(f, r) for f in GATE_FAMILIES + SOLO_FAMILIES for r in ROUTES if not (r == 'w43_up' and f in PROLOGUE_ONLY)])
+@pytest.mark.parametrize('family,route', [(f, r) for f in GATE_FAMILIES + SOLO_FAMILIES for r in ROUTES if not (r in UP_ROUTES and f in PROLOGUE_ONLY)])
 def test_family_within_the_gate(cc, family, route):
     """The per-element gate on every shape, code and split count that reaches the route; the measured / gate ratio is printed, may not exceed 1 and may
     not fall below 1e-3 of the emulation's (a gate that loose would check nothing)."""
@@ -216,7 +228,7 @@ def test_every_split_count_gives_the_same_bits(cc, family):
 def test_an_image_alone_equals_the_image_inside_a_batch_of_three(cc, family):
     import torch
     reached = set()
-    for key in ('b', 'c', 'd', 'e', 'g', 'u1', 'u2'):
+    for key in ('b', 'c', 'd', 'e', 'g', 'u1', 'u2', 'zu1', 'zu2'):
         d, _ = cc.prepared(family, key)
         x0 = d['x'][:1]
         first = lambda t: t[:1].expand(3, *t.shape[1:]).contiguous()
@@ -247,7 +259,7 @@ def test_a_concatenated_input_equals_the_dense_tensor(cc, family):
                 y = cc.run(d, code, sk, (family, key), c_split=c)
                 assert cc.bits_equal(y, dense), (family, key, route, cname, form, c, int((y != dense).sum()))
             reached.add(route)
-    assert reached == set(ROUTES) - {'w43_up'}            # (the upsampling gather takes one input)
+    assert reached == set(ROUTES) - set(UP_ROUTES)        # (the upsampling forms take one input)
 
 
 def _allowed(route, pixels, H, W):
@@ -265,12 +277,28 @@ def _allowed(route, pixels, H, W):
     return ok
 
 
-@pytest.mark.parametrize('key', ('b', 'c', 'd', 'u1'))
+def _allowed42(r, q, H, W):
+    """Sub-pixel F(4,2) phases, (H, W) and the pixel (r, q) on the LOW-RESOLUTION grid: phase (a, b) of tile (t, v) reads the rows 4 t - 1 + a .. 4 t + 3 + a and the
+    columns 4 v - 1 + b .. 4 v + 3 + b, and writes the outputs (2 i + a, 2 j + b) of its 4x4 positions.  -> (2 H, 2 W) bool."""
+    import torch
+    ok = torch.zeros(2 * H, 2 * W, dtype=torch.bool)
+    for a in (0, 1):
+        for b in (0, 1):
+            for t in range(H // 4):
+                for v in range(W // 4):
+                    if 4 * t - 1 + a <= r <= 4 * t + 3 + a and 4 * v - 1 + b <= q <= 4 * v + 3 + b:
+                        ok[8 * t + a:8 * t + 8:2, 8 * v + b:8 * v + 8:2] = True
+    return ok
+
+
+@pytest.mark.parametrize('key', ('b', 'c', 'd', 'u1', 'zu1', 'zu2'))
 def test_a_non_finite_pixel_stays_inside_the_tiles_that_read_it(cc, key):
     """One NaN, then one +inf, in a single input pixel and channel, at a patch interior, at pixels whose 3x3 reach crosses the corner of an 8x16 and of a
     16x16 patch, at pixel (0, 0) of the FIRST image (the address every clamped out-of-image load reads) and in the last row.  Affine prologue with sc = 1, sh = 0: no range scale reads the tensor (the upsampling gather
     takes no prologue and has fp32 operands: no range scale either).  Outside the allowed set every output bit equals the clean run; inside the true
-    3x3 neighbourhood every output channel is non-finite (the weights are dense, non-zero).  No statistics partials are read."""
+    3x3 neighbourhood every output channel is non-finite (the weights are dense, non-zero).  No statistics partials are read.
+    w42_up: a low-resolution pixel is read by the 4x4 low-resolution tiles whose 5x5 window, moved by the phase, holds it, in all four phases: the allowed
+    set is those tiles' outputs (2 i + a, 2 j + b), phase by phase -- within the 2x-scaled footprint of the tiles (_allowed42)."""
     import torch
     B, H, W, cin, cout, _, up = cc.SHAPES[key]
     Ho, Wo = (2 * H, 2 * W) if up else (H, W)
@@ -279,7 +307,7 @@ def test_a_non_finite_pixel_stays_inside_the_tiles_that_read_it(cc, key):
     affine = dict(base, pro=cc.PRO_AFFINE, sc=torch.ones_like(base['sc']), sh=torch.zeros_like(base['sh']))
     spots = [(4, 5), (7, 15), (15, 15), (0, 0), (H - 1, 9)]
     for cname, code, sk, route, form in cc.launches(key):
-        d = base if route == 'w43_up' else affine
+        d = base if route in UP_ROUTES else affine
         clean = cc.run(d, code, sk, ('cancel_pairs', key))
         assert bool(torch.isfinite(clean).all())
         for val in (float('nan'), float('inf')):
@@ -289,7 +317,8 @@ def test_a_non_finite_pixel_stays_inside_the_tiles_that_read_it(cc, key):
                 x[bi, r, q, (7 * i + 3) % cin] = val
                 y = cc.run(d, code, sk, ('cancel_pairs', key), x=x)
                 pixels = [(2 * r + a, 2 * q + b) for a in (0, 1) for b in (0, 1)] if up else [(r, q)]
-                ok = _allowed(route, pixels, Ho, Wo).cuda()
+                ok = (_allowed42(r, q, H, W) if route == 'w42_up' else _allowed(route, pixels, Ho, Wo)).cuda()
+                assert route != 'w42_up' or (int(ok.sum()) <= 4 * 64 and bool(ok[2 * r:2 * r + 2, 2 * q:2 * q + 2].all()))     # (at most four tiles' footprints)
                 same = (y.view(torch.int32) == clean.view(torch.int32)).all(dim=3)
                 others = [b for b in range(B) if b != bi]
                 assert bool(same[others].all()) and bool(same[bi][~ok].all()), (key, route, cname, form, val, (r, q), int((~same[bi][~ok]).sum()))
@@ -297,3 +326,16 @@ def test_a_non_finite_pixel_stays_inside_the_tiles_that_read_it(cc, key):
                 for pr, pq in pixels:
                     near[max(pr - 1, 0):pr + 2, max(pq - 1, 0):pq + 2] = True
                 assert bool((~torch.isfinite(y[bi][near.cuda()])).all()), (key, route, cname, form, val, (r, q))
+
+
+@pytest.mark.parametrize('key', W42_KEYS)
+def test_the_sub_pixel_form_repeats_its_bits(cc, key):
+    """w42_up, run to run, on the two families whose sums cancel; and the four phases are all written: no output keeps the fill of a fresh tensor."""
+    import torch
+    from codeformer_amd import ops
+    for family in ('dc_plus_ripple', 'cancel_pairs'):
+        d, ref = cc.prepared(family, key)
+        y0 = cc.run(d, ops.WF42U, 0, (family, key))
+        y1 = cc.run(d, ops.WF42U, 0, (family, key))
+        assert cc.bits_equal(y0, y1), (family, key, int((y0 != y1).sum()))
+        assert tuple(y0.shape) == tuple(ref['out'].shape) and bool(torch.isfinite(y0).all())

@@ -4,7 +4,9 @@ algebra is pinned on the CPU by tests/test_f42_transforms.py).
 Shapes: B = 2, 32x32 -> 64x64 -- four 16x16 low-resolution blocks per image, so every image border, the interior block borders and all four
 phases are in every launch (16 workgroups per image and channel tile) -- at 128 -> 128 channels (4 slabs, one channel tile) and 256 -> 256 (8
 slabs, two channel tiles).  Every output element is compared with the fp64 reference (tools/conv_case.py) under the bound
-tests/test_gpu_split.py::test_winograd_f43_fp32_upsampling_gather uses at |ref| > 4, 4e-5 max|ref| / 4.
+tests/test_gpu_split.py::test_winograd_f43_fp32_upsampling_gather uses at |ref| > 4, 4e-5 max|ref| / 4.  That is one bound for the whole tensor at the
+network's size; the per-element gate of this form (c u S + 2 u |pre|, c = cin + 15), on 1, 3 and 8 slabs, a non-square image and the mixed-scale,
+cancelling, DC + ripple and single-channel families, is the route w42_up of tools/conv_check.py, run by tests/test_gpu_conv_families.py.
 
 Impulses: a unit pixel at a corner, on an edge, on both sides of the interior block border and inside a block, each in an input channel of its
 own and routed by a one-hot tap of value 81 to an output channel of its own.  The output is then 81 on the 2 x 2 footprint ((Y + ky - 1) >> 1,

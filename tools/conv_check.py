@@ -16,7 +16,14 @@ cf_wf43_launch and cf_split_launch; weights are packed with the explicit code, n
   w43_16k32  WF43 WF43F    sixteen-wave form on 32-channel slabs (cout % 128 == 0, cin % 32 == 0, c_split % 32 == 0), cin <= 512
   w43_16k16  WF43 WF43F    sixteen-wave form on 16-channel slabs (cout % 128 == 0, cin % 32 != 0), cin <= 256
   w43_up     WF43F + upsample    the upsampling gather of the sixteen-wave form (prologue none, no epilogue operand, one input)
-Shapes (SHAPES: B, H, W of the INPUT, cin, cout, c_split, upsample): nothing above 48x48 pixels, batch 3 or 512 channels.
+  w42_up     WF42U + upsample    nearest x2 + 3x3 as four F(4x4,2x2) sub-pixel phases on the low-resolution image (cf_conv_desc.upsample == 2; what the
+                           Upsample blocks of precision 'fp32' run): fp32 operands, prologue none, no epilogue operand, one input, cin % 32 == 0 and <= 512
+                           (the 32-channel-slab form's limit; the 256 and the smallest size of ops.f43_up_ok are policy, not the form), cout % 128 == 0,
+                           whole 16x16 blocks of the INPUT.  A packing of its own: ops.pack_weight(w, b, bf16=ops.WF42U), no up2x.  Route, code and
+                           shapes enter ROUTES, CODES and SHAPES through with_f42() (the two families tests and this script's own listing call it)
+Shapes (SHAPES: B, H, W of the INPUT, cin, cout, c_split, upsample): nothing above 48x48 pixels, batch 3 or 512 channels.  UP_SHAPES (zu1: three slabs,
+32x48, two channel tiles; zu2: eight slabs on 16x16) join them through with_f42(); with u1 (one slab: fill and drain with no steady state, one
+block per phase) they are the shapes of w42_up.
 
 Families (CPU, fixed seeds; family(name, shape_key) -> dict x, w, b, sc, sh, res, ss, pro, epi, sft_w; computed once, never modified):
   int_coded      x in -3..3, w in (-3..3) 2^-5, bias / residual / SFT operands small integers, prologue none or affine with sc in {1/2, 1, 2} and
@@ -60,7 +67,8 @@ Gate, against fp64, PER ELEMENT (u = 2^-24):
   S   direct routes: sum over taps and channels of |w| |p(x)|, p = the prologue, zero outside the image.  Winograd routes: the SAME evaluation the
       kernel makes with every matrix and operand replaced by its absolute value, |A^T| [ sum_c (|G| |g| |G^T|) (.) (|B^T| |p(x)| |B|) ] |A| -- it bounds
       every partial result of the algorithm, is never below the direct S, and is at most (the squared product of the absolute row sums of A^T, G
-      and B^T) times sum_c max|g_c| max|p_c| over the tile's window (81 for F(2,3), 14581 for F(4,3): both bounds asserted by the host test).  The direct S cannot serve there: a Winograd tile's outputs read all of the tile's window, so an
+      and B^T) times sum_c max|g_c| max|p_c| over the tile's window (81 for F(2,3), 14581 for F(4,3), 4556.25 = (10.125 x 4/3 x 5)^2 for F(4,2) with g_c the
+      FOLDED 2x2 taps of the phase, themselves sums of up to four weights and the operand of that form: all three bounds asserted by the host test).  The direct S cannot serve there: a Winograd tile's outputs read all of the tile's window, so an
       element whose own 3x3 neighbourhood is empty (onehot_pixels) still carries the rounding of its neighbours' products.
   c   the number of roundings on the way of one element, each at most u times a partial result <= S (no statistical discount):
         d32      9 cin (the fp32 FMA chain over taps and channels), + 3 with folded taps (a folded weight is a sum of up to four)
@@ -70,6 +78,19 @@ Gate, against fp64, PER ELEMENT (u = 2^-24):
                  chunk additions.  Split halves: 3 cin + 12 + 7.  Single IEEE half (WF16): cin + 7 + 2 x 2^-11 / u; single bf16: cin + 7 + 2 x 2^-8 / u.
         w43      cin + 10 (B'^T d B': rows of up to four terms with the factor 17/16: five roundings per pass; absolute row sum 1.875) + 1 (U; rows
                  of G': up to 56/15) + 8 (A^T M A: five terms per row, absolute sums up to 17.25) = cin + 19; split halves 3 cin + 12 + 19
+        w42      (w42_up; S through |A42^T|, |G42| |g_p| |G42^T| with g_p the folded taps, |B42^T|: absolute row sums up to 10.125, 4/3, 5.)  Read off
+                 the kernel's arithmetic, every operation counted that can round, the worst row of each pass:
+                 cin (the fp32 MFMA chain over the slabs, one rounding per product added)
+                 + 8  B42^T d B42, bt42 of cf_wf43.hip, 4 per pass.  Rows xi 0 and 4, (d0 + d3) - (d1 + d2) 1.5: two additions, the product by 1.5 and the
+                      subtraction, four roundings (1.5 and 2.5 are not powers of two: their products round; where the compiler contracts product and
+                      subtraction into one FMA there are three -- counted as four, the bound holds either way).  Row 1, (d1 + d3) - 2.5 d2: three.
+                      Rows 2 and 3, (d3 - d2) - 2 d1 and .5 (d2 - d1) + d3: two, the products by 2 and .5 are exact.
+                 + 1  U = G42 g_p G42^T with the fold in fp64, rounded once (cf_pack.hip; ops.f42_weights): the fold adds no fp32 rounding
+                 + 6  A42^T M A42, 3 per pass; every factor (.5, 2, .25, 4, .125, 8) is a power of two, so only additions round.  xi pass (col()):
+                      m1 + ca1 m2 + ca2 m3 and (cb1 m2 + cb2 m3) - m1 two additions, + m0 (rows 0, 1) or + m4 (rows 2, 3) a third.  nu pass: (t0 + t1) +
+                      (t2 + t3) three, (.5 t2 + 2 t3) - t1 and (.25 t2 + 4 t3) + t1 two, ((.125 t2 + 8 t3) - t1) + t4 three.
+                 = cin + 15.  acc_scale is 1 with fp32 operands (an exact product); the bias addition is the epilogue's 2 u |pre|.  No prologue term,
+                 no epilogue operand, no floor.
   P   the prologue's own error taken through the same absolute evaluation as S: affine 2 u (|x sc| + |sh|); swish |swish'(y)| times that +
       (2 |y| + 8) u |swish(y)| (v_exp_f32 on y log2 e, 1 + e, v_rcp_f32, one product: whole ulps); leaky u |p|; none 0 (the range scale is a power of two)
   floor  split-half and single-half routes: IEEE half has the spacing 2^-24 below 2^-14, so a half of an operand that falls there carries an ABSOLUTE
@@ -91,7 +112,10 @@ The solo families (SOLO_FAMILIES), two changes, both consequences of the exact z
 The emulation (emulate(): torch float32 on the CPU; transforms as two passes of fp32 einsums, U from fp64 rounded once, halves split as
 gemm_check.split_halves does, three products lo hi + hi lo + hi hi, fp32 epilogue) is the condition on the gate: tests/test_conv_families_host.py asserts its
 error within 0.5 of the gate for every gate family, operand scheme and transform at every shape the GPU test uses (the folded forms are emulated on
-the upsampled image with the unfolded weight: the fold's additions are the + 3 of c).  emulate(.., act_halves=) takes an edit of the activation's
+the upsampled image with the unfolded weight: the fold's additions are the + 3 of c; w42_up is emulated as it runs, wino42() in float32 on the
+low-resolution image, and takes two edits of its own -- fold=swapped_fold, phase (a, b) given the taps folded for (b, a), and zero_positions=IDLE_LOWER /
+IDLE_UPPER, the thirteenth position of the lower wave half or the last of the upper taken for the idle accumulator -- each of which the host test shows
+at >= 10 times the gate on some family at every w42_up shape).  emulate(.., act_halves=) takes an edit of the activation's
 split: with drop_small_lo (the lo half zeroed where it is subnormal, |a| < 2^-3) the solo families' emulation exceeds their gate 25 .. 103 times at
 every shape and split-half scheme while no other family's ratio at shape b moves by 0.002 of its gate (the host test asserts >= 10 and <= 0.005).  No number here was fitted to
 what a kernel returns; the kernels' figures are in the docstring of tests/test_gpu_conv_families.py.
@@ -124,10 +148,18 @@ EPI_NONE, EPI_RESIDUAL, EPI_SFT = ops.EPI_NONE, ops.EPI_RESIDUAL, ops.EPI_SFT
 ROUTES = ('d32', 'dsplit', 'w23_f32', 'w23_h4', 'w23_h8', 'w43_8', 'w43_16k32', 'w43_16k16', 'w43_up')
 EXACT_ROUTES = ('d32', 'dsplit', 'w23_f32', 'w23_h4', 'w23_h8')
 CODES = {'F32': 0, 'SPLIT': ops.SPLIT, 'WINOGRAD': ops.WINOGRAD, 'WSPLIT': ops.WSPLIT, 'WF16': ops.WF16, 'WBF16': ops.WBF16, 'WF43': ops.WF43, 'WF43F': ops.WF43F}
+# The sub-pixel F(4,2) form joins ROUTES, CODES and SHAPES through with_f42() (as tools/conv_geom_check.py adds its NCHW ends): the module as loaded
+# keeps the nine routes, eight codes and nine shapes that its other users pin (tests/test_gpu_sft_per_image.py, tests/test_gpu_wf43_kparts.py).
+F42_ROUTE, F42_CODE = 'w42_up', 'WF42U'
 # key -> (B, H, W of the input, cin, cout, c_split, upsample)
 SHAPES = {'a': (1, 16, 16, 16, 64, None, False), 'b': (2, 16, 32, 32, 64, None, False), 'c': (2, 32, 32, 64, 128, 32, False),
           'd': (3, 32, 48, 48, 128, None, False), 'e': (1, 16, 16, 256, 64, None, False), 'f': (1, 16, 16, 512, 128, 256, False),
           'g': (1, 48, 32, 192, 192, None, False), 'u1': (2, 16, 16, 32, 128, None, True), 'u2': (1, 16, 16, 64, 64, None, True)}
+# the further upsampling shapes of the sub-pixel F(4,2) form (w42_up; u1 is its first: one slab, one block per phase, every side an image border): an odd
+# slab count (3) on a non-square image with interior block borders on both axes and two channel tiles; the slab maximum of the network (8) on the
+# smallest image.  Not in SHAPES until with_f42(): family() seeds by the sorted position of a key, and tests/test_gpu_wf43_kparts.py appends
+# its own keys behind SHAPES' -- these sort after both, so every older key keeps its data bit for bit either way.
+UP_SHAPES = {'zu1': (1, 32, 48, 96, 256, None, True), 'zu2': (1, 16, 16, 256, 128, None, True)}
 GATE_FAMILIES = ('mixed_cout', 'mixed_cin', 'mixed_cin_act', 'cancel_pairs', 'dc_plus_ripple', 'swish_leaky_edges', 'swish_leaky_edges_sft')
 # one input channel per output channel: gate families too, under a gate that counts and sums the channels that HAVE a product.  A tuple of their own:
 # GATE_FAMILIES is the list of the dense families, which tests and tools/conv_geom_check.py pin as it is
@@ -146,9 +178,23 @@ G4 = [[4, 0, 0], [-32 / 15, -16 / 15, -8 / 15], [-32 / 15, 16 / 15, -8 / 15], [1
 AT4 = [[1, 1, 1, 1, 1, 0], [0, .5, -.5, 2, -2, 0], [0, .25, .25, 4, 4, 0], [0, .125, -.125, 8, -8, 1]]
 
 
+F42 = 42       # the transform tag of F(4x4,2x2) on the sub-pixel phases (scheme_of); its matrices are ops.B42T, ops.G42, ops.A42T
+
+
 def mats(m, dtype=torch.float64):
-    """(B^T, G, A^T) of F(m x m, 3x3), m = 2 | 4."""
-    return tuple(torch.tensor(t, dtype=dtype) for t in ((BT2, G2, AT2) if m == 2 else (BT4, G4, AT4)))
+    """(B^T, G, A^T) of F(m x m, 3x3), m = 2 | 4, or of F(4x4, 2x2), m = F42."""
+    return tuple(torch.tensor(t, dtype=dtype) for t in ((BT2, G2, AT2) if m == 2 else (ops.B42T, ops.G42, ops.A42T) if m == F42 else (BT4, G4, AT4)))
+
+
+def with_f42():
+    """ROUTES, CODES and SHAPES of this module object with the sub-pixel F(4,2) form in them: the route w42_up, the code WF42U, and UP_SHAPES behind
+    the older keys (idempotent)."""
+    global ROUTES
+    assert min(UP_SHAPES) > max(k for k in SHAPES if k not in UP_SHAPES)
+    SHAPES.update(UP_SHAPES)
+    CODES[F42_CODE] = ops.WF42U
+    if F42_ROUTE not in ROUTES:
+        ROUTES = ROUTES + (F42_ROUTE,)
 
 
 # ---- routes ----------------------------------------------------------------------------------------------------------------------------------
@@ -182,6 +228,11 @@ def route_of(code, H, W, cin, cout, up=False, split_k=0, c_split=None):
         if not split_k and cout % 128 == 0 and px >= 1024:
             return 'w23_h8', {ops.WSPLIT: 'f16x2', ops.WF16: 'f16', ops.WBF16: 'bf16'}[code]
         return ('w23_h4', sk) if code == ops.WSPLIT else None
+    if code == ops.WF42U:                                                # cf_wf43_launch, cf_conv_desc.upsample == 2 (the packer: whole 32-channel slabs, 128 output channels)
+        # fp32 operands, one input, cf_wf43_k32 (cout % 128 == 0, cin % 32 == 0), whole 16x16 blocks of the INPUT, no split_k; the channel limit is the
+        # 32-channel-slab form's own (F4_TAB_32 = 512 -- the 256 of ops.f43_up_ok is policy, as is its smallest size)
+        ok = up and not split_k and c_split is None and cin % 32 == 0 and cin <= 512 and cout % 128 == 0 and H % 16 == 0 and W % 16 == 0
+        return ('w42_up', 'sub-pixel phases') if ok else None
     if code in (ops.WF43, ops.WF43F):                                    # cf_wf43_launch
         if split_k or cin % 16 or c0 % 16 or cout % 64 or Ho % 16 or Wo % 16:
             return None
@@ -211,9 +262,9 @@ def routes():
 
 
 def scheme_of(route, code):
-    """(transform 0 | 2 | 4, operands 'f32' | 'half2' | 'half' | 'bf16')."""
-    m = 0 if route in ('d32', 'dsplit') else 2 if route.startswith('w23') else 4
-    op = {0: 'f32', ops.WINOGRAD: 'f32', ops.WF43F: 'f32', ops.WF16: 'half', ops.WBF16: 'bf16'}.get(code, 'half2')
+    """(transform 0 | 2 | 4 | F42, operands 'f32' | 'half2' | 'half' | 'bf16')."""
+    m = 0 if route in ('d32', 'dsplit') else 2 if route.startswith('w23') else F42 if route == 'w42_up' else 4
+    op = {0: 'f32', ops.WINOGRAD: 'f32', ops.WF43F: 'f32', ops.WF42U: 'f32', ops.WF16: 'half', ops.WBF16: 'bf16'}.get(code, 'half2')
     return m, op
 
 
@@ -383,6 +434,8 @@ def wino(p, w, m, dtype=torch.float64, absolute=False, products=None):
     V = B^T d B in two passes, U = G g G^T in fp64 rounded to `dtype`, the products over the channels per position, Y = A^T M A in two passes.
     absolute: every matrix and operand by its absolute value.  products(V, U) -> M replaces the channel contraction (the operand schemes).
     -> (Y (B, H, W, cout), sum_c |V| and sum_c |U| taken through |A^T| . |A| (absolute only))."""
+    if m == F42:          # (p is the conv's input, the upsampled image: its even pixels are the low-resolution one)
+        return wino42(p[:, ::2, ::2], w, dtype, absolute, products)
     BT, G, AT = mats(m)
     n = m + 2
     B, H, W, C = p.shape
@@ -409,6 +462,63 @@ def wino(p, w, m, dtype=torch.float64, absolute=False, products=None):
     fv = back(Vm.sum(2, keepdim=True).reshape(n, n, B, th, tw, 1))
     fu = back(Um.sum(1)[:, None, :].expand(-1, B * th * tw, -1).reshape(n, n, B, th, tw, -1))
     return back(M), (fv, fu)
+
+
+def swapped_fold(a, b):
+    """An edit of wino42 / emulate: phase (a, b) multiplied with the weights folded for phase (b, a) -- pa / pb exchanged in the weight only."""
+    return b, a
+
+
+# The other edit: one transform-domain position's products taken as zero.  The M interval of the kernel splits a phase's 25 positions 13 / 12 over two
+# wave halves, and the upper half's thirteenth accumulator is idle; taking the wrong accumulator for the idle one loses position 12 (the thirteenth of
+# the lower half) or position 24 (the twelfth, last, of the upper half).
+IDLE_LOWER, IDLE_UPPER = (12,), (24,)
+
+
+def wino42(x, w, dtype=torch.float64, absolute=False, products=None, fold=None, zero_positions=()):
+    """nearest-x2 + 3x3 (zero padding) of the LOW-RESOLUTION NHWC tensor x with the weight w (cout, cin, 3, 3), evaluated as the UP form of cf_wf43.hip
+    does: per output parity p = 2 a + b the folded 2x2 taps g_p (ops.fold_phase_taps, fp64), U = G42 g_p G42^T in fp64 rounded once to `dtype`
+    (ops.f42_weights: the fold adds no fp32 rounding), V = B42^T d B42 in two passes on the 5x5 windows of the image padded by one pixel and moved by
+    the phase (window of tile t: rows 4 t - 1 + a .. 4 t + 3 + a), the products over the channels per position, Y = A42^T M A42 in two passes, the
+    4x4 outputs of a tile at (2 i + a, 2 j + b).  absolute / products: as wino().  fold(a, b) -> the parity whose taps phase (a, b) is given;
+    zero_positions: positions xi * 5 + nu whose M is taken as zero (two edits for the host test that shows the gate notices them).
+    -> (Y (B, 2 H, 2 W, cout), sum_c |V| and sum_c |U| taken through |A42^T| . |A42| (absolute only))."""
+    BT, G, AT = mats(F42)
+    B, H, W, C = x.shape
+    N = w.shape[0]
+    if absolute:
+        BT, G, AT, x = BT.abs(), G.abs(), AT.abs(), x.abs()
+    xp = F.pad(x.permute(0, 3, 1, 2), (1, 1, 1, 1))
+    Bt = BT.to(dtype)
+    th, tw = H // 4, W // 4
+    out = [None, None, None]
+    for ph in range(4):
+        a, b = ph >> 1, ph & 1
+        g = ops.fold_phase_taps(w.double(), *((a, b) if fold is None else fold(a, b)))      # (cout, cin, 2, 2), fp64: the operand of this phase
+        d = xp[:, :, a:a + H + 1, b:b + W + 1].unfold(2, 5, 4).unfold(3, 5, 4)            # (B, C, th, tw, 5, 5)
+        V = torch.einsum('ia,bcyxaj->bcyxij', Bt, d.to(dtype))                            # column pass
+        V = torch.einsum('bcyxia,ja->bcyxij', V, Bt)                                      # row pass
+        Uw = torch.einsum('ia,kcab,jb->ijck', G, g.abs() if absolute else g, G).to(dtype)  # (5, 5, C, N)
+        Vm = V.permute(4, 5, 0, 2, 3, 1).reshape(25, B * th * tw, C)
+        Um = Uw.reshape(25, C, N)
+        M = torch.bmm(Vm, Um) if products is None else products(Vm, Um)
+        if zero_positions:
+            M = M.clone()
+            M[list(zero_positions)] = 0
+        At = AT.to(M.dtype)
+
+        def back(Mx):
+            Y = torch.einsum('oi,ijbyxk->ojbyxk', At, Mx.reshape(5, 5, B, th, tw, -1))
+            Y = torch.einsum('ojbyxk,pj->opbyxk', Y, At)
+            return Y.permute(2, 3, 0, 4, 1, 5).reshape(B, H, W, -1)
+        parts = [back(M)]
+        if absolute:
+            parts += [back(Vm.sum(2, keepdim=True)), back(Um.sum(1)[:, None, :].expand(-1, B * th * tw, -1))]
+        for i, y in enumerate(parts):
+            if out[i] is None:
+                out[i] = y.new_zeros(B, 2 * H, 2 * W, y.shape[3])
+            out[i][:, a::2, b::2] = y
+    return out[0], ((out[1], out[2]) if absolute else None)
 
 
 def conv64(p, w):
@@ -453,7 +563,7 @@ def coef(route, code, cin, split_k=0, up=False, live=None):
     n = cin if live is None else live
     if m == 0:
         return (9 * n if op == 'f32' else 27 * n + 12) + (3 if up else 0)
-    t = 7 if m == 2 else 19
+    t = 7 if m == 2 else 15 if m == F42 else 19
     if op == 'f32':
         return n + t + (cin // 128 if split_k else 0)
     if op == 'half2':
@@ -539,9 +649,9 @@ def drop_every_lo(a, ah, al):
     return ah, torch.zeros_like(al)
 
 
-def emulate(d, route, code, act_halves=None):
+def emulate(d, route, code, act_halves=None, fold=None, zero_positions=()):
     """The route's arithmetic in torch float32 -> (B, Ho, Wo, cout) float32.  act_halves(a, hi, lo) -> (hi, lo): an edit of the activation's split
-    (split halves only; default none), for the host test that shows which family notices it."""
+    (split halves only; default none), for the host test that shows which family notices it.  fold, zero_positions: wino42's two edits (w42_up only)."""
     m, op = scheme_of(route, code)
     f = torch.float32
     x, sc, sh = d['x'], d['sc'][:, None, None, :], d['sh'][:, None, None, :]
@@ -575,7 +685,10 @@ def emulate(d, route, code, act_halves=None):
         v = products(cols.contiguous(), wm).reshape(*p.shape[:3], -1)
     else:
         Um_scale = torch.tensor(scale, dtype=torch.float64)
-        v, _ = wino(p, d['w'].double() * Um_scale, m, dtype=f, products=products)
+        if m == F42:
+            v, _ = wino42(p[:, ::2, ::2], d['w'].double() * Um_scale, f, products=products, fold=fold, zero_positions=zero_positions)
+        else:
+            v, _ = wino(p, d['w'].double() * Um_scale, m, dtype=f, products=products)
     assert v.dtype == f
     v = v * (1.0 / scale) / s + d['b']
     if d['epi'] == EPI_RESIDUAL:
@@ -642,7 +755,7 @@ _PW = {}
 def packed(d, code, name_key):
     k = (name_key, code)
     if k not in _PW:
-        up2x = d['up'] and code not in (ops.WF43F,)
+        up2x = d['up'] and code not in (ops.WF43F, ops.WF42U)          # (both are packings of their own: ops.pack_weight(w, b, bf16=code) is the whole call)
         _PW[k] = ops.pack_weight(d['w'].cuda(), d['b'].cuda(), bf16=code, up2x=up2x)
     return _PW[k]
 
@@ -680,6 +793,7 @@ def case(name, key, code, split_k, route, variant=0, emulate_too=True):
 
 
 if __name__ == '__main__':
+    with_f42()
     bad = 0
     for fam in GATE_FAMILIES + SOLO_FAMILIES + ('onehot_pixels',):
         for key in SHAPES:
