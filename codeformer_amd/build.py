@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 ROOT = os.path.dirname(PKG)
 LIB = os.path.join(PKG, 'libcodeformer_hip.so')
-SOURCES = ['cf_igemm.hip', 'cf_winograd.hip', 'cf_split.hip', 'cf_wsplit.hip', 'cf_wf43.hip', 'cf_ksum.hip', 'cf_gemm_split.hip', 'cf_pack.hip', 'cf_norm.hip', 'cf_attention.hip', 'cf_misc.hip', 'cf_paste.hip', 'cf_dcn.hip', 'cf_warp.hip', 'cf_metrics.hip', 'cf_arcface.hip', 'cf_vgg.hip', 'cf_bisenet.hip']
+SOURCES = ['cf_igemm.hip', 'cf_winograd.hip', 'cf_split.hip', 'cf_wsplit.hip', 'cf_wf43.hip', 'cf_ksum.hip', 'cf_gemm_split.hip', 'cf_pack.hip', 'cf_norm.hip', 'cf_attention.hip', 'cf_misc.hip', 'cf_paste.hip', 'cf_dcn.hip', 'cf_warp.hip', 'cf_metrics.hip', 'cf_arcface.hip', 'cf_vgg.hip', 'cf_bisenet.hip', 'cf_retina.hip']
 
 
 def _hipcc():

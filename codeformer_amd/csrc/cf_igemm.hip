@@ -1218,11 +1218,14 @@ static int conv_validate(const cf_conv_desc* d, const int* pq, ConvFacts& f) {
   CF_REQUIRE(d->batch > 0 && d->hin > 0 && d->win > 0 && d->cout > 0, "cf_conv2d: bad dims");
   CF_REQUIRE(!(d->upsample && (d->stride != 1 || d->taps != 9 || d->in_nchw || d->out_nchw)),
              "cf_conv2d: upsample needs a 3x3 stride-1 NHWC conv");
-  const int exp_h = d->stride == 2 ? d->hin / 2 : (d->hin << (d->upsample ? 1 : 0));
-  const int exp_w = d->stride == 2 ? d->win / 2 : (d->win << (d->upsample ? 1 : 0));
+  // stride 2 with one padded row / column in front (pad_lo 1, nn.Conv2d(3, 2, 1)) takes any size: (h + 1) / 2 outputs, the last of which
+  // reads row h of an odd image -- outside, refused by the gather like every padded pixel.  pad_lo 0 keeps its even sizes.
+  const bool s2_sym = d->stride == 2 && d->pad_lo == 1;
+  const int exp_h = d->stride == 2 ? (d->hin + (s2_sym ? 1 : 0)) / 2 : (d->hin << (d->upsample ? 1 : 0));
+  const int exp_w = d->stride == 2 ? (d->win + (s2_sym ? 1 : 0)) / 2 : (d->win << (d->upsample ? 1 : 0));
   CF_REQUIRE(d->hout == exp_h && d->wout == exp_w, "cf_conv2d: hout/wout %dx%d, expected %dx%d", d->hout, d->wout,
              exp_h, exp_w);
-  CF_REQUIRE(d->stride == 1 || (d->hin % 2 == 0 && d->win % 2 == 0), "cf_conv2d: stride 2 needs even input");
+  CF_REQUIRE(d->stride == 1 || s2_sym || (d->hin % 2 == 0 && d->win % 2 == 0), "cf_conv2d: stride 2 with pad_lo 0 needs even input");
   if (d->out_nchw || d->cout % 4 != 0)
     CF_REQUIRE(d->epilogue == CF_EPI_NONE && !d->stats_out, "cf_conv2d: cout %d / NCHW output supports no epilogue op or statistics",
                d->cout);

@@ -2,14 +2,22 @@
 
 Same constructor, configs, `state_dict` keys (body.* / fpn.* / ssh1-3.* / ClassHead|BboxHead|LandmarkHead.N.conv1x1.*) and result
 conventions as the reference: `detect_faces(bgr image)` -> (k, 15) rows [x1, y1, x2, y2, score, 5 x (lx, ly)] in pixels of the given
-image, score-sorted and NMS-filtered; `batched_detect_faces(frames)` -> per-frame lists.  Detection is the host-code half of the
-pipeline (north star: "facelib detection/alignment left on host"): the module is stock torch ops and runs on whatever device it is
-placed on -- the entrypoint puts it on the compute device, as the reference does (MIOpen: 193 frames/s at 640x1138 on an MI355X,
-2 frames/s on 64 host threads; tools/detector_bench.py) -- and takes device-resident frames; the crops its boxes yield are cut,
-restored and pasted back by the HIP path (codeformer_amd.facelib.paste).
+image, score-sorted and NMS-filtered; `batched_detect_faces(frames)` -> per-frame lists.  The module takes device-resident frames; the
+crops its boxes yield are cut, restored and pasted back by the HIP path (codeformer_amd.facelib.paste).
+
+Two backends, chosen by `backend` (constructor argument, attribute, or the environment variable CODEFORMER_HIP_DETECTOR read at construction):
+  * 'torch' (default): stock torch ops on whatever device the module is placed on (MIOpen on the compute device: 193 frames/s at
+    640x1138 on an MI355X, 2 frames/s on 64 host threads; tools/detector_bench.py);
+  * 'hip': the ResNet-50 network on this project's kernels (retinaface_hip.py: pointwise / 3x3 MFMA convolutions with BatchNorm, ReLU and
+    the shortcut folded in, fused heads) and softmax, decode and the score threshold in one kernel, so that only the rows above
+    `conf_threshold` leave the device.  It needs network_name='resnet50', a CUDA device, eval mode and half=False; anything else raises
+    NotImplementedError naming the reason.  tools/detector_hip_bench.py times both backends side by side.
+The score sort, `py_cpu_nms` and the alignment stay on the host, on those few rows, for either backend.
 
 Not built: `align_multi` (112x112 crops through matlab_cp2tform; unused by the restoration entrypoints).
 """
+import os
+
 import numpy as np
 import torch
 from torch import nn
@@ -17,6 +25,7 @@ from torch.nn import functional as F
 
 from ....utils.img_util import resize_linear_f32
 from .retinaface_net import (FPN, SSH, MobileNetTrunk, ResNet50Trunk, make_bbox_head, make_class_head, make_landmark_head)
+from .retinaface_hip import HipDetector, forward_folded, hip_refusal
 from .retinaface_utils import PriorBox, batched_decode, batched_decode_landm, decode, decode_landm, py_cpu_nms
 
 _COMMON = dict(min_sizes=[[16, 32], [64, 128], [256, 512]], steps=[8, 16, 32], variance=[0.1, 0.2], clip=False, loc_weight=2.0,
@@ -36,8 +45,12 @@ def generate_config(network_name):
 
 class RetinaFace(nn.Module):
 
-    def __init__(self, network_name='resnet50', half=False, phase='test', device='cpu'):
+    BACKENDS = ('torch', 'hip')
+
+    def __init__(self, network_name='resnet50', half=False, phase='test', device='cpu', backend=None):
         super().__init__()
+        self.__dict__['_hip'] = HipDetector(self)     # (not a registered child: the state_dict keys are the reference's)
+        self._backend = 'torch'
         self.half_inference = half
         cfg = generate_config(network_name)
         self.backbone = cfg['name']
@@ -58,14 +71,41 @@ class RetinaFace(nn.Module):
         self.eval()
         if half:
             self.half()
+        self.backend = backend or os.environ.get('CODEFORMER_HIP_DETECTOR') or 'torch'
 
     @property
     def device(self):
         return self.mean_tensor.device
 
+    @property
+    def backend(self):
+        return self._backend
+
+    @backend.setter
+    def backend(self, name):
+        if name not in self.BACKENDS:
+            raise ValueError(f'backend {name!r}: one of {self.BACKENDS}')
+        if name == 'hip' and (self.cfg['name'] != 'Resnet50' or self.half_inference):
+            raise NotImplementedError(hip_refusal(self))      # (the device and the mode can still change: checked again at every call)
+        self._backend = name
+
+    def _use_hip(self):
+        if self._backend != 'hip':
+            return False
+        why = hip_refusal(self)
+        if why:
+            raise NotImplementedError(why)
+        return True
+
+    def forward_folded(self, inputs):
+        """The HIP backend's dataflow (BatchNorm folded, fused heads) on stock torch ops in the parameters' dtype; same outputs as forward."""
+        return forward_folded(self, inputs)
+
     def forward(self, inputs):
         """(B,3,H,W) mean-subtracted BGR -> (bbox (B,n,4), class probabilities (B,n,2), landmarks (B,n,10)); n = anchors of the three
         pyramid levels in level-major, row-major, anchor-minor order (the order PriorBox emits)."""
+        if self._use_hip():
+            return self._hip(inputs)
         pyramid = self.fpn(self.body(inputs))
         feats = [self.ssh1(pyramid[0]), self.ssh2(pyramid[1]), self.ssh3(pyramid[2])]
         bbox = torch.cat([h(f) for h, f in zip(self.BboxHead, feats)], dim=1)
@@ -119,6 +159,10 @@ class RetinaFace(nn.Module):
         if self.half_inference:
             image = image.half()
         image = image - self.mean_tensor.to(image.dtype)
+        if self._use_hip():       # the rows above the threshold, decoded and scaled on the device, in anchor order
+            rows = self._hip.detect(image, self.resize, conf_threshold)[0]
+            rows = rows[rows[:, 4].argsort()[::-1]]
+            return rows[py_cpu_nms(rows[:, :5], nms_threshold)]
         loc, conf, landmarks, priors = self._run(image)
         boxes = (decode(loc.squeeze(0), priors, self.cfg['variance']) * self.scale / self.resize).cpu().numpy()
         scores = conf.squeeze(0).cpu().numpy()[:, 1]
@@ -157,6 +201,13 @@ class RetinaFace(nn.Module):
         frames, self.resize = self.batched_transform(frames, use_origin_size)
         frames = frames.to(self.device)
         frames = frames - self.mean_tensor
+        if self._use_hip():
+            final_boxes, final_landmarks = [], []
+            for rows in self._hip.detect(frames, self.resize, conf_threshold):
+                keep = py_cpu_nms(rows[:, :5], nms_threshold)
+                final_boxes.append(rows[keep, :5] if len(rows) else np.array([], dtype=np.float32))
+                final_landmarks.append(rows[keep, 5:] if len(rows) else np.array([], dtype=np.float32))
+            return final_boxes, final_landmarks
         b_loc, b_conf, b_landmarks, priors = self._run(frames)
         priors = priors.unsqueeze(0)
         b_loc = batched_decode(b_loc, priors, self.cfg['variance']) * self.scale / self.resize

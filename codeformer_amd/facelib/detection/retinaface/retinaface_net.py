@@ -6,11 +6,13 @@ so `detection_Resnet50_Final.pth` holds `body.conv1 ... body.layer4.*` only).  T
 so both released checkpoints load with strict=True; the module tree is table-driven instead of spelled out.
 
 Every conv + BatchNorm (+ LeakyReLU) triple is a `ConvUnit`: an `nn.Sequential` whose children carry the reference's indices
-(0 conv, 1 bn, 2 act).  On the host it runs as stock torch ops; `folded()` hands the HIP path the BatchNorm-folded weight.
+(0 conv, 1 bn, 2 act).  On the host it runs as stock torch ops; `folded(torch.float64)` hands the HIP path (retinaface_hip.py) the BatchNorm-folded weight.
 """
 import torch
 from torch import nn
 from torch.nn import functional as F
+
+from ....archs.arcface_arch import fold_conv_bn
 
 
 class ConvUnit(nn.Sequential):
@@ -23,12 +25,15 @@ class ConvUnit(nn.Sequential):
         super().__init__(*layers)
         self.slope = slope
 
-    def folded(self):
-        """(weight, bias) of the equivalent bias-carrying convolution in eval mode."""
-        conv, bn = self[0], self[1]
-        g = bn.weight.detach().float() * torch.rsqrt(bn.running_var.float() + bn.eps)
-        return (conv.weight.detach().float() * g.view(-1, 1, 1, 1)).contiguous(), \
-            (bn.bias.detach().float() - bn.running_mean.float() * g).contiguous()
+    def folded(self, dtype=None):
+        """(weight, bias) of the equivalent bias-carrying convolution in eval mode, evaluated in `dtype` (default: the parameters'): the one
+        folding routine of the project (arcface_arch.fold_conv_bn).  The HIP path asks for float64 and rounds once."""
+        return fold_conv_bn(self[0], self[1], dtype)
+
+    def fold_deps(self):
+        """The tensors a cached folded weight depends on."""
+        bn = self[1]
+        return [self[0].weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
 
 
 def conv_bn(inp, oup, stride=1, leaky=0):                 # retinaface_net.py:6-9

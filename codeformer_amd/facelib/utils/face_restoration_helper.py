@@ -54,9 +54,9 @@ class FaceRestoreHelper(object):
 
     def __init__(self, upscale_factor, face_size=512, crop_ratio=(1, 1), det_model='retinaface_resnet50', save_ext='png',
                  template_3points=False, pad_blur=False, use_parse=False, device=None, face_detector=None, face_parse=None,
-                 det_device='cpu'):
+                 det_device='cpu', det_backend=None):
         """Extra arguments: `face_detector` / `face_parse` take ready models (otherwise init_detection_model / init_parsing_model read
-        weights/facelib/; face_detector=False builds none); `det_device` is where the detector runs (host by default)."""
+        weights/facelib/; face_detector=False builds none); `det_device` is where the detector runs (host by default), `det_backend` its backend ('torch' | 'hip' | None: RetinaFace's default)."""
         if det_model == 'dlib':
             raise NotImplementedError('det_model dlib is not built')
         if pad_blur:
@@ -71,7 +71,7 @@ class FaceRestoreHelper(object):
             device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
         self.device = torch.device(device)
         if face_detector is None:
-            face_detector = init_detection_model(det_model, half=False, device=det_device)
+            face_detector = init_detection_model(det_model, half=False, device=det_device, backend=det_backend)
         self.face_detector = face_detector or None            # face_detector=False: no detector (alignment matrices come from outside)
         if face_parse is None and use_parse:
             from ..parsing import init_parsing_model

@@ -132,6 +132,11 @@ SIGNATURES = {
     'cf_scale_add_row': (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     'cf_resize_bilinear_ac': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     'cf_resize_bilinear_ac_argmax': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    'cf_pointwise_packed_elems': (_L, [_I, _I]),
+    'cf_pack_pointwise': (_I, [_P, _I, _I, _P, _P]),
+    'cf_pointwise': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    'cf_nearest_add': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    'cf_retina_decode': (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _I, _P, _P]),
     'cf_warp_affine_u8':(_I, [_P, _L, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'cf_warp_affine_f32': (_I, [_P, _I, _I, ctypes.POINTER(ctypes.c_double), _P, _I, _I, _I, _I, _P]),
     'cf_erode_f32': (_I, [_P, _P, _P, _I, _I, _I, _P]),

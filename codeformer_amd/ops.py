@@ -704,7 +704,8 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     sft_w with EPI_SFT: a float, or a contiguous float32 tensor of B values on x's device -- one weight per image (cf_conv2d_sft_w); image b
     is then bitwise the launch on that image alone with sft_w = float(sft_w[b]).
     pad_mode: PAD_ZERO, PAD_REFLECT (ReflectionPad2d(1) + unpadded 3x3) or PAD_EDGE (with upsample: reflection padding of the
-    upsampled image); pad_lo=1 with stride 2: one padded row / column on every side instead of right / bottom only.
+    upsampled image); pad_lo=1 with stride 2: one padded row / column on every side instead of right / bottom only, at any
+    input size (Ho = (H + 1) // 2: nn.Conv2d(3, 2, 1)); pad_lo=0 needs even H and W.
     act: (B, 2) range-scale table of an un-normalised input (act_scale(x)); dropped when the layer's kernel has fp32 operands.
     stats_into: a StatsPair -- the statistics partials of this launch go into its shared buffer (two sibling convolutions whose range-scale
     tables are then ONE launch: act_scale_pair).
@@ -757,7 +758,7 @@ def conv2d(x, pw, *, x2=None, stride=1, upsample=False, prologue=PRO_NONE, scale
     if bool(pw.s2) != (stride == 2 and int(pw.bf16) == OPERAND_F16X2):
         raise ValueError('a weight packed with stride2=True serves conv2d(stride=2) only (and f16x2 operands at stride 2 need it)')
     if stride == 2:
-        Ho, Wo = H // 2, W // 2
+        Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if pad_lo == 1 else (H // 2, W // 2)   # (pad_lo 1: nn.Conv2d(3, 2, 1) at any size; pad_lo 0 needs even sizes)
     else:
         Ho, Wo = (H * 2, W * 2) if upsample else (H, W)
     shape = (B, pw.cout, Ho, Wo) if out_nchw else (B, Ho, Wo, pw.cout)
@@ -1868,3 +1869,108 @@ def resize_bilinear_ac_argmax(x, size, c=None):
     out = torch.empty((B, oh, ow), dtype=torch.int64, device=x.device)
     L.check(L.load().cf_resize_bilinear_ac_argmax(L.ptr(x), B, H, W, ld, c, L.ptr(out, dtype=torch.int64), oh, ow, L.stream_ptr()), 'cf_resize_bilinear_ac_argmax')
     return out
+
+
+# ---- RetinaFace (cf_retina.hip) -- definitions at "RetinaFace ResNet-50 detector" in include/codeformer_hip.h ------------------------------
+class PackedPointwise:
+    """A 1x1 convolution's weight in the layout cf_pointwise reads (pack_pointwise) and its bias (or None)."""
+
+    def __init__(self, w, bias, cin, cout):
+        self.w, self.bias, self.cin, self.cout = w, bias, cin, cout
+
+
+def pack_pointwise(weight, bias=None):
+    """(cout,cin) or (cout,cin,1,1) float32 -> PackedPointwise: rows padded to a multiple of 64, columns to a multiple of 32, with zeros."""
+    w = _f32(weight).detach()
+    if w.dim() == 4 and tuple(w.shape[2:]) == (1, 1):
+        w = w.reshape(w.shape[0], w.shape[1])
+    if w.dim() != 2 or w.shape[1] % 4:
+        raise ValueError(f'pack_pointwise: a (cout,cin[,1,1]) weight with cin % 4 == 0, got {tuple(weight.shape)}')
+    cout, cin = w.shape
+    lib = L.load()
+    n = lib.cf_pointwise_packed_elems(cin, cout)
+    if n <= 0:
+        raise ValueError(f'pack_pointwise: bad dims cin {cin}, cout {cout}')
+    w = w.contiguous()
+    wp = torch.empty(n, dtype=torch.float32, device=w.device)
+    L.check(lib.cf_pack_pointwise(L.ptr(w), cin, cout, L.ptr(wp), L.stream_ptr()), 'cf_pack_pointwise')
+    if bias is not None and tuple(_f32(bias).shape) != (cout,):
+        raise ValueError(f'pack_pointwise: bias {tuple(bias.shape)} for {cout} outputs')
+    return PackedPointwise(wp, None if bias is None else bias.detach().contiguous(), cin, cout)
+
+
+def pointwise(x, pp, *, res=None, relu=False, step=1, out=None):
+    """[relu](x @ W^T + bias [+ res]) over the pixels of a channels-last (B,H,W,cin) float32 tensor -> (B,Ho,Wo,cout), one launch on the fp32
+    MFMA.  step 2 reads pixel (2y, 2x): Ho = ceil(H / 2), the 1x1 stride-2 convolution.  x, res and `out` may be channel slices
+    `buf[..., a:b]` of wider channels-last buffers (x is read four channels at a time: a % 4 == 0 and a buffer width % 4 == 0; res and out are free).  One fixed K order, no split-K: image b is bitwise the call on it alone."""
+    _f32(x)
+    if x.dim() != 4 or x.shape[3] != pp.cin:
+        raise ValueError(f'pointwise: x {tuple(x.shape)} for a weight of {pp.cin} input channels')
+    if step not in (1, 2):
+        raise ValueError(f'pointwise: step {step} (1 or 2)')
+    B, H, W, _ = x.shape
+    Ho, Wo = (H + step - 1) // step, (W + step - 1) // step
+    shape = (B, Ho, Wo, pp.cout)
+    ldx = _nhwc_ld(x, 'x')
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != x.device:
+        raise ValueError(f'pointwise: out expected float32 {shape} on {x.device}')
+    else:
+        _drop_state(out)
+    ldo = _nhwc_ld(out, 'out')
+    ldr = 0
+    if res is not None:
+        if tuple(_f32(res).shape) != shape or res.device != x.device:
+            raise ValueError(f'pointwise: res {tuple(res.shape)} != {shape}')
+        ldr = _nhwc_ld(res, 'res')
+    L.check(L.load().cf_pointwise(L.ptr(x, True), ldx, L.ptr(pp.w), L.ptr(pp.bias), L.ptr(res, True), ldr, B, H, W, pp.cin, pp.cout, step,
+                                  1 if relu else 0, L.ptr(out, True), ldo, L.stream_ptr()), 'cf_pointwise')
+    return out
+
+
+def nearest_add(a, b):
+    """a + F.interpolate(b, size=a's, mode='nearest') on dense channels-last (B,H,W,C) float32 tensors, bitwise the torch expression."""
+    B, H, W, C = _nhwc_dense(a, 'nearest_add')
+    Bb, Hb, Wb, Cb = _nhwc_dense(b, 'nearest_add')
+    if (Bb, Cb) != (B, C):
+        raise ValueError(f'nearest_add: a {tuple(a.shape)}, b {tuple(b.shape)}')
+    out = torch.empty_like(a)
+    L.check(L.load().cf_nearest_add(L.ptr(a), L.ptr(b), B, H, W, Hb, Wb, C, L.ptr(out), L.stream_ptr()), 'cf_nearest_add')
+    return out
+
+
+def retina_decode(heads, priors=None, *, variance=(0.1, 0.2), img_wh=(1.0, 1.0), resize=1.0, conf_threshold=None, cap=0, full=False):
+    """The detector's tail.  heads: three dense (B,H_l,W_l,32) float32 tensors, an anchor's 16 values together (4 box, 2 class, 10 landmark).
+    full=True: (bbox (B,n,4), softmax (B,n,2), landmarks (B,n,10)), what RetinaFace.forward returns.  conf_threshold given: (rows (B,cap,15),
+    counts (B,) int32) -- the decoded, scaled rows [x1, y1, x2, y2, score, 5 x (lx, ly)] of the anchors with score > conf_threshold in
+    ascending anchor order and their TRUE number per image (a count above cap: take the full tensors).  One mode per call."""
+    if len(heads) != 3:
+        raise ValueError('retina_decode: three pyramid levels')
+    B, dev = heads[0].shape[0], heads[0].device
+    nps = []
+    for h in heads:
+        b, hh, ww, c = _nhwc_dense(h, 'retina_decode')
+        if b != B or c != 32:
+            raise ValueError(f'retina_decode: heads of shape {tuple(h.shape)} (B,H,W,32)')
+        nps.append(hh * ww)
+    n = 2 * sum(nps)
+    compact = conf_threshold is not None
+    if bool(full) == compact:
+        raise ValueError('retina_decode: one mode per call, full=True or a conf_threshold')
+    outs = []
+    bbox = conf = ldm = rows = counts = None
+    if full:
+        bbox, conf, ldm = (torch.empty((B, n, k), dtype=torch.float32, device=dev) for k in (4, 2, 10))
+        outs += [bbox, conf, ldm]
+    if compact:
+        if priors is None or tuple(_f32(priors).shape) != (n, 4) or priors.device != dev or cap < 1:
+            raise ValueError(f'retina_decode: the compact rows need ({n},4) priors on {dev} and cap >= 1')
+        rows = torch.empty((B, cap, 15), dtype=torch.float32, device=dev)
+        counts = torch.empty((B,), dtype=torch.int32, device=dev)
+        outs += [rows, counts]
+    L.check(L.load().cf_retina_decode(L.ptr(heads[0]), L.ptr(heads[1]), L.ptr(heads[2]), nps[0], nps[1], nps[2], L.ptr(priors), B,
+                                      float(variance[0]), float(variance[1]), float(img_wh[0]), float(img_wh[1]), float(resize),
+                                      float(conf_threshold) if compact else 0.0, L.ptr(bbox), L.ptr(conf), L.ptr(ldm), L.ptr(rows), int(cap),
+                                      L.ptr(counts, dtype=torch.int32), L.stream_ptr()), 'cf_retina_decode')
+    return tuple(outs)

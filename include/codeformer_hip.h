@@ -659,6 +659,51 @@ int cf_scale_add_row(const float* x, const float* g, const float* r, int batch, 
 int cf_resize_bilinear_ac(const float* x, int batch, int h, int w, int ld, int c, float* out, int oh, int ow, cf_stream_t stream);
 int cf_resize_bilinear_ac_argmax(const float* x, int batch, int h, int w, int ld, int c, int64_t* labels, int oh, int ow, cf_stream_t stream);
 
+/* ---- RetinaFace ResNet-50 detector (facelib/detection/retinaface/retinaface.py, retinaface_net.py, retinaface_utils.py) ------------------
+ * Additive exports, CF_ABI_VERSION stays 22.  fp32, channels-last.  No split-K, no float atomics, one fixed summation order per output:
+ * bitwise repeatable, and image b of a batch is bitwise the call on it alone.  Every argument is checked before a launch.
+ *   cf_pointwise_packed_elems   floats of a packed pointwise weight: ceil64(cout) * ceil32(cin); -1: bad arguments.
+ *   cf_pack_pointwise  w [cout][cin] -> wp [ceil64(cout)][ceil32(cin)], wp[n][k] = w[n][k], zero where n >= cout or k >= cin.
+ *   cf_pointwise       a 1x1 convolution over pixels as one GEMM on v_mfma_f32_32x32x2_f32 with IEEE-fp32 operands:
+ *                        out[b][oy][ox][n] = act(bias[n] + sum_k wp[n][k] * x[b][step * oy][step * ox][k] [+ res[b][oy][ox][n]])
+ *                      x [batch][h][w] pixels of ld_x floats (the first cin are read; a channel slice of a wider buffer is ld_x > cin),
+ *                      out / res [batch][ho][wo] pixels of ld_out / ld_res floats, ho = (h + step - 1) / step, wo likewise; step 1 or 2 (the
+ *                      1x1 stride-2 `downsample` of a bottleneck: every second pixel of every second row).  M = batch * ho * wo is any value:
+ *                      a workgroup owns 128 rows x 64 columns, edge rows and columns are masked on the store and read from a clamped address.
+ *                      K order: slabs of 32 channels in ascending order; within a slab the instruction j (0 .. 15) of a wave multiplies
+ *                      channels (8 (j / 4) + j % 4, 8 (j / 4) + 4 + j % 4); all of an output's products go down ONE accumulation chain
+ *                      from zero, in that order whatever M, N and the batch are.  Then one addition of the bias, one of the residual, and
+ *                      act: CF_PW_NONE, or CF_PW_RELU (v > 0 ? v : +0, a NaN stays).  cin % 4 == 0, ld_x % 4 == 0, x and wp 16-byte
+ *                      aligned (x is read four channels at a time; res and out one float at a time: ld_res and ld_out are any value >= cout); bias may be NULL (zero), res may be NULL.  A padded k multiplies a stored zero by a stored zero.
+ *   cf_nearest_add     out = a + nearest(b -> a's size): a / out [batch][ha][wa][c], b [batch][hb][wb][c], c % 4 == 0; the source index of
+ *                      destination index d on an axis is min((int)floorf((float)d * scale), n_in - 1) with scale = (float)n_in / (float)n_out
+ *                      computed once: F.interpolate(mode='nearest', size=...) as torch evaluates it (retinaface_net.py:94-99), followed by
+ *                      one fp32 addition -- bitwise `a + F.interpolate(b, size=a's, mode='nearest')`.
+ *   cf_retina_decode   the detector's tail on the fused head outputs.  Level l (0 .. 2) is heads[l]: [batch][np_l] pixels of 32 floats, anchor
+ *                      a (0, 1) of a pixel at floats 16 a .. 16 a + 15: 4 box regressions, 2 class logits, 10 landmark regressions.  Anchor
+ *                      i of an image (n = 2 (np_0 + np_1 + np_2), level-major, pixel-major, anchor-minor: the order of PriorBox) has
+ *                      priors[i] = (cx, cy, w, h).  Softmax: m = max(l0, l1), e_j = expf(l_j - m), p_j = e_j / (e_0 + e_1).
+ *                      Full mode (bbox != NULL): bbox [batch][n][4], conf [batch][n][2], ldm [batch][n][10] = the regressions as they are,
+ *                      the softmax, the landmark regressions: what RetinaFace.forward returns.
+ *                      Compact mode (rows != NULL): per anchor, score = p_1;  box (retinaface_utils.py:254-271): c = prior.xy + (loc.xy * var0)
+ *                      * prior.wh, s = prior.wh * expf(loc.wh * var1), lo = c - s / 2, hi = s + lo;  landmarks (:274-294): prior.xy +
+ *                      (pre * var0) * prior.wh;  each value then (v * scale) / resize with scale = img_w for x, img_h for y -- every step one
+ *                      fp32 operation, none contracted.  The anchors with score > conf_threshold are written as rows of 15 floats (x1, y1,
+ *                      x2, y2, score, 5 x (lx, ly)) to rows [batch][cap][15] in ASCENDING anchor order: one workgroup per image counts,
+ *                      scans and writes chunk by chunk, no atomic append.  counts [batch] (int32) receives the TRUE number of passing
+ *                      anchors; rows beyond cap are not written, and the caller that sees counts[b] > cap takes the full mode instead.
+ *                      One mode per call: asking for both, or for neither, is refused.  np_l >= 0, n >= 1, batch <= 65535. */
+#define CF_PW_NONE 0
+#define CF_PW_RELU 1
+int64_t cf_pointwise_packed_elems(int cin, int cout);
+int cf_pack_pointwise(const float* w, int cin, int cout, float* wp, cf_stream_t stream);
+int cf_pointwise(const float* x, int ld_x, const float* wp, const float* bias, const float* res, int ld_res, int batch, int h, int w, int cin,
+                 int cout, int step, int act, float* out, int ld_out, cf_stream_t stream);
+int cf_nearest_add(const float* a, const float* b, int batch, int ha, int wa, int hb, int wb, int c, float* out, cf_stream_t stream);
+int cf_retina_decode(const float* heads0, const float* heads1, const float* heads2, int np0, int np1, int np2, const float* priors, int batch,
+                     float var0, float var1, float img_w, float img_h, float resize, float conf_threshold, float* bbox, float* conf, float* ldm,
+                     float* rows, int cap, int* counts, cf_stream_t stream);
+
 /* ---- alignment warp and paste-back of the whole-image / video path ----------------------------------------------------------
  * Replaces the OpenCV calls of facelib/utils/face_restoration_helper.py: cv2.warpAffine of align_warp_face (:343-344) and of
  * paste_faces_to_input_image (:400, :428, :479), cv2.erode (:430-431, :447), cv2.GaussianBlur (:449), np.sum (:433), the soft-mask

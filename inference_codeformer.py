@@ -72,6 +72,9 @@ def parse_args(argv=None):
     p.add_argument('--det_device', type=str, default='auto',
                    help="where the face detector runs: 'auto' = the compute device, as the reference places it (stock torch ops through "
                         "MIOpen: 193 frames/s for RetinaFace-ResNet50 at 640x1138 on an MI355X), 'cpu' = the host cores (2 frames/s on 64 threads)")
+    p.add_argument('--det_backend', type=str, default=None, choices=('torch', 'hip'),
+                   help="the detector's backend: 'torch' = stock torch ops, 'hip' = RetinaFace-ResNet50 on this project's kernels (needs a ROCm "
+                        "device); default: the environment variable CODEFORMER_HIP_DETECTOR, else 'torch'")
     p.add_argument('--io_workers', type=int, default=None, help='PNG decode / encode worker threads of the GPU pipeline')
     p.add_argument('--strict', action='store_true', help='Raise on inference errors instead of returning the input face')
     p.add_argument('--frame_window', type=int, default=32, help='Whole-image / video path: images restored, pasted back and written per window '
@@ -105,13 +108,13 @@ def build_detector(args, device):
     from facelib.detection import RetinaFace, init_detection_model
     det_device = device if args.det_device == 'auto' else torch.device(args.det_device)
     try:
-        return init_detection_model(args.detection_model, half=False, device=det_device)
+        return init_detection_model(args.detection_model, half=False, device=det_device, backend=args.det_backend)
     except FileNotFoundError:
         if args.random_init_seed is None:
             raise
         print(f'WARNING: detector checkpoint not found -- using torch.manual_seed({args.random_init_seed}) random weights')
         torch.manual_seed(args.random_init_seed)
-        return RetinaFace(network_name=args.detection_model.replace('retinaface_', ''), device=det_device)
+        return RetinaFace(network_name=args.detection_model.replace('retinaface_', ''), device=det_device, backend=args.det_backend)
 
 
 def build_parser(args, device):

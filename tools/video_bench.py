@@ -4,7 +4,7 @@ forwards, paste-back on the device at --upscale.  Reports faces/s and frames/s w
 (PCIe included) and with the network alone for comparison.  With a fourth argument (cuda | cpu) the detection stage of
 FaceRestoreHelper.get_face_landmarks_5(resize=640) -- INTER_AREA reduction on the host, RetinaFace-ResNet50 (seeded weights: its boxes are
 discarded, the prepared matrices are used) on that device -- runs per frame inside the timed region.
-usage: python tools/video_bench.py [frames] [faces_per_frame] [upscale] [detector device]"""
+usage: python tools/video_bench.py [frames] [faces_per_frame] [upscale] [detector device] [detector backend: torch | hip]"""
 import os
 import sys
 import time
@@ -22,6 +22,7 @@ nf = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 up = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 det_dev = sys.argv[4] if len(sys.argv) > 4 else None
+det_backend = sys.argv[5] if len(sys.argv) > 5 else None       # 'torch' | 'hip' (RetinaFace's backend; None: its default)
 rng = np.random.default_rng(0)
 base = rng.integers(0, 256, (1080, 1920, 3), dtype=np.uint8)
 frames = [np.roll(base, 7 * i, axis=1) for i in range(nf)]
@@ -46,7 +47,7 @@ if det_dev:
     from codeformer_amd import ops
     from codeformer_amd.facelib.detection import RetinaFace
     from codeformer_amd.utils.img_util import resize_area
-    det = RetinaFace('resnet50', device=det_dev)
+    det = RetinaFace('resnet50', device=det_dev, backend=det_backend)
 
     def detect(f):
         if det_dev == 'cuda':       # the frame goes up once; the INTER_AREA reduction is a kernel, the detector reads its output
@@ -60,7 +61,7 @@ if det_dev:
         for f in frames:
             detect(f)
     torch.cuda.synchronize()
-    det_note = f'; detection stage (INTER_AREA reduction + RetinaFace-ResNet50 on {det_dev}) {nf / (time.perf_counter() - t0):.1f} frames/s, included'
+    det_note = f'; detection stage (INTER_AREA reduction + RetinaFace-ResNet50 on {det_dev}, backend {det.backend}) {nf / (time.perf_counter() - t0):.1f} frames/s, included'
 out = vr.restore(frames, affs)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
