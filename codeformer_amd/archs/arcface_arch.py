@@ -30,6 +30,7 @@ from torch.nn import functional as F
 
 from .. import ops
 from ..utils.registry import ARCH_REGISTRY
+from .folded import bn_affine, bn_deps, conv_hip, fold_conv_bn, folded_layer, need_eval, prelu_slope
 from .hip_module import HipModule
 
 IN_SIZE = 128   # fc5 = Linear(512 * 8 * 8, 512) after four halvings
@@ -38,41 +39,6 @@ IN_SIZE = 128   # fc5 = Linear(512 * 8 * 8, 512) after four halvings
 def conv3x3(inplanes, outplanes, stride=1):
     """3x3 convolution, padding 1, no bias (arcface_arch.py:5-13)."""
     return nn.Conv2d(inplanes, outplanes, kernel_size=3, stride=stride, padding=1, bias=False)
-
-
-def bn_affine(bn, dtype=None):
-    """(scale, shift) of an eval-mode BatchNorm: y = x * scale + shift."""
-    dtype = dtype or bn.weight.dtype
-    g = bn.weight.detach().to(dtype) * torch.rsqrt(bn.running_var.detach().to(dtype) + bn.eps)
-    return g, bn.bias.detach().to(dtype) - bn.running_mean.detach().to(dtype) * g
-
-
-def fold_conv_bn(conv, bn, dtype=None, embed3=False):
-    """(weight, bias) of bn(conv(x)) for a bias-free conv.  embed3: a 1x1 weight as the centre tap of a 3x3 one."""
-    dtype = dtype or conv.weight.dtype
-    g, t = bn_affine(bn, dtype)
-    w = conv.weight.detach().to(dtype) * g.view(-1, 1, 1, 1)
-    if embed3:
-        w3 = w.new_zeros(w.shape[0], w.shape[1], 3, 3)
-        w3[:, :, 1, 1] = w[:, :, 0, 0]
-        w = w3
-    return w.contiguous(), t.contiguous()
-
-
-def _bn_deps(bn):
-    return [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-
-
-def prelu_slope(mod, prelu):
-    """The one slope of an nn.PReLU() as a Python float, read back once per parameter version."""
-    if prelu.weight.numel() != 1:
-        raise NotImplementedError('HIP path: nn.PReLU() with one slope')
-    return mod._packed(('slope', id(prelu)), lambda: float(prelu.weight.detach().reshape(-1)[0]), prelu.weight)
-
-
-def _need_eval(mod):
-    if mod.training:
-        raise RuntimeError(f'{type(mod).__name__} on HIP folds BatchNorm and drops Dropout: call .eval() first')
 
 
 class BasicBlock(nn.Module):
@@ -170,16 +136,19 @@ class IRBlock(HipModule):
             self.se = SEBlock(planes)
 
     # -- folded parameters (dtype None: the parameters' own) -------------------------------------------------------------------------------
+    def layer(self, which):
+        """The folded.folded_layer 'conv1' | 'conv2' | 'shortcut' (the 1x1 as the centre tap of a 3x3)."""
+        if which != 'shortcut':
+            return folded_layer(getattr(self, which), getattr(self, 'bn' + which[-1]))
+        conv, bn = self.downsample[0], self.downsample[1]
+        if conv.kernel_size != (1, 1) or conv.bias is not None or conv.stride != (self.stride, self.stride):
+            raise NotImplementedError('IRBlock shortcut: a bias-free 1x1 conv at the block stride, then BatchNorm2d')
+        return folded_layer(conv, bn, embed3=True)
+
     def folded(self, dtype=None):
         """dict: pre (scale, shift) of bn0; conv1 / conv2 (weight, bias) with bn1 / bn2 folded; shortcut (3x3 centre-tap weight, bias) or None."""
-        sc = None
-        if self.downsample is not None:
-            conv, bn = self.downsample[0], self.downsample[1]
-            if conv.kernel_size != (1, 1) or conv.bias is not None or conv.stride != (self.stride, self.stride):
-                raise NotImplementedError('IRBlock shortcut: a bias-free 1x1 conv at the block stride, then BatchNorm2d')
-            sc = fold_conv_bn(conv, bn, dtype, embed3=True)
-        return {'pre': bn_affine(self.bn0, dtype), 'conv1': fold_conv_bn(self.conv1, self.bn1, dtype), 'conv2': fold_conv_bn(self.conv2, self.bn2, dtype),
-                'shortcut': sc}
+        return {'pre': bn_affine(self.bn0, dtype), 'conv1': self.layer('conv1')[0](dtype), 'conv2': self.layer('conv2')[0](dtype),
+                'shortcut': None if self.downsample is None else self.layer('shortcut')[0](dtype)}
 
     def forward_folded(self, x):
         """The device dataflow on stock torch ops (NCHW), in the parameters' dtype."""
@@ -197,14 +166,6 @@ class IRBlock(HipModule):
         return torch.where(h > 0, h, a * h)
 
     # -- HIP -------------------------------------------------------------------------------------------------------------------------------
-    def _pw(self, which):
-        conv, bn = {'conv1': (self.conv1, self.bn1), 'conv2': (self.conv2, self.bn2), 'shortcut': tuple(self.downsample or (None, None))[:2]}[which]
-
-        def build():
-            w, b = self.folded(torch.float64)[which]
-            return ops.pack_weight(w.float(), b.float())
-        return self._packed(('w', which), build, conv.weight, *_bn_deps(bn))
-
     def _pre_tables(self, batch):
         """bn0 as the (batch, C) scale / shift tables of CF_PRO_AFFINE.  Every row is the same: a table of 16 rows, or of the next power of
         two above a larger batch, is cached and the batch takes its first rows (a contiguous slice: no launch)."""
@@ -213,21 +174,18 @@ class IRBlock(HipModule):
         def build():
             s, t = bn_affine(self.bn0, torch.float64)
             return s.float().expand(rows, -1).contiguous(), t.float().expand(rows, -1).contiguous()
-        s, t = self._packed(('pre', rows), build, *_bn_deps(self.bn0))
+        s, t = self._packed(('pre', rows), build, *bn_deps(self.bn0))
         return s[:batch], t[:batch]
 
     def run_hip(self, x):
-        _need_eval(self)
+        need_eval(self)
         a = prelu_slope(self, self.prelu)
         s, t = self._pre_tables(x.shape[0])
-        h = ops.conv2d(x, self._pw('conv1'), prologue=ops.PRO_AFFINE, scale=s, shift=t, epilogue=ops.EPI_PRELU, sft_w=a)
-        geom = dict(stride=2, pad_lo=1) if self.stride == 2 else {}
-        if self.stride not in (1, 2):
-            raise NotImplementedError(f'IRBlock stride {self.stride} (HIP path: 1 or 2)')
-        res = x if self.downsample is None else ops.conv2d(x, self._pw('shortcut'), **geom)
+        h = conv_hip(self, ('w', 'conv1'), self.layer('conv1'), x, slope=a, prologue=ops.PRO_AFFINE, scale=s, shift=t)
+        res = x if self.downsample is None else conv_hip(self, ('w', 'shortcut'), self.layer('shortcut'), x, stride=self.stride)
         if not self.use_se:
-            return ops.conv2d(h, self._pw('conv2'), epilogue=ops.EPI_RES_PRELU, res=res, sft_w=a, **geom)
-        h = ops.conv2d(h, self._pw('conv2'), **geom)
+            return conv_hip(self, ('w', 'conv2'), self.layer('conv2'), h, stride=self.stride, res=res, slope=a)
+        h = conv_hip(self, ('w', 'conv2'), self.layer('conv2'), h, stride=self.stride)
         return ops.se_scale_res_prelu(h, self.se.gate_hip(h), res, a)
 
     def forward_host(self, x):
@@ -291,9 +249,6 @@ class ResNetArcFace(HipModule):
         return [b for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer]
 
     # -- folded parameters -------------------------------------------------------------------------------------------------------------------
-    def folded_stem(self, dtype=None):
-        return fold_conv_bn(self.conv1, self.bn1, dtype)
-
     def folded_tail(self, dtype=None):
         """(weight (512, 32768), bias) of bn5(fc5(flatten(bn4(x)))) on the CHANNELS-LAST flattening (h*8 + w)*512 + c of x."""
         dtype = dtype or self.fc5.weight.dtype
@@ -308,7 +263,7 @@ class ResNetArcFace(HipModule):
     def forward_folded(self, x):
         """The device dataflow on stock torch ops, in the parameters' dtype."""
         a = self.prelu.weight.detach().reshape(-1)[0]
-        h = F.conv2d(x, *self.folded_stem(), padding=1)
+        h = F.conv2d(x, *fold_conv_bn(self.conv1, self.bn1), padding=1)
         h = F.max_pool2d(torch.where(h > 0, h, a * h), 2, 2)
         for blk in self._blocks():
             h = blk.forward_folded(h)
@@ -318,7 +273,7 @@ class ResNetArcFace(HipModule):
     # -- HIP -------------------------------------------------------------------------------------------------------------------------------
     def check_device_call(self, shape):
         """What the HIP path refuses, before it touches a device: training mode (RuntimeError), any input but (B,1,128,128) (ValueError)."""
-        _need_eval(self)
+        need_eval(self)
         if len(shape) != 4 or tuple(shape[1:]) != (1, IN_SIZE, IN_SIZE) or shape[0] < 1:
             raise ValueError(f'ResNetArcFace on HIP takes (B,1,{IN_SIZE},{IN_SIZE}) (fc5 fixes the size), got {tuple(shape)}')
         for blk in self._blocks():
@@ -328,18 +283,14 @@ class ResNetArcFace(HipModule):
     def forward_hip(self, x):
         self.check_device_call(x.shape)
 
-        def stem():
-            w, b = self.folded_stem(torch.float64)
-            return ops.pack_weight(w.float(), b.float())
-
         def tail():
             w, b = self.folded_tail(torch.float64)
             return ops.pack_fc_rows(w.float()), b.float().contiguous()
-        h = ops.conv2d(x.float().contiguous(), self._packed('stem', stem, self.conv1.weight, *_bn_deps(self.bn1)), in_nchw=True)
+        h = conv_hip(self, 'stem', folded_layer(self.conv1, self.bn1), x.float().contiguous(), in_nchw=True)
         h = ops.prelu_maxpool2(h, prelu_slope(self, self.prelu))
         for blk in self._blocks():
             h = blk.run_hip(h)
-        wp, bias = self._packed('tail', tail, self.fc5.weight, self.fc5.bias, *_bn_deps(self.bn4), *_bn_deps(self.bn5))
+        wp, bias = self._packed('tail', tail, self.fc5.weight, self.fc5.bias, *bn_deps(self.bn4), *bn_deps(self.bn5))
         return ops.fc_rows(h.view(h.shape[0], -1), wp, bias)
 
     def forward_host(self, x):

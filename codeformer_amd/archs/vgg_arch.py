@@ -15,7 +15,7 @@ CPU tensors run `forward_host` (stock torch ops: the reference's forward).  CUDA
   * every conv asks ops.conv_code(ops.WINOGRAD, ...): exact-fp32 Winograd F(2x2,3x3) on whole 8x16 patches, the general fp32 kernel elsewhere
     (`winograd_f43 = True` requests ops.WINOGRAD_F43 instead: faster from 64x64 up, larger error -- opt-in, see profiles/NOTES.md); on the
     general kernel a layer of more than 128 input channels runs per 128 channels, the parts added by the residual epilogue (_conv);
-  * a BatchNorm is folded into the packed weight and bias in float64, rounded once (arcface_arch.fold_conv_bn); a requested `convX_Y` of a
+  * a BatchNorm is folded into the packed weight and bias in float64, rounded once (folded.fold_conv_bn); a requested `convX_Y` of a
     `_bn` type (the value BEFORE the BatchNorm) is a second launch with the unfolded weight;
   * ReLU is cf_relu (in place unless the pre-ReLU tensor was requested) or rides in cf_relu_maxpool2, which also hands out the full-size
     ReLU tensor when `reluX_Y` in front of a pool was requested.
@@ -31,7 +31,7 @@ from torch import nn
 
 from .. import ops
 from ..utils.registry import ARCH_REGISTRY
-from .arcface_arch import _bn_deps, bn_affine, fold_conv_bn
+from .folded import folded_layer
 from .hip_module import HipModule
 
 VGG_PRETRAIN_PATH = 'experiments/pretrained_models/vgg19-dcbb9e9d.pth'
@@ -199,16 +199,14 @@ class VGGFeatureExtractor(HipModule):
         code = ops.conv_code(ops.WINOGRAD_F43 if self.winograd_f43 else ops.WINOGRAD, cin, cout, x.shape[1], x.shape[2])
         step = CHAIN_CIN if (code == 0 and cin > CHAIN_CIN and cin % CHAIN_CIN == 0) else cin
 
+        fold, deps = folded_layer(conv, bn)
+
         def build(k0):
-            if bn is None:
-                w, b = conv.weight.detach(), conv.bias.detach()
-            else:
-                w, t = fold_conv_bn(conv, bn, torch.float64)
-                w, b = w.float(), (t + bn_affine(bn, torch.float64)[0] * conv.bias.detach().double()).float()
-            return ops.pack_weight(w[:, k0:k0 + step].contiguous(), b if k0 == 0 else None, bf16=code)
+            w, b = fold()
+            return ops.pack_weight(w.float()[:, k0:k0 + step].contiguous(), b.float() if k0 == 0 else None, bf16=code)
         y = None
         for k0 in range(0, cin, step):
-            pw = self._packed((name, code, bn is not None, k0, step), lambda: build(k0), conv.weight, conv.bias, *([] if bn is None else _bn_deps(bn)))
+            pw = self._packed((name, code, bn is not None, k0, step), lambda: build(k0), *deps)
             xs = x if step == cin else x[..., k0:k0 + step]
             y = ops.conv2d(xs, pw) if y is None else ops.conv2d(xs, pw, epilogue=ops.EPI_RESIDUAL, res=y)
         return y

@@ -18,7 +18,7 @@ import torch
 from torch.nn import functional as F
 
 from .... import ops
-from ....archs.arcface_arch import _bn_deps, fold_conv_bn
+from ....archs.folded import conv_hip, fold_conv_bn, folded_layer, pointwise_hip, stem7x7_hip
 from ....archs.hip_module import HipModule
 from .retinaface_utils import PriorBox
 
@@ -109,39 +109,15 @@ class HipDetector(HipModule):
         self.__dict__['net'] = net      # (not a registered child: the detector is an attribute of `net`)
         self.__dict__['_priors'] = {}
 
-    # ---- packed layers ----------------------------------------------------------------------------------------------------------
-    # a layer is (fold, deps): fold() -> (weight, bias) in float64, deps the tensors the packed weight is cached against.  Both kinds go
-    # through arcface_arch.fold_conv_bn, the ConvUnits by their own folded().
-    @staticmethod
-    def _pair(conv, bn):
-        return (lambda: fold_conv_bn(conv, bn, torch.float64)), [conv.weight, *_bn_deps(bn)]
-
-    @staticmethod
-    def _unit(u):
-        return (lambda: u.folded(torch.float64)), u.fold_deps()
-
-    def _pw1(self, key, layer):
-        def build():
-            w, b = layer[0]()
-            return ops.pack_pointwise(w.float(), b.float())
-        return self._packed(key, build, *layer[1])
-
-    def _conv3(self, key, layer, x, stride=1, out=None):
-        """relu(bn(conv 3x3(x))) on the general fp32 kernel, one launch."""
-        def build():
-            w, b = layer[0]()
-            return ops.pack_weight(w.float().contiguous(), b.float())
-        geom = dict(stride=2, pad_lo=1) if stride == 2 else {}
-        return ops.conv2d(x, self._packed(key, build, *layer[1]), epilogue=ops.EPI_PRELU, sft_w=0.0, out=out, **geom)
-
+    # ---- layers: folded.folded_layer pairs, a ConvUnit's by its own layer() ---------------------------------------------------------------------
     def _block(self, key, blk, x):
         s = blk.stride
         idt = x
         if blk.downsample is not None:
-            idt = ops.pointwise(x, self._pw1((key, 'down'), self._pair(blk.downsample[0], blk.downsample[1])), step=s)
-        y = ops.pointwise(x, self._pw1((key, 1), self._pair(blk.conv1, blk.bn1)), relu=True)
-        y = self._conv3((key, 2), self._pair(blk.conv2, blk.bn2), y, stride=s)
-        return ops.pointwise(y, self._pw1((key, 3), self._pair(blk.conv3, blk.bn3)), res=idt, relu=True)
+            idt = ops.pointwise(x, pointwise_hip(self, (key, 'down'), folded_layer(blk.downsample[0], blk.downsample[1])), step=s)
+        y = ops.pointwise(x, pointwise_hip(self, (key, 1), folded_layer(blk.conv1, blk.bn1)), relu=True)
+        y = conv_hip(self, (key, 2), folded_layer(blk.conv2, blk.bn2), y, stride=s, slope=0.0)
+        return ops.pointwise(y, pointwise_hip(self, (key, 3), folded_layer(blk.conv3, blk.bn3)), res=idt, relu=True)
 
     def _ssh(self, lv, x):
         ssh = getattr(self.net, f'ssh{lv + 1}')
@@ -155,7 +131,7 @@ class HipDetector(HipModule):
         buf = torch.empty((B, H, W, c + 2 * q), dtype=torch.float32, device=x.device)
 
         def run(n, x, out=None):
-            return self._conv3(('ssh', lv, n), self._unit(u[n]), x, out=out)
+            return conv_hip(self, ('ssh', lv, n), u[n].layer(), x, slope=0.0, out=out)
         run('conv3X3', x, buf[..., :c])
         mid = run('conv5X5_1', x)
         run('conv5X5_2', mid, buf[..., c:c + q])
@@ -171,12 +147,7 @@ class HipDetector(HipModule):
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
             raise ValueError(f'HIP detector: a float32 (B,3,H,W) CUDA tensor, got {x.dtype} {tuple(x.shape)} on {x.device}')
         body = net.body
-
-        def stem():
-            w, b = fold_conv_bn(body.conv1, body.bn1, torch.float64)
-            return ops.pack_stem7x7(w.float()), b.float().contiguous()
-        wp, b = self._packed('stem', stem, body.conv1.weight, *_bn_deps(body.bn1))
-        h = ops.maxpool3s2(ops.stem7x7s2(x.contiguous(), wp, b))
+        h = ops.maxpool3s2(stem7x7_hip(self, 'stem', body.conv1, body.bn1, x))
         taps = []
         for li, layer in enumerate((body.layer1, body.layer2, body.layer3, body.layer4)):
             for bi, blk in enumerate(layer):
@@ -186,15 +157,13 @@ class HipDetector(HipModule):
         for n in ('output1', 'output2', 'output3', 'merge1', 'merge2'):
             if getattr(fpn, n).slope != 0.0:
                 raise NotImplementedError(f'HIP detector: FPN.{n} has LeakyReLU({getattr(fpn, n).slope}); the kernels fuse ReLU (out_channel > 64)')
-        o1, o2, o3 = (ops.pointwise(t, self._pw1(('fpn', i), self._unit(getattr(fpn, f'output{i + 1}'))), relu=True) for i, t in enumerate(taps[1:]))
-        o2 = self._conv3(('fpn', 'merge2'), self._unit(fpn.merge2), ops.nearest_add(o2, o3))
-        o1 = self._conv3(('fpn', 'merge1'), self._unit(fpn.merge1), ops.nearest_add(o1, o2))
+        o1, o2, o3 = (ops.pointwise(t, pointwise_hip(self, ('fpn', i), getattr(fpn, f'output{i + 1}').layer()), relu=True) for i, t in enumerate(taps[1:]))
+        o2 = conv_hip(self, ('fpn', 'merge2'), fpn.merge2.layer(), ops.nearest_add(o2, o3), slope=0.0)
+        o1 = conv_hip(self, ('fpn', 'merge1'), fpn.merge1.layer(), ops.nearest_add(o1, o2), slope=0.0)
         out = []
         for lv, o in enumerate((o1, o2, o3)):
-            def build(lv=lv):
-                w, b = fold_heads(net, lv, torch.float64)
-                return ops.pack_pointwise(w.float(), b.float())
-            out.append(ops.pointwise(self._ssh(lv, o), self._packed(('heads', lv), build, *_head_deps(net, lv))))
+            head = (lambda lv=lv: fold_heads(net, lv, torch.float64)), _head_deps(net, lv)
+            out.append(ops.pointwise(self._ssh(lv, o), pointwise_hip(self, ('heads', lv), head)))
         return out
 
     def priors(self, h, w, device):

@@ -12,7 +12,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from ....archs.arcface_arch import fold_conv_bn
+from ....archs.folded import folded_layer
 
 
 class ConvUnit(nn.Sequential):
@@ -25,15 +25,17 @@ class ConvUnit(nn.Sequential):
         super().__init__(*layers)
         self.slope = slope
 
+    def layer(self):
+        """The unit as a folded.folded_layer (the one folding routine of the project): the HIP path folds in float64 and rounds once."""
+        return folded_layer(self[0], self[1])
+
     def folded(self, dtype=None):
-        """(weight, bias) of the equivalent bias-carrying convolution in eval mode, evaluated in `dtype` (default: the parameters'): the one
-        folding routine of the project (arcface_arch.fold_conv_bn).  The HIP path asks for float64 and rounds once."""
-        return fold_conv_bn(self[0], self[1], dtype)
+        """(weight, bias) of the equivalent bias-carrying convolution in eval mode, evaluated in `dtype` (default: the parameters')."""
+        return self.layer()[0](dtype)
 
     def fold_deps(self):
         """The tensors a cached folded weight depends on."""
-        bn = self[1]
-        return [self[0].weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        return self.layer()[1]
 
 
 def conv_bn(inp, oup, stride=1, leaky=0):                 # retinaface_net.py:6-9

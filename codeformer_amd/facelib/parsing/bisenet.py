@@ -9,7 +9,7 @@ weights.
 CPU tensors run `forward_host` (stock torch ops: the reference's forward, any size).  CUDA tensors run the device dataflow, value-only, eval
 mode, channels-last fp32 with IEEE-fp32 MFMA operands (ops.pack_weight defaults):
   * ResNet18: see resnet.py (7x7 stem kernel, 3x3 / stride-2 max-pool, BasicBlocks on ops.conv2d with BatchNorm folded);
-  * AttentionRefinementModule: 3x3 conv + bn + ReLU (resnet.conv_hip), cf_se_pool,
+  * AttentionRefinementModule: 3x3 conv + bn + ReLU (folded.conv_hip), cf_se_pool,
     then the single-layer gate sigmoid(W'p + b') with bn_atten folded (cf_pooled_fc).  arm32: feat * gate + the per-image conv_avg row
     (cf_scale_add_row; the nearest upsampling of a 1x1 map is a row broadcast); arm16: feat * gate + feat32_up (cf_se_scale_res_prelu, slope 1);
   * conv_avg: the 1x1 conv + bn + ReLU on the pooled feat32 is cf_pooled_fc with ReLU;
@@ -34,9 +34,9 @@ from torch import nn
 from torch.nn import functional as F
 
 from ... import ops
-from ...archs.arcface_arch import _bn_deps, _need_eval, fold_conv_bn
+from ...archs.folded import bn_deps, centre_tap, conv_hip, fold_conv_bn, folded_layer, need_eval
 from ...archs.hip_module import HipModule
-from .resnet import NetPart, ResNet18, conv_hip
+from .resnet import NetPart, ResNet18
 
 LEVEL = 32   # the device path takes heights and widths that are multiples of it: every nearest interpolation is then exactly x2
 
@@ -52,23 +52,22 @@ def up2x_conv_folded(x, w, b):
     return out
 
 
-def conv1x1_hip(mod, key, x, fold, deps, x2=None, relu=False):
-    """[relu](1x1 conv) of channels-last x (x2 concatenated after it).  fold() -> (weight (cout,cin,1,1), bias or None) in float32; cout % 4 == 0.
+def conv1x1_hip(mod, key, layer, x, x2=None, relu=False):
+    """[relu](1x1 conv) of channels-last x (x2 concatenated after it); layer: a folded.folded_layer with a (cout,cin,1,1) weight, cout % 4 == 0.
     The 1x1 kernel tiles the pixels of an image by 128 or 256 and the channels by 64: it takes images of a multiple of 256 pixels and cout % 64
-    == 0 (512x512 faces: 4096 pixels at 1/8).  Anything else -- the 20 class maps, small or odd-sized levels -- runs on the general 3x3 kernel
-    with the weight as the centre tap (the eight other taps add 0 * x = 0 to a finite sum).  The rule reads the per-image shape only."""
-    def build(embed):
+    == 0 (512x512 faces: 4096 pixels at 1/8); it has no activation epilogue (cf_relu follows, in place).  Anything else -- the 20 class maps,
+    small or odd-sized levels -- runs on the general 3x3 kernel with the weight as the centre tap.  The rule reads the per-image shape only."""
+    fold, deps = layer
+    if (x.shape[1] * x.shape[2]) % 256 != 0 or deps[0].shape[0] % 64 != 0:
+        def fold3():
+            w, b = fold()
+            return centre_tap(w), b
+        return conv_hip(mod, (key, True), (fold3, deps), x, x2=x2, slope=0.0 if relu else None)
+
+    def build():
         w, b = fold()
-        if embed:
-            w3 = w.new_zeros(w.shape[0], w.shape[1], 3, 3)
-            w3[:, :, 1, 1] = w[:, :, 0, 0]
-            w = w3
-        return ops.pack_weight(w.contiguous(), b)
-    embed = (x.shape[1] * x.shape[2]) % 256 != 0 or deps[0].shape[0] % 64 != 0
-    pw = mod._packed((key, embed), lambda: build(embed), *deps)
-    if embed and relu:   # (the PReLU epilogues exist on the plain 3x3 instantiations only)
-        return ops.conv2d(x, pw, x2=x2, epilogue=ops.EPI_PRELU, sft_w=0.0)
-    y = ops.conv2d(x, pw, x2=x2)
+        return ops.pack_weight(w.float(), None if b is None else b.float())
+    y = ops.conv2d(x, mod._packed((key, False), build, *deps), x2=x2)
     return ops.relu(y, inplace=True) if relu else y
 
 
@@ -80,11 +79,11 @@ class ConvBNReLU(NetPart):
         self.conv = nn.Conv2d(in_chan, out_chan, kernel_size=ks, stride=stride, padding=padding, bias=False)
         self.bn = nn.BatchNorm2d(out_chan)
 
-    def folded(self, dtype=None):
-        return fold_conv_bn(self.conv, self.bn, dtype)
+    def layer(self):
+        return folded_layer(self.conv, self.bn)
 
-    def _deps(self):
-        return [self.conv.weight, *_bn_deps(self.bn)]
+    def folded(self, dtype=None):
+        return self.layer()[0](dtype)
 
     def forward_folded(self, x, up2x=False):
         w, b = self.folded()
@@ -94,27 +93,24 @@ class ConvBNReLU(NetPart):
 
     def run_hip(self, x, up2x=False, x2=None):
         """Channels-last.  up2x: nearest x2 first; x2: a second tensor concatenated after x (1x1 only)."""
-        _need_eval(self)
+        need_eval(self)
         ks, st, pad = self.conv.kernel_size, self.conv.stride, self.conv.padding
         if ks == (1, 1) and st == (1, 1) and pad == (0, 0) and not up2x:
-            def fold():
-                w, b = self.folded(torch.float64)
-                return w.float(), b.float()
-            return conv1x1_hip(self, 'w1x1', x, fold, self._deps(), x2=x2, relu=True)
+            return conv1x1_hip(self, 'w1x1', self.layer(), x, x2=x2, relu=True)
         if ks != (3, 3) or pad != (1, 1) or st not in ((1, 1), (2, 2)) or x2 is not None or (up2x and st != (1, 1)):
             raise NotImplementedError(f'ConvBNReLU on HIP: 3x3 pad 1 at stride 1 or 2, or 1x1 pad 0 at stride 1; got ks {ks}, stride {st}, padding {pad}')
-        return conv_hip(self, 'w', x, lambda: self.folded(torch.float64), self._deps(), stride=st[0], up2x=up2x)
+        return conv_hip(self, 'w', self.layer(), x, stride=st[0], up2x=up2x, slope=0.0)
 
     def fc_hip(self, pooled):
         """A 1x1 ConvBNReLU on a 1x1 map: (B,C) pooled rows -> (B,out_chan)."""
-        _need_eval(self)
+        need_eval(self)
         if self.conv.kernel_size != (1, 1):
             raise NotImplementedError('ConvBNReLU.fc_hip: a 1x1 convolution')
 
         def build():
             w, b = self.folded(torch.float64)
             return w.float().flatten(1).contiguous(), b.float().contiguous()
-        return ops.pooled_fc(pooled, *self._packed('fc', build, *self._deps()), act='relu')
+        return ops.pooled_fc(pooled, *self._packed('fc', build, *self.layer()[1]), act='relu')
 
     def forward_host(self, x):
         return F.relu(self.bn(self.conv(x)))
@@ -144,7 +140,7 @@ class BiSeNetOutput(NetPart):
             w = self.conv_out.weight.detach().float()
             pad = (w.shape[0] + 3) // 4 * 4 - w.shape[0]
             return (torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0) if pad else w), None
-        return conv1x1_hip(self, 'out', feat, fold, [self.conv_out.weight]), feat
+        return conv1x1_hip(self, 'out', (fold, [self.conv_out.weight]), feat), feat
 
     def forward_host(self, x):
         feat = self.conv.forward_host(x)
@@ -176,13 +172,13 @@ class AttentionRefinementModule(NetPart):
 
     def feat_gate_hip(self, x):
         """Channels-last x -> (feat (B,h,w,C), gate (B,C))."""
-        _need_eval(self)
+        need_eval(self)
         feat = self.conv.run_hip(x)
 
         def build():
             w, b = self.folded_gate(torch.float64)
             return w.float().contiguous(), b.float().contiguous()
-        w, b = self._packed('gate', build, self.conv_atten.weight, *_bn_deps(self.bn_atten))
+        w, b = self._packed('gate', build, self.conv_atten.weight, *bn_deps(self.bn_atten))
         return feat, ops.pooled_fc(ops.se_pool(feat), w, b, act='sigmoid')
 
     def forward_host(self, x):
@@ -268,7 +264,7 @@ class FeatureFusionModule(NetPart):
 def check_size(mod, shape):
     """What the device path refuses before it touches a device: training mode (RuntimeError), anything but (B,3,H,W) with H and W multiples
     of 32 (ValueError)."""
-    _need_eval(mod)
+    need_eval(mod)
     if len(shape) != 4 or shape[1] != 3 or shape[0] < 1 or shape[2] < LEVEL or shape[3] < LEVEL or shape[2] % LEVEL or shape[3] % LEVEL:
         raise ValueError(f'BiSeNet on HIP takes (B,3,H,W) with H % {LEVEL} == 0 and W % {LEVEL} == 0 (H, W >= {LEVEL}: every level of the context '
                          f'path is then exactly x2 of the next), got {tuple(shape)}; forward_host takes any size')

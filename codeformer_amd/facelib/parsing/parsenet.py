@@ -24,6 +24,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from ... import ops
+from ...archs.folded import bn_deps, need_eval
 from ...archs.hip_module import HipModule
 
 _SLOPE = 0.2
@@ -96,7 +97,7 @@ class ConvLayer(HipModule):
 
     def packed(self, cout_to=None):
         bn = self.norm.norm if isinstance(self.norm.norm, nn.BatchNorm2d) else None
-        deps = [self.conv2d.weight, self.conv2d.bias] + ([bn.weight, bias_of(bn), bn.running_mean, bn.running_var] if bn else [])
+        deps = [self.conv2d.weight, self.conv2d.bias] + (bn_deps(bn) if bn else [])
 
         def build():
             w, b = self._folded(cout_to)
@@ -104,8 +105,7 @@ class ConvLayer(HipModule):
         return self._packed(('w', cout_to, self.scale), build, *deps)
 
     def run_hip(self, x, *, epilogue=None, cout_to=None, **kw):
-        if self.training:
-            raise RuntimeError('ParseNet on HIP folds BatchNorm: call .eval() first')
+        need_eval(self)
         if self.conv2d.kernel_size != (3, 3) or not self.use_pad:
             raise NotImplementedError('HIP path: reflection-padded 3x3 convolutions')
         if epilogue is None:
@@ -129,10 +129,6 @@ class ConvLayer(HipModule):
 
     def forward_nhwc(self, x):
         return self.run_hip(x)
-
-
-def bias_of(bn):
-    return bn.bias
 
 
 class ResidualBlock(HipModule):

@@ -9,8 +9,8 @@ own):
   * stem: cf_stem7x7s2 (7x7 / stride 2 / pad 3 on the NCHW image, bn1 folded in float64 and rounded once, ReLU in the epilogue), then
     cf_maxpool3s2 (3x3 / stride 2 / pad 1, padding -inf);
   * BasicBlock: conv1 + bn1 + ReLU and conv2 + bn2 + shortcut + ReLU are one ops.conv2d launch each on the general fp32 kernel (stride 2:
-    stride=2, pad_lo=1); ReLU is the PReLU epilogue with slope 0.0 (CF_EPI_PRELU / CF_EPI_RES_PRELU: x > 0 ? x : 0 * x);
-  * the 1x1 stride-s `downsample` conv runs as a 3x3 stride-s conv whose only non-zero tap is the centre (arcface_arch.fold_conv_bn(embed3=True)):
+    one padded row / column on every side); ReLU is the PReLU epilogue with slope 0.0 (CF_EPI_PRELU / CF_EPI_RES_PRELU: x > 0 ? x : 0 * x);
+  * the 1x1 stride-s `downsample` conv runs as a 3x3 stride-s conv whose only non-zero tap is the centre (folded.fold_conv_bn(embed3=True)):
     the eight other taps add 0 * x = 0 to a finite sum;
   * long accumulation chains: the general fp32 kernel adds all 9 * cin products of an output in one chain of MFMA accumulations, and layer3 /
     layer4 reach K = 4608.  VGGFeatureExtractor had to run such layers per 128 input channels to meet the 8x gate; here the gate does not need
@@ -23,35 +23,13 @@ from torch import nn
 from torch.nn import functional as F
 
 from ... import ops
-from ...archs.arcface_arch import _bn_deps, _need_eval, fold_conv_bn
+from ...archs.folded import conv_hip, fold_conv_bn, folded_layer, need_eval, stem7x7_hip
 from ...archs.hip_module import HipModule
 
 
 def conv3x3(in_planes, out_planes, stride=1):
     """3x3 convolution, padding 1, no bias (resnet.py:5-7)."""
     return nn.Conv2d(in_planes, out_planes, kernel_size=3, stride=stride, padding=1, bias=False)
-
-
-def conv_hip(mod, key, x, fold, deps, *, res=None, relu=True, stride=1, up2x=False):
-    """[relu](conv(x) + bias [+ res]) of the channels-last x on the general fp32 kernel, one launch.  fold() -> (weight (cout,cin,3,3), bias or
-    None) in float64; the packed weight is cached on `mod` under `key` until one of `deps` changes.  stride 2: one padded row / column on every
-    side; up2x: nearest x2 first (the folded sub-pixel form, whose instantiations have no ReLU epilogue: cf_relu follows, in place)."""
-    if stride not in (1, 2):
-        raise NotImplementedError(f'HIP path: stride 1 or 2, got {stride}')
-
-    def build():
-        w, b = fold()
-        return ops.pack_weight(w.float().contiguous(), None if b is None else b.float(), up2x=up2x)
-    pw = mod._packed(key, build, *deps)
-    if up2x:
-        y = ops.conv2d(x, pw, upsample=True, pad_mode=ops.PAD_ZERO, **({} if res is None else dict(epilogue=ops.EPI_RESIDUAL, res=res)))
-        return ops.relu(y, inplace=True) if relu else y
-    geom = dict(stride=2, pad_lo=1) if stride == 2 else {}
-    if relu:
-        epi = dict(epilogue=ops.EPI_PRELU, sft_w=0.0) if res is None else dict(epilogue=ops.EPI_RES_PRELU, res=res, sft_w=0.0)
-    else:
-        epi = {} if res is None else dict(epilogue=ops.EPI_RESIDUAL, res=res)
-    return ops.conv2d(x, pw, **geom, **epi)
 
 
 class NetPart(HipModule):
@@ -79,28 +57,25 @@ class BasicBlock(NetPart):
         if in_chan != out_chan or stride != 1:
             self.downsample = nn.Sequential(nn.Conv2d(in_chan, out_chan, kernel_size=1, stride=stride, bias=False), nn.BatchNorm2d(out_chan))
 
-    def folded(self, dtype=None):
-        """dict: conv1 / conv2 (weight, bias) with bn1 / bn2 folded; shortcut (3x3 centre-tap weight, bias) or None."""
-        sc = None if self.downsample is None else fold_conv_bn(self.downsample[0], self.downsample[1], dtype, embed3=True)
-        return {'conv1': fold_conv_bn(self.conv1, self.bn1, dtype), 'conv2': fold_conv_bn(self.conv2, self.bn2, dtype), 'shortcut': sc}
+    def layers(self):
+        """The folded.folded_layer of conv1, conv2 and the shortcut (the 1x1 as the centre tap of a 3x3), the last None without a `downsample`."""
+        sc = None if self.downsample is None else folded_layer(self.downsample[0], self.downsample[1], embed3=True)
+        return {'conv1': folded_layer(self.conv1, self.bn1), 'conv2': folded_layer(self.conv2, self.bn2), 'shortcut': sc}
 
     def forward_folded(self, x):
         """The device dataflow on stock torch ops (NCHW), in the parameters' dtype."""
-        f = self.folded()
+        f = {k: None if v is None else v[0](None) for k, v in self.layers().items()}   # (weight, bias) in the parameters' dtype
         s = self.conv1.stride[0]
         h = F.relu(F.conv2d(x, *f['conv1'], stride=s, padding=1))
         res = x if f['shortcut'] is None else F.conv2d(x, *f['shortcut'], stride=s, padding=1)
         return F.relu(F.conv2d(h, *f['conv2'], padding=1) + res)
 
     def run_hip(self, x):
-        _need_eval(self)
-        s = self.conv1.stride[0]
-        h = conv_hip(self, 'conv1', x, lambda: self.folded(torch.float64)['conv1'], [self.conv1.weight, *_bn_deps(self.bn1)], stride=s)
-        res = x
-        if self.downsample is not None:
-            res = conv_hip(self, 'shortcut', x, lambda: self.folded(torch.float64)['shortcut'], [self.downsample[0].weight, *_bn_deps(self.downsample[1])],
-                           relu=False, stride=s)
-        return conv_hip(self, 'conv2', h, lambda: self.folded(torch.float64)['conv2'], [self.conv2.weight, *_bn_deps(self.bn2)], res=res)
+        need_eval(self)
+        s, ly = self.conv1.stride[0], self.layers()
+        h = conv_hip(self, 'conv1', ly['conv1'], x, stride=s, slope=0.0)
+        res = x if self.downsample is None else conv_hip(self, 'shortcut', ly['shortcut'], x, stride=s)
+        return conv_hip(self, 'conv2', ly['conv2'], h, res=res, slope=0.0)
 
     def forward_host(self, x):
         residual = F.relu(self.bn1(self.conv1(x)))
@@ -127,9 +102,6 @@ class ResNet18(HipModule):
         self.layer3 = create_layer_basic(128, 256, bnum=2, stride=2)
         self.layer4 = create_layer_basic(256, 512, bnum=2, stride=2)
 
-    def folded_stem(self, dtype=None):
-        return fold_conv_bn(self.conv1, self.bn1, dtype)
-
     def _layers(self, x, method):
         """layer1 .. layer4 through every block's `method` (a block's own forward would pick its path by the device); the last three outputs."""
         feats = []
@@ -141,18 +113,13 @@ class ResNet18(HipModule):
 
     def forward_folded(self, x):
         """The device dataflow on stock torch ops, in the parameters' dtype."""
-        h = F.max_pool2d(F.relu(F.conv2d(x, *self.folded_stem(), stride=2, padding=3)), 3, 2, 1)
+        h = F.max_pool2d(F.relu(F.conv2d(x, *fold_conv_bn(self.conv1, self.bn1), stride=2, padding=3)), 3, 2, 1)
         return self._layers(h, 'forward_folded')
 
     def stem_hip(self, x):
         """(B,3,H,W) NCHW -> the stem's ReLU output (B,ceil(H/2),ceil(W/2),64) channels-last, before the max-pool."""
-        _need_eval(self)
-
-        def build():
-            w, b = self.folded_stem(torch.float64)
-            return ops.pack_stem7x7(w.float()), b.float().contiguous()
-        wp, b = self._packed('stem', build, self.conv1.weight, *_bn_deps(self.bn1))
-        return ops.stem7x7s2(x.float().contiguous(), wp, b)
+        need_eval(self)
+        return stem7x7_hip(self, 'stem', self.conv1, self.bn1, x.float())
 
     def run_hip(self, x):
         """NCHW image -> the three features, channels-last."""

@@ -8,6 +8,7 @@ from torch.nn import functional as F
 import arcface_ref as R
 from codeformer_amd import metrics as M
 from codeformer_amd.archs import arcface_arch as A
+from codeformer_amd.archs.folded import need_eval
 
 
 @pytest.fixture(scope='module')
@@ -203,7 +204,7 @@ def test_what_the_hip_path_refuses(nets):
     with pytest.raises(RuntimeError):
         train.check_device_call((3, 1, 128, 128))
     with pytest.raises(RuntimeError):
-        A._need_eval(train.layer1[0])
+        need_eval(train.layer1[0])
     with pytest.raises(TypeError):
         A.ResNetArcFace(A.BasicBlock, [1, 1, 1, 1])   # as in the reference: _make_layer passes use_se to every block
 

@@ -85,7 +85,7 @@ def test_hip_is_refused_where_it_cannot_run(RetinaFace, monkeypatch):
 
 
 def test_conv_unit_folded_is_the_shared_routine(RetinaFace):
-    from codeformer_amd.archs.arcface_arch import fold_conv_bn
+    from codeformer_amd.archs.folded import fold_conv_bn
     net = R.build(RetinaFace)
     for u in (net.fpn.output2, net.fpn.merge1, net.ssh2.conv7x7_3):
         for dt in (None, torch.float64):

@@ -149,15 +149,18 @@ def main():
         # the convolutions: ArcFace form beside the plain ops.conv2d of the same shape
         seen = set()
         h = torch.randn(B, 64, 64, 64, device='cuda', generator=gen)   # what the stem hands to layer1
+        def packed(blk, which):
+            w, b = blk.layer(which)[0]()
+            return ops.pack_weight(w.float(), b.float())
         for blk in net._blocks():
             s, tb = blk._pre_tables(B)
             geom = dict(stride=2, pad_lo=1) if blk.stride == 2 else {}
-            res = h if blk.downsample is None else ops.conv2d(h, blk._pw('shortcut'), **geom)
-            mid = ops.conv2d(h, blk._pw('conv1'), prologue=ops.PRO_AFFINE, scale=s, shift=tb, epilogue=ops.EPI_PRELU, sft_w=0.25)
-            layers = [('conv1: bn0 prologue, PReLU epilogue', h, blk._pw('conv1'), dict(prologue=ops.PRO_AFFINE, scale=s, shift=tb, epilogue=ops.EPI_PRELU, sft_w=0.25), {}),
-                      ('conv2: residual + PReLU epilogue', mid, blk._pw('conv2'), dict(epilogue=ops.EPI_RES_PRELU, res=res, sft_w=0.25), geom)]
+            res = h if blk.downsample is None else ops.conv2d(h, packed(blk, 'shortcut'), **geom)
+            mid = ops.conv2d(h, packed(blk, 'conv1'), prologue=ops.PRO_AFFINE, scale=s, shift=tb, epilogue=ops.EPI_PRELU, sft_w=0.25)
+            layers = [('conv1: bn0 prologue, PReLU epilogue', h, packed(blk, 'conv1'), dict(prologue=ops.PRO_AFFINE, scale=s, shift=tb, epilogue=ops.EPI_PRELU, sft_w=0.25), {}),
+                      ('conv2: residual + PReLU epilogue', mid, packed(blk, 'conv2'), dict(epilogue=ops.EPI_RES_PRELU, res=res, sft_w=0.25), geom)]
             if blk.downsample is not None:
-                layers.append(('shortcut: 1x1 as the centre tap of a 3x3', h, blk._pw('shortcut'), {}, geom))
+                layers.append(('shortcut: 1x1 as the centre tap of a 3x3', h, packed(blk, 'shortcut'), {}, geom))
             for what, inp, pw_, fused, g2 in layers:
                 key = (what, tuple(inp.shape), pw_.cout, blk.stride)
                 if key not in seen:
@@ -166,7 +169,7 @@ def main():
                     report(what, lambda: ops.conv2d(inp, pw_, **fused, **g2), impl='arcface form', **tag)
                     if fused:
                         report(what, lambda: ops.conv2d(inp, pw_, **g2), impl='ops.conv2d, no prologue / epilogue', **tag)
-            h = ops.conv2d(mid, blk._pw('conv2'), epilogue=ops.EPI_RES_PRELU, res=res, sft_w=0.25, **geom)
+            h = ops.conv2d(mid, packed(blk, 'conv2'), epilogue=ops.EPI_RES_PRELU, res=res, sft_w=0.25, **geom)
 
 
 if __name__ == '__main__':
